@@ -27,6 +27,7 @@ Rank 0 prints ONE JSON line.  Besides the contract's fields it carries `roofline
 `rooflines` (every HBM-bound kernel of the step, necessary bytes / time / 8 TB/s -- a fraction above 1 is impossible by
 construction), `cpu_baseline`, and at N = 1 the extra legs `aperture_premade_cubes` (the per-target stage alone, SURVEY 8d's
 reading), `linpsf` (BASELINE configs[3]) and `end_to_end` (cubes start in pinned host memory: H2D overlapped with compute).
+`--dump-outputs DIR` writes what the last timed step computed under DIR (benchlib/dump.py), to compare two builds output for output.
 """
 
 import os
@@ -74,7 +75,13 @@ def parse_args(argv=None):
 	p.add_argument('--linpsf-drift', type=int, default=1, help='1: the LinPSF leg also runs the scene with a pointing drift (0 = skip: the profiling passes, whose per-kernel means it would mix)')
 	p.add_argument('--frames-large', type=int, default=10000, help='targets of the second frames-to-results leg, on a 1024 x 1024 stack (0 = skip)')
 	p.add_argument('--frames-targets', type=int, default=2500, help='targets of the frames-to-results leg on a 512 x 512 stack (0 = skip)')
-	return p.parse_args(argv)
+	p.add_argument('--dump-outputs', metavar='DIR', default=None, help='after the timed steps, write what the last one computed (the '
+		'arrays a caller of the step receives; a fixed sample of targets above 64 MB) as DIR/<name>.npy, finite values only: where '
+		'a value is NaN or infinite, DIR/<name>_nonfinite.npy holds its code (benchlib/dump.py)')
+	args = p.parse_args(argv)
+	if args.steps < 1 or args.warmup < 0:
+		p.error('--steps must be at least 1 and --warmup at least 0')
+	return args
 
 
 
@@ -126,6 +133,8 @@ def main():
 	run = sharded.ShardedRun(worker, Nt * world, rank=rank, world=world, group=group,
 		gather='none' if args.no_gather else 'auto', when='step', shared_device=shared_device, compact=not args.no_compact)
 	cubes, batch, lin = worker.cubes, worker.batch, worker.lin
+	if args.dump_outputs and world > 1 and not run.gathers:
+		raise SystemExit('--dump-outputs needs the gather of the output block to rank 0 (no --no-gather)')
 
 	def device_sync():
 		run.sync()
@@ -164,6 +173,9 @@ def main():
 	prof = ctx.profile_report()
 	work = worker.works[run.last_buffer if run.last_buffer is not None else 0]
 	per_step_gather_ms = run.gather_ms or per_step_gather_ms
+	if args.dump_outputs and rank == 0:
+		from benchlib.dump import dump_outputs
+		dump_outputs(run.collect(), args.dump_outputs, run.n_total)
 
 	result = None
 	if rank == 0:

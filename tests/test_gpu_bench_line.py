@@ -31,6 +31,30 @@ def test_single_gpu_line(tmp_path):
 	assert full['value'] == pytest.approx(d['value'], rel=1e-5) and 'kernels' in full
 
 
+def test_dump_outputs_of_the_last_step(tmp_path):
+	"""--dump-outputs: the arrays of the last timed step in float32 / float64, every file finite (the NaN of the light curves in
+	their _nonfinite files), under 64 MB, the same from run to run (seeded inputs); --steps sets the number of timed steps."""
+	import numpy as np
+	from benchlib import dump
+	dumps = []
+	for k, steps in enumerate(('2', '4')):
+		d = str(tmp_path / str(k))
+		line = _run([sys.executable, 'bench.py', '--gpus', '1', '--dump-outputs', d] + SMALL + ['--steps', steps], tmp_path)
+		assert line['steps'] == int(steps) and line['ms_per_step'] > 0
+		kernels = json.load(open(os.path.join(ROOT, bl.LEGS_FILE)))['kernels']    # launches in the timed region: one of each per step
+		assert kernels['tp_bkg_stamp_sum_kernel']['launches'] == int(steps) and kernels['tp_aperture_fused_kernel']['launches'] == int(steps)
+		dumps.append({f[:-4]: np.load(os.path.join(d, f)) for f in os.listdir(d)})
+		assert sum(os.path.getsize(os.path.join(d, f)) for f in os.listdir(d)) <= dump.MAX_BYTES
+	a, b = dumps
+	assert set(a) == {'lc', 'lc_nonfinite', 'contamination', 'contamination_nonfinite', 'status', 'flags', 'mask', 'target_index'}
+	assert a['lc'].shape == a['lc_nonfinite'].shape == (5, 512, 200)
+	for name in a:
+		assert a[name].dtype in (np.float32, np.float64) and np.isfinite(a[name]).all(), name
+		np.testing.assert_array_equal(a[name], b[name], err_msg=name)
+	# the cubes carry NaN pixels: the flux of a cadence with one in the mask is NaN (the reference's np.sum), a code of 1 here
+	assert (a['lc'][0] != 0).any() and (a['lc_nonfinite'][0] == 1).any() and (a['mask'] > 0).any()
+
+
 @pytest.mark.parametrize('launcher', ['own', 'torchrun'])
 def test_two_ranks_on_one_device_line(tmp_path, launcher):
 	if launcher == 'own':

@@ -156,7 +156,7 @@ def test_psf_plugin(ctx, tmp_path):
 		np.testing.assert_allclose(pho.lightcurve['pos_centroid'][ok], ref['pos_centroid'][ok], atol=2e-4)
 
 
-def test_batch_api(ctx):
+def test_batch_api(ctx, tmp_path):
 	s = _scene(n=12, T=30, seed=9)
 	res = tessphot_batch(ctx, s)
 	assert len(res) == 12
@@ -167,7 +167,7 @@ def test_batch_api(ctx):
 		if r.status != STATUS.ERROR:
 			assert r.lightcurve['flux'].shape == (30,) and r._details['mask_size'] == r.final_phot_mask.sum()
 			# the batch carries the same diagnostics as the per-target plugin (host code mirroring BasePhotometry.py:1343-1407)
-			with AperturePhotometry(int(s.target_starid[i]), source_from_scene(s, i), '/tmp', datasource='ffi', ctx=ctx) as pho:
+			with AperturePhotometry(int(s.target_starid[i]), source_from_scene(s, i), str(tmp_path), datasource='ffi', ctx=ctx) as pho:
 				pho.photometry()
 				assert pho.status == r.status
 				for key in ('mean_flux', 'ptp', 'edge_flux'):

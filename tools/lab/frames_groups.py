@@ -1,5 +1,5 @@
 import os, sys, numpy as np
-sys.path.insert(0, os.environ.get('GRAFT_REPO_ROOT', '/root/repo'))
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', '..'))
 from photometry_amd import pipeline
 from photometry_amd.device import Context
 from benchlib.legs.frames import synthetic_region

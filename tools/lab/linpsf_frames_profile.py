@@ -1,5 +1,5 @@
 import os, sys, time, cProfile, pstats, io
-sys.path.insert(0, '/root/repo')
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', '..'))
 import numpy as np
 from photometry_amd import pipeline, simulate, psf as hpsf
 from photometry_amd.device import Context, bind_host_to_device
