@@ -676,6 +676,24 @@ typedef struct { uint64_t src_offset, dst_offset, count; int32_t kind; int32_t r
 int tp_block_compact(tp_ctx* ctx, const void* d_block, void* d_compact, const tp_block_field* fields, int32_t n_fields);
 int tp_comm_allgather(tp_ctx* ctx, const void* d_send, void* d_recv, uint64_t nbytes_per_rank);
 
+/* ---- image movement kernels (photometry/image_motion.py) --------------------------------------------------------------
+ * tp_motion_prepare replaces ImageMovementKernel._prepare_flux (image_motion.py:74-110) for every frame of a stack
+ *   d_frames float32 [n_frames] frames of [frame_rows][frame_cols] (contiguous rows) frame_stride values apart:
+ *   log10(flux - nanmin + 1) rescaled to [-1, 1], the Scharr gradient magnitude of scikit-image 0.19 (mode 'reflect'),
+ *   NaN -> 0.  d_out float32 [n_frames][frame_rows][frame_cols].
+ * tp_motion_ecc replaces ImageMovementKernel.calc_kernel (image_motion.py:182-256): cv2.findTransformECC of every prepared
+ *   frame (d_frames, as tp_motion_prepare writes them) against the prepared reference d_template [frame_rows][frame_cols],
+ *   criteria (EPS | COUNT, max_iter, eps), gaussFiltSize 5, warp starting at the identity.  n_params: 2 translation,
+ *   3 euclidian, 6 affine.  chunk_bytes: device memory for the blurred frames of one chunk (0: 2 GiB).  Out, per frame:
+ *   d_warp float64 [n_frames][6] (w00 w01 w02 w10 w11 w12), d_rho float64 (the last correlation measured), d_iters int32 (the
+ *   loop bodies run), d_status int32: 1 converged, 2 iteration cap, 3 failed (NaN correlation), 4 failed (lambda_d <= 0: the
+ *   reference's calc_kernel returns NaN for 3 and 4).  Deterministic: no float atomics.                                     */
+int tp_motion_prepare(tp_ctx* ctx, const float* d_frames, int32_t n_frames, int32_t frame_rows, int32_t frame_cols, int64_t frame_stride,
+	float* d_out);
+int tp_motion_ecc(tp_ctx* ctx, const float* d_template, const float* d_frames, int32_t n_frames, int32_t frame_rows, int32_t frame_cols,
+	int64_t frame_stride, int32_t n_params, int32_t max_iter, double eps, int64_t chunk_bytes, double* d_warp, double* d_rho,
+	int32_t* d_iters, int32_t* d_status);
+
 /* ---- synthetic data (bench / test utility, not part of the reference path) -----------------
  * Fill images / images_err / backgrounds cubes on the device from scene parameters, following
  * the data model of simulation/simulateFITS.py:338-405 (see photometry_amd/simulate.py).

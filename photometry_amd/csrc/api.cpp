@@ -42,6 +42,12 @@ static const char* const kKernelNames[TPK_COUNT] = {
 	"tp_star_positions_kernel",
 	"tp_f64_to_f32_kernel",
 	"tp_blit_kernel",
+	"tp_motion_prepare_kernel",
+	"tp_motion_blur_kernel",
+	"tp_motion_iter_kernel",
+	"tp_motion_finish_kernel",
+	"tp_motion_minmax_kernel",
+	"tp_motion_init_kernel",
 };
 
 extern "C" {

@@ -40,6 +40,12 @@ enum tp_kernel_id {
 	TPK_STAR_POSITIONS,
 	TPK_BLOCK_COMPACT,
 	TPK_BLIT,
+	TPK_MOTION_PREPARE,
+	TPK_MOTION_BLUR,
+	TPK_MOTION_ITER,
+	TPK_MOTION_FINISH,
+	TPK_MOTION_MINMAX,
+	TPK_MOTION_INIT,
 	TPK_COUNT
 };
 

@@ -33,15 +33,26 @@ def _aligned(n):
 	return (int(n) + ALIGN - 1) // ALIGN * ALIGN
 
 
-def write_stack(path, groups, row_offset=0, col_offset=44, time=None, cadenceno=None, quality=None, attrs=None):
+def write_stack(path, groups, row_offset=0, col_offset=44, time=None, cadenceno=None, quality=None, attrs=None, movement_kernel=None,
+	movement_warpmode='translation', movement_ref_frame=None):
 	"""
 	Write ``groups`` (dict name -> array ``(T, R, C)``, all the same shape; float32 images or uint8 flags) to ``path``.
 	``row_offset / col_offset``: CCD coordinates of frame pixel (0, 0) (PIXEL_OFFSET_ROW / _COLUMN, BasePhotometry.py:724-727).
+	``movement_kernel``: the ``(T, n_params)`` kernels of the prepare stage (the HDF5 ``movement_kernel`` dataset, prepare.py:693-697)
+	with its ``warpmode`` and ``ref_frame`` attributes; kept in ``attrs['movement_kernel']`` (JSON floats round-trip exactly, NaN
+	included) -- ``motion.movement_from_header`` builds the :class:`~photometry_amd.motion.MovementKernel` back.
 	"""
 	names = list(groups)
 	first = np.asarray(groups[names[0]])
 	T, R, C = first.shape
-	meta = {'shape': [int(T), int(R), int(C)], 'row_offset': int(row_offset), 'col_offset': int(col_offset), 'groups': [], 'attrs': attrs or {}}
+	attrs = dict(attrs or {})
+	if movement_kernel is not None:
+		k = np.asarray(movement_kernel, dtype='float64')
+		if k.ndim != 2 or len(k) != T:
+			raise ValueError(f"movement_kernel: ({T}, n_params) expected, got {k.shape}")
+		attrs['movement_kernel'] = {'kernels': k.tolist(), 'warpmode': str(movement_warpmode),
+			'ref_frame': None if movement_ref_frame is None else int(movement_ref_frame)}
+	meta = {'shape': [int(T), int(R), int(C)], 'row_offset': int(row_offset), 'col_offset': int(col_offset), 'groups': [], 'attrs': attrs}
 	for key, vec in (('time', time), ('cadenceno', cadenceno), ('quality', quality)):
 		if vec is not None:
 			meta[key] = [float(v) if key == 'time' else int(v) for v in np.asarray(vec)]

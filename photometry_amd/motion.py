@@ -1,0 +1,269 @@
+# -*- coding: utf-8 -*-
+"""
+Image movement kernels (photometry/image_motion.py) on the device.
+
+The prepare stage of the reference measures where the stars are at every cadence: ``ImageMovementKernel.calc_kernel``
+(image_motion.py:182-256) registers every FFI of a CCD against a reference frame with OpenCV's ECC maximisation
+(``cv2.findTransformECC``) on a Scharr-gradient image (``_prepare_flux``, :74-110) and stores the warps as the
+``movement_kernel`` dataset (prepare.py:678-697).  Everything downstream reads them through ``load_series`` /
+``interpolate`` / ``jitter`` (:259-421): ``catalog_attime`` (BasePhotometry.py:1224-1258) and the ``pos_corr`` column (:473).
+
+:class:`MovementKernel` has the public surface of ``ImageMovementKernel``; its ``calc_kernel`` and the batched
+:func:`movement_kernels_frames` run on the device (``tp_motion_prepare`` / ``tp_motion_ecc``, csrc/motion.hip).  The
+restatement the device is held to is ``tests/motion_common.py``; DESIGN.md section 9 lists the deliberate differences from
+OpenCV.  The ``'wcs'`` warpmode needs astropy.wcs, which this build does not have: it is accepted by the constructor and raises
+``NotImplementedError`` wherever it would be used.
+"""
+
+import logging
+import warnings
+import numpy as np
+from scipy.interpolate import interp1d
+
+logger = logging.getLogger(__name__)
+
+#: per-frame states written by tp_motion_ecc
+STATUS_CONVERGED, STATUS_CAP_REACHED, STATUS_FAILED_NAN, STATUS_FAILED_LAMBDA = 1, 2, 3, 4
+
+_WCS_MESSAGE = "warpmode 'wcs' needs astropy.wcs, which this build does not provide"
+
+
+def _no_wcs():
+	raise NotImplementedError(_WCS_MESSAGE)
+
+
+def _device_stack(ctx, images):
+	"""A float32 DeviceArray (T, R, C) of ``images`` (a DeviceArray is used as it is)."""
+	if hasattr(images, 'ptr'):
+		if np.dtype(images.dtype) != np.dtype('float32') or len(images.shape) != 3:
+			raise ValueError("images: float32 stack (T, R, C) expected")
+		return images
+	a = np.asarray(images, dtype='float32')
+	if a.ndim == 2:
+		a = a[None]
+	if a.ndim != 3:
+		raise ValueError("images: float32 stack (T, R, C) expected")
+	return ctx.array(np.ascontiguousarray(a))
+
+
+def prepare_frames(ctx, images):
+	"""``_prepare_flux`` of every frame of ``images`` (T, R, C) on the device: a float32 DeviceArray (T, R, C)."""
+	d = _device_stack(ctx, images)
+	T, R, C = d.shape
+	out = ctx.empty((T, R, C), 'float32')
+	ctx._check(ctx.lib.tp_motion_prepare(ctx.handle, d.ptr, T, R, C, R * C, out.ptr))
+	return out
+
+
+def _warp_to_kernels(warp, warpmode):
+	"""calc_kernel's return values (image_motion.py:241-256) from the (T, 2, 3) warps."""
+	if warpmode == 'affine':
+		return warp.reshape(len(warp), 6).copy()
+	k = np.empty((len(warp), 3 if warpmode == 'euclidian' else 2))
+	k[:, 0] = warp[:, 0, 2]
+	k[:, 1] = warp[:, 1, 2]
+	if warpmode == 'euclidian':
+		k[:, 2] = np.arctan2(warp[:, 1, 0], warp[:, 0, 0])
+	return k
+
+
+def ecc_prepared(ctx, template, prepared, warpmode, number_of_iterations=10000, termination_eps=1e-6, chunk_bytes=0):
+	"""
+	``tp_motion_ecc`` of the prepared frames ``prepared`` (float32 DeviceArray (T, R, C)) against the prepared reference
+	``template`` (float32 DeviceArray (R, C) or a view of one frame).  Returns a dict of host arrays: ``kernels`` (T, n_params)
+	float64 (NaN where the frame failed), ``warp`` (T, 2, 3), ``rho``, ``iterations``, ``status``.
+	"""
+	n_params = MovementKernel.N_PARAMS[warpmode]
+	T, R, C = prepared.shape
+	# tp_motion_ecc reads the template as one frame of the stack's geometry: anything else would be read out of its bounds
+	tshape = tuple(template.shape)
+	if tshape not in ((R, C), (1, R, C)):
+		raise ValueError(f"template of shape {tshape} does not match the frames ({R}, {C})")
+	d_warp = ctx.empty((T, 6), 'float64')
+	d_rho = ctx.empty((T,), 'float64')
+	d_iters = ctx.empty((T,), 'int32')
+	d_status = ctx.empty((T,), 'int32')
+	ctx._check(ctx.lib.tp_motion_ecc(ctx.handle, template.ptr, prepared.ptr, T, R, C, R * C, n_params, int(number_of_iterations),
+		float(termination_eps), int(chunk_bytes), d_warp.ptr, d_rho.ptr, d_iters.ptr, d_status.ptr))
+	warp = d_warp.to_host().reshape(T, 2, 3)
+	status = d_status.to_host()
+	kernels = _warp_to_kernels(warp, warpmode)
+	failed = status >= STATUS_FAILED_NAN
+	kernels[failed] = np.nan
+	for k in np.flatnonzero(failed):
+		# image_motion.py:237-239: every exception of findTransformECC gives a NaN kernel
+		logger.error("Could not find transform: frame %d: %s", k, "NaN encountered" if status[k] == STATUS_FAILED_NAN else
+			"the correlation is going to be minimized; images may be uncorrelated or non-overlapped")
+	return {'kernels': kernels, 'warp': warp, 'rho': d_rho.to_host(), 'iterations': d_iters.to_host(), 'status': status}
+
+
+def movement_kernels_frames(ctx, images, ref_frame, warpmode='translation', number_of_iterations=10000, termination_eps=1e-6, chunk_bytes=0):
+	"""
+	``ImageMovementKernel(image_ref=images[ref_frame], warpmode=warpmode).calc_kernel`` of every frame of ``images``
+	(float32 ``(T, R, C)``, host array or DeviceArray) -- the loop of prepare.py:678-697 in one call.
+
+	Returns a dict of host arrays: ``kernels`` ``(T, n_params)`` float64, NaN where a frame failed (logged as the reference does),
+	``rho`` (the last correlation measured), ``iterations`` and ``status`` (1 converged, 2 iteration cap, 3 / 4 failed) per frame,
+	and ``warp`` ``(T, 2, 3)``.
+	"""
+	if warpmode not in MovementKernel.N_PARAMS:
+		raise ValueError("Invalid warpmode")
+	if warpmode == 'wcs':
+		_no_wcs()
+	d = _device_stack(ctx, images)
+	T = d.shape[0]
+	if warpmode == 'unchanged':
+		return {'kernels': np.empty((T, 0)), 'warp': np.tile(np.eye(2, 3), (T, 1, 1)), 'rho': np.full(T, np.nan),
+			'iterations': np.zeros(T, dtype='int32'), 'status': np.full(T, STATUS_CONVERGED, dtype='int32')}
+	ref_frame = int(ref_frame)
+	if not 0 <= ref_frame < T:
+		raise ValueError(f"ref_frame {ref_frame} outside the stack of {T} frames")
+	prepared = prepare_frames(ctx, d)
+	try:
+		return ecc_prepared(ctx, prepared.slice0(ref_frame, 1), prepared, warpmode, number_of_iterations, termination_eps, chunk_bytes)
+	finally:
+		ctx.sync()
+		prepared.free()
+
+
+class MovementKernel(object):
+	"""
+	``ImageMovementKernel`` (image_motion.py:29-421) with ``calc_kernel`` on the device.
+
+	Parameters:
+		warpmode (str): ``'wcs'``, ``'unchanged'``, ``'translation'``, ``'euclidian'`` or ``'affine'``.
+		image_ref (2D ndarray): the reference image (prepared on the device when a kernel is first computed).
+		wcs_ref: accepted for the reference's signature; ``'wcs'`` is not available in this build.
+		ctx: the device :class:`photometry_amd.device.Context` ``calc_kernel`` runs on (default: a context on GPU 0, opened on
+			first use).
+	"""
+
+	N_PARAMS = {
+		'unchanged': 0,
+		'translation': 2,
+		'euclidian': 3,
+		'affine': 6,
+		'wcs': 1
+	}
+
+	def __init__(self, warpmode='euclidian', image_ref=None, wcs_ref=None, ctx=None):
+		if warpmode not in MovementKernel.N_PARAMS:
+			raise ValueError("Invalid warpmode")
+		self.warpmode = warpmode
+		self.n_params = MovementKernel.N_PARAMS[warpmode]
+		self.image_ref = None if image_ref is None else np.array(image_ref, dtype='float32')
+		if wcs_ref is not None:
+			_no_wcs()
+		self.wcs_ref = None
+		self.ctx = ctx
+		self._template = None
+		self._interpolator = None
+
+	def __call__(self, *args, **kwargs):
+		return self.apply_kernel(*args, **kwargs)
+
+	def _context(self):
+		if self.ctx is None:
+			from .device import Context
+			self.ctx = Context(0)
+		return self.ctx
+
+	def apply_kernel(self, xy, kernel):
+		"""The change of the positions ``xy`` (rows of column, row) under ``kernel`` (image_motion.py:113-179)."""
+		xy = np.atleast_2d(xy)
+		delta_pos = np.empty_like(xy)
+		if self.warpmode == 'wcs':
+			_no_wcs()
+		elif self.warpmode == 'unchanged':
+			delta_pos.fill(0)
+		elif self.warpmode == 'translation':
+			delta_pos[:, 0] = kernel[0]
+			delta_pos[:, 1] = kernel[1]
+		else:
+			if self.warpmode == 'euclidian':
+				c, s = np.cos(kernel[2]), np.sin(kernel[2])
+				M = np.array([[c, -s, kernel[0]], [s, c, kernel[1]]])
+			else:
+				M = np.reshape(kernel, (2, 3))
+			# one 3-vector product per position, evaluated like the reference's np.dot(matrix, [x, y, 1])
+			for i, (x, y) in enumerate(xy):
+				delta_pos[i, :] = np.dot(M, [x, y, 1])
+			delta_pos -= xy
+		return delta_pos
+
+	def calc_kernel(self, image, number_of_iterations=10000, termination_eps=1e-6):
+		"""The movement kernel of ``image`` against the reference image (image_motion.py:182-256), computed on the device."""
+		if self.warpmode == 'unchanged':
+			return []
+		if self.image_ref is None:
+			raise RuntimeError("Reference image not defined")
+		if self.warpmode == 'wcs':
+			_no_wcs()
+		if np.shape(image) != self.image_ref.shape:
+			# findTransformECC refuses images of another size than the template: the reference logs it and returns NaN
+			# (image_motion.py:237-239); nothing goes to the device
+			logger.error("Could not find transform: image of shape %s against a reference image of shape %s", np.shape(image),
+				self.image_ref.shape)
+			return np.full(self.n_params, np.nan)
+		ctx = self._context()
+		if self._template is None:
+			self._template = prepare_frames(ctx, self.image_ref)
+		prepared = prepare_frames(ctx, image)
+		try:
+			res = ecc_prepared(ctx, self._template, prepared, self.warpmode, number_of_iterations, termination_eps)
+		finally:
+			ctx.sync()
+			prepared.free()
+		k = res['kernels'][0]
+		return k if self.warpmode == 'affine' or not np.all(np.isfinite(k)) else list(k)
+
+	def load_series(self, times, kernels):
+		"""Time series of kernels and its interpolator (image_motion.py:259-335); non-finite kernels are left out."""
+		if self.warpmode == 'wcs':
+			_no_wcs()
+		self.series_times = np.asarray(times)
+		self.series_kernels = np.atleast_2d(kernels)
+		expected = (len(self.series_times), self.n_params)
+		if self.series_kernels.shape != expected:
+			raise ValueError("Wrong shape of kernels. Anticipated ({0},{1}), but got {2}".format(expected[0], expected[1], self.series_kernels.shape))
+		good = np.isfinite(times) & np.all(np.isfinite(kernels), axis=1)
+		# the fill values are the first and last kernels of the series as given, finite or not
+		self._interpolator = interp1d(times[good], kernels[good, :], axis=0, assume_sorted=True, bounds_error=False,
+			fill_value=(kernels[0, :], kernels[-1, :]))
+
+	def interpolate(self, time, xy):
+		"""The change of the positions ``xy`` at ``time`` from the loaded series (image_motion.py:338-399)."""
+		if self.warpmode == 'wcs':
+			_no_wcs()
+		if self._interpolator is None:
+			raise ValueError("Interpolator is not defined. ")
+		with warnings.catch_warnings():
+			warnings.filterwarnings('ignore', category=RuntimeWarning, module='scipy')
+			kernel = self._interpolator(time)
+		return self.apply_kernel(xy, kernel)
+
+	def jitter(self, time, column, row):
+		"""(T, 2) changes in column and row of the position (column, row) at the timestamps ``time`` (image_motion.py:402-421)."""
+		xy = np.array([column, row])
+		out = np.empty((len(time), 2), dtype='float64')
+		for k, t in enumerate(time):
+			out[k, :] = self.interpolate(t, xy)
+		return out
+
+
+def movement_from_header(header, times=None):
+	"""
+	A :class:`MovementKernel` with its series loaded from a ``.tpstack`` header (``frameio.read_header``) that carries the
+	``movement_kernel`` of the prepare stage (``attrs['movement_kernel']``: ``kernels``, ``warpmode``, ``ref_frame``) -- what
+	``BasePhotometry.MovementKernel`` builds from the HDF5 dataset (BasePhotometry.py:1185-1221).  ``times``: the timestamps of
+	the series (default: the header's ``time`` vector).  Returns None when the header holds no kernels.
+	"""
+	mk = (header.get('attrs') or {}).get('movement_kernel')
+	if mk is None:
+		return None
+	kernels = np.asarray(mk['kernels'], dtype='float64')
+	times = np.asarray(header['time'] if times is None else times, dtype='float64')
+	m = MovementKernel(warpmode=mk['warpmode'])
+	m.load_series(times, kernels.reshape(len(times), m.n_params))
+	m.ref_frame = None if mk.get('ref_frame') is None else int(mk['ref_frame'])
+	return m

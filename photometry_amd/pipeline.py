@@ -1230,17 +1230,27 @@ def _jitter32(jitter, T):
 	return j[:, 0].astype('float32'), j[:, 1].astype('float32')
 
 
-def linpsf_frames(ctx, stack, targets, catalog, time, quality, prf_model, jitter=None, cutoff_radius=5):
+def linpsf_frames(ctx, stack, targets, catalog, time, quality, prf_model, jitter=None, cutoff_radius=5, movement=None, timecorr=None):
 	"""
 	``LinPSFPhotometry.do_photometry`` (linpsf_photometry.py:79-219) for every target of a CCD region held in a
 	:class:`FrameStack`: default stamps grouped by size and cut on the device, the stars fitted beside each target selected as
 	the plugin does (:93-104), their positions at every cadence = catalogue position + ``jitter[k]`` (``(T, 2)`` column / row
 	shifts: what ``catalog_attime`` returns for a translation), one ``tp_linpsf_prf`` + ``tp_linpsf_fit`` per group.
 	Status and messages follow the plugin: ERROR "All target flux values are NaN.", WARNING "High contamination" above 0.1.
+	``movement``: a translation :class:`~photometry_amd.motion.MovementKernel` with a loaded series instead of ``jitter``: the
+	shifts are ``movement.jitter(time - timecorr, 0.0, 0.0)`` (frames whose ECC failed come out interpolated, as ``load_series`` does).
 	Returns a :class:`PSFFramesResult`.
 	"""
 	from . import psf as hpsf
 	n, T = len(targets['starid']), stack.n_cad
+	if movement is not None:
+		if jitter is not None:
+			raise ValueError("give either jitter or movement, not both")
+		if movement.warpmode != 'translation':
+			raise ValueError(f"linpsf_frames: translation movement kernels expected, got '{movement.warpmode}'")
+		t = np.asarray(time, dtype='float64')
+		# float positions: jitter() builds its position array from them, and integer ones would truncate the shifts
+		jitter = movement.jitter(t if timecorr is None else t - np.asarray(timecorr, dtype='float64'), 0.0, 0.0)
 	catalog = {k: np.asarray(v) for k, v in catalog.items()}
 	out = PSFFramesResult(n, T, 'linpsf')
 	cur, valid, groups = _psf_frame_groups(stack, targets)

@@ -176,6 +176,10 @@ class BasePhotometry(object):
 			pos_centroid=np.zeros((self.Ntimes, 2)), pos_corr=np.zeros((self.Ntimes, 2)))
 		if getattr(src, 'jitter', None) is not None:
 			self.lightcurve['pos_corr'] = np.array(src.jitter, dtype='float64')
+		elif getattr(src, 'movement', None) is not None:
+			# BasePhotometry.py:473: the jitter of the movement kernels at the target's position
+			self.lightcurve['pos_corr'][:] = src.movement.jitter(self.lightcurve['time'] - self.lightcurve['timecorr'], self.target_pos_column,
+				self.target_pos_row)
 		# The timestamp offset of the early data releases (fixes/time_offset.py upstream, applied at BasePhotometry.py:244 / :384)
 		# belongs to the input adapter: a source hands over corrected times.  The reference applies
 		# the correction silently (a DEBUG record, fixes/time_offset.py:125), so nothing may enter details['errors'] here: a source
@@ -388,6 +392,16 @@ class BasePhotometry(object):
 
 	def catalog_attime(self, time):
 		"""BasePhotometry.py:1224-1258 with a translation kernel: reference catalogue + jitter at ``time``."""
+		mk = getattr(self.source, 'movement', None)
+		if mk is not None:
+			if mk.warpmode == 'unchanged':
+				return self.catalog
+			# BasePhotometry.py:1249-1256: the float64 changes added into the float32 columns
+			cat = Table(**{key: np.array(v, copy=True) for key, v in self.catalog.cols.items()})
+			jitter = mk.interpolate(time, np.column_stack((cat['column'], cat['row'])))
+			for key, j in (('column', 0), ('row', 1), ('column_stamp', 0), ('row_stamp', 1)):
+				cat[key] = (cat[key] + jitter[:, j]).astype('float32')
+			return cat
 		jit = getattr(self.source, 'jitter', None)
 		if jit is None:
 			return self.catalog

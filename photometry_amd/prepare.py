@@ -338,7 +338,7 @@ def pixel_flags_frames(ctx, raw, first_excluded=None, is_tess=False, flux_cutoff
 
 
 def prepare_frames(ctx, raw, raw_err, quality, cadence=1800, flux_cutoff=8e4, pixel_flags=None, backapp=False, camera=None, ccd=None,
-	headers=None, backgrounds_pixels_threshold=0.5):
+	headers=None, backgrounds_pixels_threshold=0.5, calc_movement_kernel=False, ref_frame=None, reference_time=None, time=None):
 	"""
 	The image arithmetic of ``prepare_photometry`` for one CCD (prepare.py:265-470) on device-resident stacks ``(T, R, C)``:
 	pixel flags (manual excludes and the background mask, :296-297, :406-408), backgrounds (B1), their smoothing over
@@ -353,6 +353,11 @@ def prepare_frames(ctx, raw, raw_err, quality, cadence=1800, flux_cutoff=8e4, pi
 
 	Returns a dict of DeviceArrays: ``backgrounds, images, images_err`` float32 ``(T, R, C)``, ``sumimage`` float64 ``(R, C)``,
 	and, when flags exist, ``pixel_flags`` uint8 ``(T, R, C)`` and ``backgrounds_pixels_used`` uint8 ``(R, C)``.
+
+	``calc_movement_kernel``: also the image movement kernels of prepare.py:678-697 -- translation ECC of every background-subtracted
+	image against the reference frame (``motion.movement_kernels_frames``) -- as ``movement_kernel`` (host ``(T, 2)`` float64, NaN
+	where a frame failed) and ``movement_kernel_ref_frame``.  The reference frame is ``ref_frame``, or the good-quality frame whose
+	``time`` is nearest ``reference_time`` (:659-667); its quality must be 0 (RuntimeError as at :671-672).
 	"""
 	T, R, C = raw.shape
 	time_smooth = {1800: 3, 600: 9}[int(cadence)]
@@ -385,8 +390,33 @@ def prepare_frames(ctx, raw, raw_err, quality, cadence=1800, flux_cutoff=8e4, pi
 			float(backgrounds_pixels_threshold), used.ptr))
 		out['pixel_flags'] = pixel_flags
 		out['backgrounds_pixels_used'] = used
+	if calc_movement_kernel:
+		from . import motion
+		quality = np.asarray(quality)
+		if ref_frame is None:
+			if reference_time is None or time is None:
+				raise ValueError("calc_movement_kernel: give ref_frame, or reference_time together with time")
+			ref_frame = _nearest_good_frame(np.asarray(time, dtype='float64'), quality, reference_time)
+		ref_frame = int(ref_frame)
+		if quality[ref_frame] != 0:
+			raise RuntimeError("The chosen refindx does not contain good values.")
+		mk = motion.movement_kernels_frames(ctx, images, ref_frame, warpmode='translation')
+		out['movement_kernel'] = mk['kernels']
+		out['movement_kernel_ref_frame'] = ref_frame
 	ctx.sync()
 	return out
+
+
+def _nearest_good_frame(time, quality, reference_time):
+	"""find_nearest over the timestamps of the quality == 0 frames (prepare.py:659-667, utilities.find_nearest)."""
+	if np.isnan(reference_time):
+		raise ValueError("Invalid search value")
+	good = np.ma.masked_array(time, mask=(quality != 0))
+	if np.isposinf(reference_time):
+		return int(np.ma.argmax(good))
+	if np.isneginf(reference_time):
+		return int(np.ma.argmin(good))
+	return int(np.ma.argmin(np.abs(good - reference_time)))
 
 
 def background_shenanigans(ctx, images, sumimage, pixel_flags, threshold=40.0, size=15, block=25, indicator=None):

@@ -32,12 +32,17 @@ class MemoryStampSource(object):
 		time, timecorr, cadenceno, quality: light-curve base arrays ``(T,)``.
 		catalog: dict of arrays ``starid, tmag, row, column`` (CCD coordinates) of ALL stars of the region.
 		jitter: optional ``(T, 2)`` per-cadence (column, row) shift used by ``catalog_attime``.
+		movement: optional :class:`photometry_amd.motion.MovementKernel` with a loaded series (the prepare stage's
+			``movement_kernel``): ``catalog_attime`` and ``pos_corr`` then come from it as in BasePhotometry.py:473, :1224-1258.
+			Not together with ``jitter``.
 		frames may also hold ``pixel_flags`` (uint8 ``(R, C, T)``: the ``pixel_flags/%04d`` images of the prepare stage).
 		backgrounds_pixels_used: optional bool ``(R, C)`` image of the prepare stage (BasePhotometry.py:1052-1061).
 	"""
 
 	def __init__(self, frames, row0, col0, time, timecorr, cadenceno, quality, catalog, sector=1, camera=1, ccd=1,
-		cadence=1800, n_readout=720, jitter=None, prf=None, targets=None, backgrounds_pixels_used=None):
+		cadence=1800, n_readout=720, jitter=None, prf=None, targets=None, backgrounds_pixels_used=None, movement=None):
+		if jitter is not None and movement is not None:
+			raise ValueError("give either jitter or movement, not both")
 		self.frames = {k: np.asarray(v, dtype='uint8' if k == 'pixel_flags' else 'float32') for k, v in frames.items()}
 		self.backgrounds_pixels_used = None if backgrounds_pixels_used is None else np.asarray(backgrounds_pixels_used, dtype=bool)
 		R, C, T = self.frames['images'].shape
@@ -50,6 +55,7 @@ class MemoryStampSource(object):
 		self.catalog = {k: np.asarray(v) for k, v in catalog.items()}
 		self.sector, self.camera, self.ccd, self.cadence, self.n_readout = sector, camera, ccd, cadence, n_readout
 		self.jitter = None if jitter is None else np.asarray(jitter, dtype='float64')
+		self.movement = movement
 		self.prf = prf
 		#: optional float64 positions of the main targets (the reference projects ra/dec through the WCS,
 		#: BasePhotometry.py:440-447; the catalogue columns are only float32)
