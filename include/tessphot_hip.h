@@ -694,6 +694,31 @@ int tp_motion_ecc(tp_ctx* ctx, const float* d_template, const float* d_frames, i
 	int64_t frame_stride, int32_t n_params, int32_t max_iter, double eps, int64_t chunk_bytes, double* d_warp, double* d_rho,
 	int32_t* d_iters, int32_t* d_status);
 
+/* ---- Halo photometry (photometry/halo/halo_photometry.py) -------------------------------------------------------------
+ * The TV-min pixel weights that halo_photometry.py:179-196 obtains from halophot's do_lc (settings of :86-97: objective 'tv',
+ * sub 1, thresh -1, no sigma clipping, uniform start), defined in DESIGN.md ("Halo") and tests/halo_common.py.  One problem is
+ * one light-curve segment of one target (the split times of :125-159).
+ *   h_p_offset, h_npix, h_ncad: HOST arrays [n_problems].  Problem i's pixel matrix is ncad[i] rows of round_up(npix[i], 4)
+ *   floats (zero padded) at d_P + p_offset[i] (p_offset a multiple of 4, d_P 16-byte aligned): row t holds the cube's float32
+ *   values of the npix pixels at cadence t, every one of them finite.  1 <= npix <= 4096.  d_fit uint8 [sum ncad]: non-zero
+ *   for a fitted cadence (quality & DEFAULT_BITMASK == 0), problem i's cadences after those of problems 0 .. i-1.
+ *   Weights w = softmax(theta), l_t = sum_p w_p P[t][p] (float64), f = sum |l_F[j+1] - l_F[j]| / median(l_F) over the fitted
+ *   cadences F in time order (numpy's median).  Fewer than 3 fitted cadences, or a median <= 0 / not finite at the start:
+ *   status 4 (degenerate), f NaN.
+ * tp_halo_tvmin minimises f over theta from theta = 0: L-BFGS with `history` pairs (<= 16; the reference's setting is 10),
+ *   backtracking Armijo line search (alpha = 1, c1 = 1e-4, halving, 20 trials), stop after maxiter iterations (status 2), when
+ *   f_k - f_k+1 <= ftol max(|f_k|, |f_k+1|, 1) or |grad theta|_inf <= gtol (status 1), or when the line search fails (status 3).
+ *   Out: d_w float64 [sum npix] (weights, problem i after problems 0 .. i-1), d_l float64 [sum ncad] (l at every cadence of the
+ *   problem, fitted or not), d_f float64 [n_problems], d_iters int32, d_status int32.
+ * tp_halo_objective: f (d_f [n_problems]) and its gradient with respect to theta (d_grad float64 [sum npix]) at d_theta
+ *   (float64 [sum npix]), one evaluation per problem; NaN for a degenerate problem.
+ * Both are deterministic (no float atomics): a problem gives the same bits alone as inside a batch.                          */
+int tp_halo_tvmin(tp_ctx* ctx, int32_t n_problems, const int64_t* h_p_offset, const int32_t* h_npix, const int32_t* h_ncad,
+	const float* d_P, const uint8_t* d_fit, int32_t maxiter, int32_t history, double ftol, double gtol, double* d_w, double* d_l,
+	double* d_f, int32_t* d_iters, int32_t* d_status);
+int tp_halo_objective(tp_ctx* ctx, int32_t n_problems, const int64_t* h_p_offset, const int32_t* h_npix, const int32_t* h_ncad,
+	const float* d_P, const uint8_t* d_fit, const double* d_theta, double* d_f, double* d_grad);
+
 /* ---- synthetic data (bench / test utility, not part of the reference path) -----------------
  * Fill images / images_err / backgrounds cubes on the device from scene parameters, following
  * the data model of simulation/simulateFITS.py:338-405 (see photometry_amd/simulate.py).

@@ -48,6 +48,12 @@ static const char* const kKernelNames[TPK_COUNT] = {
 	"tp_motion_finish_kernel",
 	"tp_motion_minmax_kernel",
 	"tp_motion_init_kernel",
+	"tp_halo_init_kernel",
+	"tp_halo_forward_kernel",
+	"tp_halo_stat_kernel",
+	"tp_halo_backward_kernel",
+	"tp_halo_finish_kernel",
+	"tp_halo_output_kernel",
 };
 
 extern "C" {

@@ -46,6 +46,12 @@ enum tp_kernel_id {
 	TPK_MOTION_FINISH,
 	TPK_MOTION_MINMAX,
 	TPK_MOTION_INIT,
+	TPK_HALO_INIT,
+	TPK_HALO_FORWARD,
+	TPK_HALO_STAT,
+	TPK_HALO_BACKWARD,
+	TPK_HALO_FINISH,
+	TPK_HALO_OUTPUT,
 	TPK_COUNT
 };
 

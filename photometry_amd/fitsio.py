@@ -3,7 +3,8 @@
 Minimal FITS writer / reader for the TASOC light-curve files (no astropy in this image).
 
 Implements exactly what ``BasePhotometry.save_lightcurve`` needs (photometry/BasePhotometry.py:1417-1730): a primary
-HDU without data, one binary table (``TFORM`` D / E / J scalar columns), image extensions (float64 / int32 / uint8),
+HDU without data, binary tables (``TFORM`` D / E / J ... scalar columns, and vector columns with a repeat count such as
+``484E`` and an optional ``TDIM``, as the ``WEIGHTMAP`` extension of Halo photometry needs, :1673-1706), image extensions (float64 / int32 / uint8),
 80-character header cards in 2880-byte blocks, big-endian data, the ``DATASUM`` / ``CHECKSUM`` keywords of the FITS
 checksum convention (the reference writes with ``checksum=True``, :1720), optional gzip.  The reader understands the
 same subset and is used by the tests for round trips.
@@ -11,6 +12,7 @@ same subset and is used by the tests for round trips.
 
 import gzip
 import io
+import re
 import numpy as np
 
 BLOCK = 2880
@@ -125,10 +127,30 @@ def image_hdu(name, array, cards=()):
 	return _hdu_bytes(base, data)
 
 
+def _field(fmt):
+	"""``(repeat, numpy type code)`` of a TFORM value: ``'D'`` -> (1, '>f8'), ``'484E'`` -> (484, '>f4')."""
+	m = re.fullmatch(r'\s*(\d*)([A-Z])\s*', fmt)
+	if m is None or m.group(2) not in _FORMATS:
+		raise ValueError(f"unsupported TFORM: {fmt!r}")
+	return (int(m.group(1)) if m.group(1) else 1), _FORMATS[m.group(2)]
+
+
+def _dtype_entry(name, fmt, dim=None):
+	repeat, code = _field(fmt)
+	if dim is not None:
+		return (name, code, tuple(reversed(dim)))   # TDIM lists the fastest axis first
+	return (name, code) if repeat == 1 and not re.match(r'\s*\d', fmt) else (name, code, (repeat,))
+
+
+def _parse_tdim(text):
+	return tuple(int(v) for v in text.strip().strip('()').split(','))
+
+
 def bintable_hdu(name, columns, cards=()):
-	"""``columns``: list of dicts ``name, format (D/E/J/...), array`` and optional ``unit, disp, comments`` (dict of TTYPE/TFORM/... comments)."""
+	"""``columns``: list of dicts ``name, format (D/E/J/..., or with a repeat count: 484E), array`` and optional ``unit, disp,
+	dim`` (the TDIM tuple, fastest axis first) and ``comments`` (dict of TTYPE/TFORM/TUNIT/TDISP/TDIM comments)."""
 	nrows = len(columns[0]['array'])
-	dt = np.dtype([(c['name'], _FORMATS[c['format']]) for c in columns])
+	dt = np.dtype([_dtype_entry(c['name'], c['format'], c.get('dim')) for c in columns])
 	rec = np.zeros(nrows, dtype=dt)
 	for c in columns:
 		rec[c['name']] = np.asarray(c['array'])
@@ -145,6 +167,8 @@ def bintable_hdu(name, columns, cards=()):
 			base.append(card(f'TUNIT{i}', c['unit'], cm.get('TUNIT')))
 		if c.get('disp'):
 			base.append(card(f'TDISP{i}', c['disp'], cm.get('TDISP')))
+		if c.get('dim') is not None:
+			base.append(card(f'TDIM{i}', '(' + ','.join(str(int(v)) for v in c['dim']) + ')', cm.get('TDIM')))
 	base.append(card('EXTNAME', name, 'extension name'))
 	return _hdu_bytes(base, _pad(rec.tobytes()))
 
@@ -217,7 +241,8 @@ def read(path):
 		data = None
 		raw = blob[pos:pos + nbytes]
 		if header.get('XTENSION') == 'BINTABLE':
-			dt = np.dtype([(header[f'TTYPE{i}'], _FORMATS[header[f'TFORM{i}'].strip()]) for i in range(1, header['TFIELDS'] + 1)])
+			dt = np.dtype([_dtype_entry(header[f'TTYPE{i}'], header[f'TFORM{i}'],
+				_parse_tdim(header[f'TDIM{i}']) if f'TDIM{i}' in header else None) for i in range(1, header['TFIELDS'] + 1)])
 			rec = np.frombuffer(raw, dtype=dt, count=header['NAXIS2'])
 			data = {n: rec[n].astype(rec[n].dtype.newbyteorder('=')) for n in dt.names}
 		elif naxis:

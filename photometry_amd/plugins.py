@@ -26,7 +26,10 @@ from . import engine, pipeline, stamps
 #: the values of the reference's photometry/data/settings.ini, used when no settings file is given
 # ([fixes] time_offset of the reference's file is not among them: the timestamp correction of the early data releases is the
 # input adapter's job here -- see the warning in BasePhotometry.__init__ -- and a switch that switches nothing would mislead)
-DEFAULT_SETTINGS = {'todolist': {'faint_limit': '15.0'}, 'haloswitch': {'tmag_limit': '6.0', 'flux_limit': '0.01'}}
+# [halo] enabled is this engine's own switch (not in the reference's file): Halo photometry here is a TV-min implementation of its own
+# (photometry_amd.halo, DESIGN.md "Halo"), not halophot, so it runs only when a settings file asks for it
+DEFAULT_SETTINGS = {'todolist': {'faint_limit': '15.0'}, 'haloswitch': {'tmag_limit': '6.0', 'flux_limit': '0.01'},
+	'halo': {'enabled': 'false'}}
 
 TESS_DEFAULT_BITMASK = engine.TESS_DEFAULT_BITMASK
 #: PixelQualityFlags.BackgroundShenanigans / CorrectorQualityFlags.BackgroundShenanigans (photometry/quality.py:163, :85)
@@ -544,7 +547,7 @@ class BasePhotometry(object):
 			pmtotal = np.sqrt(tgt['pm_ra']**2 + tgt['pm_decl']**2)
 		hdr = self.header
 		prim = [
-			card('NEXTEND', 3, 'number of standard extensions'), card('EXTNAME', 'PRIMARY', 'name of extension'),
+			card('NEXTEND', 3 + int(getattr(self, 'halo_weightmap', None) is not None), 'number of standard extensions'), card('EXTNAME', 'PRIMARY', 'name of extension'),
 			card('ORIGIN', 'TASOC/Aarhus', 'institution responsible for creating this file'),
 			card('DATE', datetime.datetime.now().strftime("%Y-%m-%d"), 'date the file was created'),
 			card('TELESCOP', 'TESS', 'telescope'), card('INSTRUME', 'TESS Photometer', 'detector type'),
@@ -645,8 +648,11 @@ class BasePhotometry(object):
 		fname = (f'tess{self.starid:011d}-s{int(self.sector):03d}-{int(self.camera):d}-{int(self.ccd):d}-c{cadence:04d}'
 			f'-dr{data_rel:02d}-v{int(version):02d}-tasoc_lc.fits.gz')
 		path = os.path.join(output_folder, fname)
-		fitsio.write(path, [fitsio.primary_hdu(prim), fitsio.bintable_hdu('LIGHTCURVE', columns, tcards),
-			fitsio.image_hdu('SUMIMAGE', SumImage, icards), fitsio.image_hdu('APERTURE', mask, icards)])
+		hdus = [fitsio.primary_hdu(prim), fitsio.bintable_hdu('LIGHTCURVE', columns, tcards),
+			fitsio.image_hdu('SUMIMAGE', SumImage, icards), fitsio.image_hdu('APERTURE', mask, icards)]
+		if getattr(self, 'halo_weightmap', None) is not None:
+			hdus.append(weightmap_hdu(self.halo_weightmap, SumImage.shape, icards))
+		fitsio.write(path, hdus)
 		# relative to the input folder when the output lies inside it, else to the base output folder (:1722-1726)
 		base = self.output_folder_base
 		inp = self.input_folder if isinstance(self.input_folder, (str, bytes, os.PathLike)) else None
@@ -654,6 +660,26 @@ class BasePhotometry(object):
 			base = os.path.abspath(inp)
 		self._details['filepath_lightcurve'] = os.path.relpath(path, base).replace('\\', '/')
 		return path
+
+
+def weightmap_hdu(weightmap, shape, cards=()):
+	"""The ``WEIGHTMAP`` binary table of Halo photometry (BasePhotometry.py:1673-1706): one row per segment."""
+	from . import fitsio
+	npx = int(np.prod(shape))
+	i32, disp = 'column format: signed 32-bit integer', 'column display format'
+	wms = np.asarray(weightmap['weightmap'], dtype='float32').reshape(-1, shape[0], shape[1])
+	columns = [
+		{'name': 'CADENCENO1', 'format': 'J', 'array': np.asarray(weightmap['initial_cadence'], dtype='int32'), 'disp': 'I10',
+			'comments': {'TTYPE': 'column title: first cadence number', 'TFORM': i32, 'TDISP': disp}},
+		{'name': 'CADENCENO2', 'format': 'J', 'array': np.asarray(weightmap['final_cadence'], dtype='int32'), 'disp': 'I10',
+			'comments': {'TTYPE': 'column title: last cadence number', 'TFORM': i32, 'TDISP': disp}},
+		{'name': 'SAT_PIXELS', 'format': 'J', 'array': np.asarray(weightmap['sat_pixels'], dtype='int32'), 'disp': 'I10',
+			'comments': {'TTYPE': 'column title: Saturated pixels', 'TFORM': i32, 'TDISP': disp}},
+		{'name': 'WEIGHTMAP', 'format': f'{npx:d}E', 'array': wms, 'disp': 'E14.7', 'dim': (int(shape[1]), int(shape[0])),
+			'comments': {'TTYPE': 'column title: Weightmap', 'TFORM': 'column format: image of 32-bit floating point', 'TDISP': disp,
+				'TDIM': 'column dimensions: pixel aperture array'}},
+	]
+	return fitsio.bintable_hdu('WEIGHTMAP', columns, cards)
 
 
 #--------------------------------------------------------------------------------------------------
@@ -885,8 +911,59 @@ class PSFPhotometry(BasePhotometry):
 
 
 class HaloPhotometry(BasePhotometry):
-	"""Halo photometry (halo/halo_photometry.py, third-party halophot) -- not part of this engine."""
-	available = False
+	"""
+	Halo photometry (halo/halo_photometry.py:86-265): TV-min weighted-aperture photometry of very saturated stars, with the pixel
+	weights optimised on the device (:mod:`photometry_amd.halo`, csrc/halo.hip).  The weights are this engine's TV-min definition
+	(DESIGN.md "Halo"), not the third-party halophot's digits, so the plugin is off unless the settings say ``[halo] enabled = true``.
+	"""
+
+	@classmethod
+	def is_available(cls, settings=None):
+		"""Whether Halo photometry runs: the ``[halo] enabled`` switch of the settings (``TESSPHOT_SETTINGS``)."""
+		from . import halo
+		return halo.enabled(settings)
 
 	def do_photometry(self):
-		raise NotImplementedError("HaloPhotometry is outside the hot path implemented by photometry_amd")
+		from . import halo
+		logger = logging.getLogger(__name__)
+		if not self.is_available(self.settings):
+			raise NotImplementedError("HaloPhotometry is off: set '[halo] enabled = true' in the settings file named by "
+				"TESSPHOT_SETTINGS to run this engine's TV-min implementation")
+		logger.info("starid: %d", self.starid)
+		# FFI: a stamp just larger than the maximum distance from the target (:99-102)
+		if self.datasource == 'ffi':
+			self.resize_stamp(width=halo.DIST_MAX + 2, height=halo.DIST_MAX + 2)
+		logger.info("Target position in stamp: (%f, %f)", self.target_pos_row_stamp, self.target_pos_column_stamp)
+		cols, rows = self.get_pixel_grid()
+		pixel_mask = halo.pixel_mask(self.aperture, cols, rows, self.target_pos_row, self.target_pos_column)
+		lc = self.lightcurve
+		normfactor = mag2flux(self.target['tmag'])
+		res = halo.photometry(self.ctx, self.images_cube, self.images_err_cube, lc['quality'], lc['time'], lc['timecorr'],
+			lc['cadenceno'], pixel_mask, self.sector, normfactor)
+		for k, (st, it) in enumerate(zip(res['status'], res['iterations'])):
+			logger.info("Halo segment %d: %s after %d iterations", k, halo.STATUS_TEXT.get(int(st), str(st)), int(it))
+		if np.any(res['status'] == halo.DEGENERATE):
+			logger.error('Halo optimization failed')
+			return STATUS.ERROR
+		good = np.isfinite(lc['time'])
+		lc['flux'][good] = res['flux'][good]
+		lc['flux_err'] = res['flux_err']
+		# the target position per cadence; no centroids are calculated (:162-164, :221-222)
+		lc['pos_centroid'][:, 0] = self.target_pos_column + lc['pos_corr'][:, 0]
+		lc['pos_centroid'][:, 1] = self.target_pos_row + lc['pos_corr'][:, 1]
+		self.halo_weightmap = res['weightmap']
+		self.halo_result = res
+		self.additional_headers['HALO_VER'] = (halo.VERSION, 'Version of halo photometry')
+		self.additional_headers['HALO_OBJ'] = (halo.SETTINGS['objective'], 'Halophot objective function')
+		self.additional_headers['HALO_THR'] = (halo.SETTINGS['thresh'], 'Halophot saturated pixel threshold')
+		self.additional_headers['HALO_MXI'] = (halo.SETTINGS['maxiter'], 'Halophot maximum optimisation iterations')
+		self.additional_headers['HALO_SCL'] = (halo.SETTINGS['sigclip'], 'Halophot sigma clipping enabled')
+		self.additional_headers['HALO_MFL'] = (halo.SETTINGS['minflux'], 'Halophot minimum flux')
+		self.final_phot_mask = pixel_mask
+		# other targets in the mask (:257-262)
+		skip_targets = [int(sid) for sid, r, c in zip(self.catalog['starid'], self.catalog['row'], self.catalog['column'])
+			if sid != self.starid and np.any(pixel_mask & (rows == np.round(r) + 1) & (cols == np.round(c) + 1))]
+		if skip_targets:
+			logger.info("These stars could be skipped: %s", skip_targets)
+			self.report_details(skip_targets=skip_targets)
+		return STATUS.OK

@@ -93,12 +93,14 @@ def tessphot(method=None, *args, **kwargs):
 			raise ValueError(f"Invalid method: '{method:s}'")
 		pho = run_plugin(PLUGINS[method], *args, **kwargs)
 	else:
+		halo_on = HaloPhotometry.is_available()
+
 		def keep_aperture_result(p):
-			# No Halo photometry in this engine (third-party halophot upstream): the finished aperture result is kept, not
-			# thrown away for a plugin that can only fail; a good light curve is downgraded to WARNING and the request recorded
-			# BEFORE the light curve is written, so that the file and the returned status agree.
+			# Halo photometry off (the default, see HaloPhotometry): the finished aperture result is kept, not thrown away for a
+			# plugin that can only fail; a good light curve is downgraded to WARNING and the request recorded BEFORE the light
+			# curve is written, so that the file and the returned status agree.
 			why = halo_switch_reason(p)
-			if why is not None and not HaloPhotometry.available:
+			if why is not None and not halo_on:
 				p.report_details(error='Halo switch requested (' + why + ') but Halo photometry is not available: aperture result kept')
 				if p.status == STATUS.OK:
 					p._status = STATUS.WARNING
@@ -108,7 +110,7 @@ def tessphot(method=None, *args, **kwargs):
 		if reason is not None:
 			logger.warning(reason)
 			edge_flux = pho._details.get('edge_flux')
-			if HaloPhotometry.available:
+			if halo_on:
 				pho = run_plugin(HaloPhotometry, *args, **kwargs)
 				if isinstance(pho, HaloPhotometry):
 					# keep the diagnostics that led to the switch (tessphot.py:104-109)
