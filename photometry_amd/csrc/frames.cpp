@@ -18,6 +18,7 @@
 // (which stay the per-target plugin's implementation and the reference of tests/test_gpu_resize.py); messages travel as codes
 // that the Python layer turns into the reference's log strings.
 #include "common.h"
+#include "helper_pool.h"
 #include <algorithm>
 #include <atomic>
 #include <cmath>
@@ -29,8 +30,6 @@
 #include <thread>
 #include <chrono>
 #include <condition_variable>
-#include <deque>
-#include <functional>
 #include <vector>
 
 namespace {
@@ -40,7 +39,7 @@ constexpr uint32_t kBitmask = 1 | 2 | 4 | 8 | 32 | 64 | 128 | 4096;   // TESSQua
 // job runs fastest with (measured, 2 500 targets: 15 / 13 / 20 ms with 2 / 3 / 4 streams for the small groups: beyond four active
 // queues of a process the hardware time-slices them).
 constexpr int kStreams = 4;               // per slot: three streams of the engine's pool and a copy stream
-static int g_small_streams = 3;          // (experiment: TESSPHOT_FRAMES_STREAMS = 1 .. 3 pool streams per slot)
+constexpr int kPoolStreams = kStreams - 1;
 constexpr int kResizeStep = 10;          // photometry.py:124-131
 constexpr int kFusedFrom = 1024;         // from this many targets on a group is "large": stream 0, the error / background stacks cut after the mask
 constexpr int kEdgeBits = 2 | 4 | 8 | 16;
@@ -103,49 +102,6 @@ double np_pairwise_sum(const double* a, int64_t n) {
 
 } // namespace
 
-// A few helper threads of the engine, started once: the catalogue selection of a large group is cut into runs of stamps and the
-// runs are selected side by side (threads started per group cost more than they saved: 2.3 ms against 0.75 for 2 500 stamps).
-struct HelperPool {
-	std::mutex m;
-	std::condition_variable cv;
-	std::deque<std::function<void()>> tasks;
-	std::vector<std::thread> threads;
-	bool stop = false;
-	void start(int n) {
-		for (int i = 0; i < n; ++i) {
-			try {
-				threads.emplace_back([this] {
-					for (;;) {
-						std::function<void()> f;
-						{
-							std::unique_lock<std::mutex> lk(m);
-							cv.wait(lk, [this] { return stop || !tasks.empty(); });
-							if (tasks.empty()) return;      // (stop, and nothing left to do)
-							f = std::move(tasks.front());
-							tasks.pop_front();
-						}
-						f();
-					}
-				});
-			} catch (...) { break; }                   // fewer helpers, or none: the callers run what nobody takes
-		}
-	}
-	void post(std::function<void()> f) { { std::lock_guard<std::mutex> lk(m); tasks.push_back(std::move(f)); } cv.notify_one(); }
-	// a posted task that no helper has taken yet, for the poster to run itself rather than wait
-	bool take(std::function<void()>& f) {
-		std::lock_guard<std::mutex> lk(m);
-		if (tasks.empty()) return false;
-		f = std::move(tasks.front());
-		tasks.pop_front();
-		return true;
-	}
-	~HelperPool() {
-		{ std::lock_guard<std::mutex> lk(m); stop = true; }
-		cv.notify_all();
-		for (auto& t : threads) if (t.joinable()) t.join();
-	}
-};
-
 // ---- the catalogue of a region, binned into cells of 16 x 16 pixels (stars sorted by cell) ------------------------------------
 struct tp_frames_catalog {
 	int64_t n = 0;
@@ -159,7 +115,7 @@ struct tp_frames_catalog {
 struct tp_frames_engine {
 	int device = 0;
 	int n_slots = 0;
-	std::vector<tp_ctx*> ctxs;          // kStreams - 1 per slot: the engine's pool of streams, shared by the jobs in flight (SmallStream
+	std::vector<tp_ctx*> ctxs;          // kPoolStreams per slot: the engine's pool of streams, shared by the jobs in flight (SmallStream
 	                                    // below); the kStreams-th stream of a slot is its copy stream.  The process should stay below
 	                                    // ~24 streams in all: beyond that the hardware queues are time-sliced, and with six idle streams
 	                                    // more in the process four jobs in flight fell from 8.1 to 4.8 x 10^5 targets/s (round 6)
@@ -170,13 +126,15 @@ struct tp_frames_engine {
 	struct SmallStream { tp_ctx* c = nullptr; hipEvent_t busy = nullptr; double load = 0.0; bool claimed = false; };
 	std::vector<SmallStream> small;
 	std::mutex sm;
+	std::condition_variable released;    // (with sm) claims have been given back
 	std::vector<hipStream_t> copy_streams;   // one per slot (nullptr if it could not be created: the light curves then leave on the job's stream)
 	std::vector<char> busy;
 	std::mutex m;
 	PinnedPool pinned;
 	HelperPool helpers;
 	uint64_t hbm_bytes = 0;
-	std::atomic<int> running{0};         // worker threads inside run(): tp_frames_engine_destroy waits for them
+	int running = 0;                     // (with m) worker threads inside run(): tp_frames_engine_destroy waits for them on `idle`
+	std::condition_variable idle;
 };
 
 namespace {
@@ -367,31 +325,14 @@ void tp_frames_job::launch_masks(Launched& L, std::vector<hipEvent_t>& event_poo
 		std::vector<float> c_tmag, c_row, c_col, c_row_stamp, c_col_stamp;
 		if (m < 1024 || eng->helpers.threads.empty()) select_catalog(L.idx, G, c_tmag, c_row, c_col, c_row_stamp, c_col_stamp);
 		else {
-			// a large group: the stamps in four runs, three of them offered to the engine's helper threads (what no helper has taken when
-			// this thread is through with its own run it does itself), joined in order.  The selection of 2 500 stamps is 0.5 of the
-			// 0.75 ms a worker needs before it can queue anything, 2 of 2.7 ms for 10 000.
+			// a large group: the stamps in four runs, three of them offered to the engine's helper threads, joined in order.  The
+			// selection of 2 500 stamps is 0.5 of the 0.75 ms a worker needs before it can queue anything, 2 of 2.7 ms for 10 000.
 			constexpr int K = 4;
-			struct Run { Group part; std::vector<float> tmag, row, col, rs, cs; std::vector<int32_t> idx; bool done = false; };
+			struct Run { Group part; std::vector<float> tmag, row, col, rs, cs; std::vector<int32_t> idx; };
 			Run run[K];
-			std::mutex dm;
-			std::condition_variable dcv;
-			int pending = K - 1;
 			for (int k = 0; k < K; ++k) run[k].idx.assign(L.idx.begin() + (size_t)m * k / K, L.idx.begin() + (size_t)m * (k + 1) / K);
-			for (int k = 1; k < K; ++k)
-				eng->helpers.post([this, &run, &dm, &dcv, &pending, k] {
-					try { select_catalog(run[k].idx, run[k].part, run[k].tmag, run[k].row, run[k].col, run[k].rs, run[k].cs); run[k].done = true; }
-					catch (...) {}                      // (out of memory on a helper: reported below by the thread that waits)
-					{ std::lock_guard<std::mutex> lk(dm); pending -= 1; }
-					dcv.notify_one();
-				});
-			select_catalog(run[0].idx, run[0].part, run[0].tmag, run[0].row, run[0].col, run[0].rs, run[0].cs);
-			{
-				std::function<void()> f;           // (tasks of other jobs may be among them: any posted run is as good to do)
-				while (eng->helpers.take(f)) f();
-				std::unique_lock<std::mutex> lk(dm);
-				dcv.wait(lk, [&] { return pending == 0; });
-			}
-			for (int k = 1; k < K; ++k) if (!run[k].done) throw Fail("the catalogue selection of the group failed on a helper thread");
+			if (!eng->helpers.fork_join(K, [&](int k) { select_catalog(run[k].idx, run[k].part, run[k].tmag, run[k].row, run[k].col, run[k].rs, run[k].cs); }))
+				throw Fail("the catalogue selection of the group failed on a helper thread");
 			G.cat_offsets.assign(1, 0);
 			G.cat_starid.clear();
 			for (int k = 0; k < K; ++k) {
@@ -595,17 +536,10 @@ void tp_frames_job::launch_tail(Launched& L, std::vector<hipEvent_t>& event_pool
 				ckh(hipStreamWaitEvent(copy_stream, e, 0), "hipStreamWaitEvent");
 				// the five planes of the chunk as ONE rectangular copy (five rows, a plane apart): 48 DMA commands per 2 500 targets instead
 				// of 240, each followed by ~20 us of idle link (copy trace of four jobs in flight: the link was busy 87 % of the time;
-				// 7.55 -> 7.98 x 10^5 targets/s).  TESSPHOT_FRAMES_RECT=0: plane by plane
-				static const bool rect = [] { const char* e = std::getenv("TESSPHOT_FRAMES_RECT"); return !(e && e[0] == '0'); }();
-				if (rect) {
-					const size_t o = (size_t)G.off_lc + (size_t)j0 * T * 8;
-					ckh(hipMemcpy2DAsync(static_cast<char*>(G.h_block) + o, (size_t)m * T * 8, blk + o, (size_t)m * T * 8, (size_t)(j1 - j0) * T * 8, 5,
-						hipMemcpyDeviceToHost, copy_stream), "hipMemcpy2DAsync(light curves)");
-				} else
-				for (int k = 0; k < 5; ++k) {
-					const size_t o = (size_t)G.off_lc + ((size_t)k * m + (size_t)j0) * T * 8;
-					ckh(hipMemcpyAsync(static_cast<char*>(G.h_block) + o, blk + o, (size_t)(j1 - j0) * T * 8, hipMemcpyDeviceToHost, copy_stream), "hipMemcpyAsync(light curves)");
-				}
+				// 7.55 -> 7.98 x 10^5 targets/s)
+				const size_t o = (size_t)G.off_lc + (size_t)j0 * T * 8;
+				ckh(hipMemcpy2DAsync(static_cast<char*>(G.h_block) + o, (size_t)m * T * 8, blk + o, (size_t)m * T * 8, (size_t)(j1 - j0) * T * 8, 5,
+					hipMemcpyDeviceToHost, copy_stream), "hipMemcpy2DAsync(light curves)");
 			}
 		}
 		lap("extract");
@@ -720,31 +654,29 @@ void tp_frames_job::decide(Launched& L, std::vector<int32_t>& still)
 // with the least work queued since it was last seen idle; claimed until the round is queued
 void tp_frames_job::claim(Launched& L, double work, const std::vector<Launched>& round)
 {
+	std::unique_lock<std::mutex> lk(eng->sm);
 	for (;;) {
-		{
-			std::lock_guard<std::mutex> lk(eng->sm);
-			int pick = -1;
-			for (size_t k = 0; k < eng->small.size(); ++k) {
-				auto& S = eng->small[k];
-				if (S.claimed) continue;
-				if (S.busy && S.load > 0.0 && hipEventQuery(S.busy) == hipSuccess) S.load = 0.0;   // drained
-				if (S.load == 0.0) { pick = (int)k; break; }
-				if (pick < 0 || S.load < eng->small[(size_t)pick].load) pick = (int)k;
-			}
-			(void)hipGetLastError();   // hipErrorNotReady of the queries
-			if (pick < 0)                // none unclaimed.  A round with more groups than the pool has streams: one this job holds already
-				for (const Launched& o : round)
-					if (o.small >= 0 && (pick < 0 || eng->small[(size_t)o.small].load < eng->small[(size_t)pick].load)) pick = o.small;
-			if (pick >= 0) {
-				auto& S = eng->small[(size_t)pick];
-				S.claimed = true;
-				S.load += work;
-				L.small = pick;
-				L.g = S.c;
-				return;
-			}
+		int pick = -1;
+		for (size_t k = 0; k < eng->small.size(); ++k) {
+			auto& S = eng->small[k];
+			if (S.claimed) continue;
+			if (S.busy && S.load > 0.0 && hipEventQuery(S.busy) == hipSuccess) S.load = 0.0;   // drained
+			if (S.load == 0.0) { pick = (int)k; break; }
+			if (pick < 0 || S.load < eng->small[(size_t)pick].load) pick = (int)k;
 		}
-		std::this_thread::yield();     // every stream of the pool is being queued on by the other jobs' workers: a matter of microseconds
+		(void)hipGetLastError();   // hipErrorNotReady of the queries
+		if (pick < 0)                // none unclaimed.  A round with more groups than the pool has streams: one this job holds already
+			for (const Launched& o : round)
+				if (o.small >= 0 && (pick < 0 || eng->small[(size_t)o.small].load < eng->small[(size_t)pick].load)) pick = o.small;
+		if (pick >= 0) {
+			auto& S = eng->small[(size_t)pick];
+			S.claimed = true;
+			S.load += work;
+			L.small = pick;
+			L.g = S.c;
+			return;
+		}
+		eng->released.wait(lk);      // every stream of the pool is claimed by other jobs' workers until they have queued their rounds
 	}
 }
 
@@ -813,6 +745,7 @@ void tp_frames_job::run()
 							if (S.busy) (void)hipEventRecord(S.busy, S.c->stream);
 							S.claimed = false;
 						}
+						e->released.notify_all();
 					}
 					~Claims() { release(); }
 				} claims{eng, launched};
@@ -913,11 +846,9 @@ int tp_frames_engine_create(int device, int32_t n_slots, tp_frames_engine** out)
 	tp_frames_engine* eng = new tp_frames_engine();
 	eng->device = device;
 	eng->n_slots = n_slots;
-	if (const char* se = std::getenv("TESSPHOT_FRAMES_STREAMS")) { const int v = std::atoi(se); if (v >= 1 && v <= kStreams - 1) g_small_streams = v; }
-	for (int i = 0; i < n_slots * g_small_streams; ++i) {
+	for (int i = 0; i < n_slots * kPoolStreams; ++i) {
 		tp_ctx* c = nullptr;
-		const char* pe = std::getenv("TESSPHOT_FRAMES_PRIO");
-		const int rc = tp_ctx_create_stream(device, (pe && pe[0] == '1') ? 1 : 0, &c);
+		const int rc = tp_ctx_create_stream(device, 0, &c);
 		if (rc != TP_OK) {
 			for (tp_ctx* x : eng->ctxs) (void)tp_ctx_destroy(x);
 			delete eng;
@@ -943,7 +874,10 @@ int tp_frames_engine_create(int device, int32_t n_slots, tp_frames_engine** out)
 int tp_frames_engine_destroy(tp_frames_engine* eng)
 {
 	if (!eng) return TP_OK;
-	while (eng->running.load() > 0) std::this_thread::yield();   // (a job still running: its streams go only once it is through)
+	{                                // (a job still running: its streams go only once it is through)
+		std::unique_lock<std::mutex> lk(eng->m);
+		eng->idle.wait(lk, [eng] { return eng->running == 0; });
+	}
 	for (auto& S : eng->small) if (S.busy) (void)hipEventDestroy(S.busy);
 	for (hipStream_t cs : eng->copy_streams) if (cs) (void)hipStreamDestroy(cs);
 	for (tp_ctx* c : eng->ctxs) (void)tp_ctx_destroy(c);
@@ -1056,12 +990,18 @@ int tp_frames_submit(tp_frames_engine* eng, const tp_frames_stack* stack, const 
 	job->time.assign(h_time, h_time + job->T);
 	job->quality.assign(h_quality, h_quality + job->T);
 	job->budget = budget_bytes > 0 ? budget_bytes : (double)eng->hbm_bytes / 4.0;
-	eng->running.fetch_add(1);
+	{ std::lock_guard<std::mutex> lk(eng->m); eng->running += 1; }
 	try {
-		job->worker = std::thread([job] { job->run(); job->done.store(1, std::memory_order_release); job->eng->running.fetch_sub(1); });
+		job->worker = std::thread([job] {
+			job->run();
+			job->done.store(1, std::memory_order_release);
+			tp_frames_engine* e = job->eng;
+			std::lock_guard<std::mutex> lk(e->m);   // (notified under the lock: the engine may go as soon as it is released)
+			e->running -= 1;
+			e->idle.notify_all();
+		});
 	} catch (...) {          // no thread to be had: the slot is free again, the job never existed
-		eng->running.fetch_sub(1);
-		{ std::lock_guard<std::mutex> lk(eng->m); eng->busy[slot] = 0; }
+		{ std::lock_guard<std::mutex> lk(eng->m); eng->busy[slot] = 0; eng->running -= 1; }
 		delete job;
 		tp_global_err = "tp_frames_submit: could not start the job's worker thread";
 		return TP_ERR_INVALID;
