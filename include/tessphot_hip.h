@@ -719,6 +719,43 @@ int tp_halo_tvmin(tp_ctx* ctx, int32_t n_problems, const int64_t* h_p_offset, co
 int tp_halo_objective(tp_ctx* ctx, int32_t n_problems, const int64_t* h_p_offset, const int32_t* h_npix, const int32_t* h_ncad,
 	const float* d_P, const uint8_t* d_fit, const double* d_theta, double* d_f, double* d_grad);
 
+/* ---- TAN-SIP world coordinate systems (astropy.wcs as ImageMovementKernel('wcs') uses it, image_motion.py:113-421) ---------
+ * One frame's WCS is a block of TP_WCS_PARAMS float64 values packed by photometry_amd/wcs.py: [0:9] the native -> celestial
+ * rotation (row-major), [9:11] CRPIX, [11:15] CD, [15:19] CD^-1, [19] A_ORDER, [20] B_ORDER, [21] 1 with SIP, [24:124] A_p_q at
+ * p * 10 + q, [124:224] B_p_q.  All arithmetic is float64; nothing uses float atomics, so every result is bit-reproducible.
+ * tp_wcs_pix2world: n points d_xy [n][2] (x, y; `origin` 0 or 1) of one frame: mode 0 pix2foc, 1 wcs_pix2world (no SIP),
+ *   2 all_pix2world.  d_out [n][2] (focal-plane pixels, or ra in [0, 360) and dec in degrees; may be NULL for modes 1 and 2),
+ *   d_cos [n][3] the celestial unit vectors (modes 1 and 2; may be NULL).
+ * tp_wcs_radec: (ra, dec) degrees d_radec [n][2] -> unit vectors d_cos [n][3].
+ * tp_wcs_world2pix: the points d_cos [n][3] in every frame of d_params [n_frames][TP_WCS_PARAMS] (<= 65535); the points form
+ *   n_batches batches, h_offsets (HOST, [n_batches + 1], rising from >= 0 to <= n).  all = 0: wcs_world2pix; all = 1:
+ *   all_world2pix (astropy 4.3, adaptive=False, detect_divergence=True) with `tolerance` and `maxiter`, the loop's stopping test
+ *   taken over each batch.  d_pix [n_frames][n][2] (`origin`), d_status [n_frames][n] TP_WCS_* bits, d_iters [n_frames][n_batches]
+ *   (astropy's k, 0 without SIP or for an empty batch; may be NULL).  Empty batches are allowed (d_cos may be NULL when n == 0).
+ * tp_wcs_footprint_check: load_series' test of every frame: pixel (0, 0) through all_pix2world and back through all_world2pix as a
+ *   batch of one; d_status [n_frames] TP_WCS_* bits (0: the frame is kept).
+ * tp_wcs_star_positions: LinPSF positions of catalogue rows that move with the WCS.  Rows d_xy32 [n][2] (column, row float32, in
+ *   the reference WCS d_ref_params), batches h_offsets (HOST) as in tp_wcs_world2pix -- a stamp's catalogue.  Per cadence k the
+ *   jitter is that of frame d_k1[k] (d_k2[k] = -1) or interp1d's (j2 - j1) / dt[k] * dx[k] + j1 between frames k1 and k2; row i
+ *   with d_out_index[i] = o >= 0 (< n_out) gets d_pos_col[o * pos_pitch + k] = float64(float32(base_col[i] + jitter column)),
+ *   the same for rows.  d_status [n] (may be NULL): OR of the rows' status bits over the cadences (atomic integer OR).        */
+#define TP_WCS_PARAMS 224
+#define TP_WCS_DIVERGENT 1   /* astropy's `divergent` points (invalid ones included) */
+#define TP_WCS_SLOW 2        /* maxiter reached while still converging */
+#define TP_WCS_INVALID 4     /* non-finite pixel from a finite world point */
+#define TP_WCS_SCHEDULE 8    /* batch of > 64 points: dn rose above tolerance^2 again after the point had converged; the batch's
+                                iteration count and its other points may then differ from astropy's (see csrc/wcs.hip) */
+int tp_wcs_pix2world(tp_ctx* ctx, const double* d_params, int64_t n, const double* d_xy, int32_t origin, int32_t mode, double* d_out,
+	double* d_cos);
+int tp_wcs_radec(tp_ctx* ctx, int64_t n, const double* d_radec, double* d_cos);
+int tp_wcs_world2pix(tp_ctx* ctx, const double* d_params, int32_t n_frames, int64_t n, int32_t n_batches, const int64_t* h_offsets,
+	const double* d_cos, int32_t origin, int32_t all, double tolerance, int32_t maxiter, double* d_pix, int32_t* d_status, int32_t* d_iters);
+int tp_wcs_footprint_check(tp_ctx* ctx, const double* d_params, int32_t n_frames, double tolerance, int32_t maxiter, int32_t* d_status);
+int tp_wcs_star_positions(tp_ctx* ctx, const double* d_params, int32_t n_frames, const double* d_ref_params, int64_t n, int32_t n_batches,
+	const int64_t* h_offsets, const float* d_xy32, const float* d_base_col, const float* d_base_row, const int64_t* d_out_index, int64_t n_out,
+	int32_t n_cad, const int32_t* d_k1, const int32_t* d_k2, const double* d_dt, const double* d_dx, double tolerance, int32_t maxiter,
+	double* d_pos_col, double* d_pos_row, int64_t pos_pitch, int32_t* d_status);
+
 /* ---- synthetic data (bench / test utility, not part of the reference path) -----------------
  * Fill images / images_err / backgrounds cubes on the device from scene parameters, following
  * the data model of simulation/simulateFITS.py:338-405 (see photometry_amd/simulate.py).

@@ -54,6 +54,12 @@ static const char* const kKernelNames[TPK_COUNT] = {
 	"tp_halo_backward_kernel",
 	"tp_halo_finish_kernel",
 	"tp_halo_output_kernel",
+	"tp_wcs_pix2world_kernel",
+	"tp_wcs_radec_kernel",
+	"tp_wcs_world2pix_kernel",
+	"tp_wcs_footprint_kernel",
+	"tp_wcs_widen_kernel",
+	"tp_wcs_positions_kernel",
 };
 
 extern "C" {

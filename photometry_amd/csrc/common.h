@@ -52,6 +52,12 @@ enum tp_kernel_id {
 	TPK_HALO_BACKWARD,
 	TPK_HALO_FINISH,
 	TPK_HALO_OUTPUT,
+	TPK_WCS_PIX2WORLD,
+	TPK_WCS_RADEC,
+	TPK_WCS_WORLD2PIX,
+	TPK_WCS_FOOTPRINT,
+	TPK_WCS_WIDEN,
+	TPK_WCS_POSITIONS,
 	TPK_COUNT
 };
 

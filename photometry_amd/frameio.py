@@ -34,13 +34,16 @@ def _aligned(n):
 
 
 def write_stack(path, groups, row_offset=0, col_offset=44, time=None, cadenceno=None, quality=None, attrs=None, movement_kernel=None,
-	movement_warpmode='translation', movement_ref_frame=None):
+	movement_warpmode='translation', movement_ref_frame=None, wcs_headers=None, wcs_ref=None):
 	"""
 	Write ``groups`` (dict name -> array ``(T, R, C)``, all the same shape; float32 images or uint8 flags) to ``path``.
 	``row_offset / col_offset``: CCD coordinates of frame pixel (0, 0) (PIXEL_OFFSET_ROW / _COLUMN, BasePhotometry.py:724-727).
 	``movement_kernel``: the ``(T, n_params)`` kernels of the prepare stage (the HDF5 ``movement_kernel`` dataset, prepare.py:693-697)
 	with its ``warpmode`` and ``ref_frame`` attributes; kept in ``attrs['movement_kernel']`` (JSON floats round-trip exactly, NaN
 	included) -- ``motion.movement_from_header`` builds the :class:`~photometry_amd.motion.MovementKernel` back.
+	``wcs_headers``: per-frame WCS header strings (blank: no WCS for that frame), with ``wcs_ref`` the header of the reference
+	WCS (default: that of frame ``movement_ref_frame``, else frame 0); kept in ``attrs['wcs_headers']`` / ``attrs['wcs_ref']``.
+	``motion.movement_from_header`` prefers them to ``movement_kernel``, as BasePhotometry.py:1185-1221 does.
 	"""
 	names = list(groups)
 	first = np.asarray(groups[names[0]])
@@ -52,6 +55,12 @@ def write_stack(path, groups, row_offset=0, col_offset=44, time=None, cadenceno=
 			raise ValueError(f"movement_kernel: ({T}, n_params) expected, got {k.shape}")
 		attrs['movement_kernel'] = {'kernels': k.tolist(), 'warpmode': str(movement_warpmode),
 			'ref_frame': None if movement_ref_frame is None else int(movement_ref_frame)}
+	if wcs_headers is not None:
+		hdrs = [str(h) for h in wcs_headers]
+		if len(hdrs) != T:
+			raise ValueError(f"wcs_headers: {T} header strings expected, got {len(hdrs)}")
+		attrs['wcs_headers'] = hdrs
+		attrs['wcs_ref'] = str(wcs_ref) if wcs_ref is not None else hdrs[0 if movement_ref_frame is None else int(movement_ref_frame)]
 	meta = {'shape': [int(T), int(R), int(C)], 'row_offset': int(row_offset), 'col_offset': int(col_offset), 'groups': [], 'attrs': attrs}
 	for key, vec in (('time', time), ('cadenceno', cadenceno), ('quality', quality)):
 		if vec is not None:

@@ -11,8 +11,13 @@ The prepare stage of the reference measures where the stars are at every cadence
 :class:`MovementKernel` has the public surface of ``ImageMovementKernel``; its ``calc_kernel`` and the batched
 :func:`movement_kernels_frames` run on the device (``tp_motion_prepare`` / ``tp_motion_ecc``, csrc/motion.hip).  The
 restatement the device is held to is ``tests/motion_common.py``; DESIGN.md section 9 lists the deliberate differences from
-OpenCV.  The ``'wcs'`` warpmode needs astropy.wcs, which this build does not have: it is accepted by the constructor and raises
-``NotImplementedError`` wherever it would be used.
+OpenCV.
+
+The ``'wcs'`` warpmode -- the reference's default whenever the FFIs carry per-frame WCS headers (BasePhotometry.py:1185-1221) --
+takes its kernels from TAN-SIP WCS headers through :mod:`photometry_amd.wcs` (csrc/wcs.hip) instead of astropy.wcs: with a
+``wcs_ref`` (header string, card dict or :class:`~photometry_amd.wcs.TanSipWCS`), ``apply_kernel``, ``load_series``,
+``interpolate`` and ``jitter`` behave as image_motion.py:131-138, :278-313, :357-421 (``jitter`` evaluates every frame in one
+launch).  Without a ``wcs_ref`` the mode still raises ``NotImplementedError`` ("needs astropy.wcs") wherever it would be used.
 """
 
 import logging
@@ -133,7 +138,8 @@ class MovementKernel(object):
 	Parameters:
 		warpmode (str): ``'wcs'``, ``'unchanged'``, ``'translation'``, ``'euclidian'`` or ``'affine'``.
 		image_ref (2D ndarray): the reference image (prepared on the device when a kernel is first computed).
-		wcs_ref: accepted for the reference's signature; ``'wcs'`` is not available in this build.
+		wcs_ref: the reference WCS of ``'wcs'`` (header string, card dict or :class:`~photometry_amd.wcs.TanSipWCS`); given with
+			any other warpmode it raises ``NotImplementedError``.
 		ctx: the device :class:`photometry_amd.device.Context` ``calc_kernel`` runs on (default: a context on GPU 0, opened on
 			first use).
 	"""
@@ -152,9 +158,12 @@ class MovementKernel(object):
 		self.warpmode = warpmode
 		self.n_params = MovementKernel.N_PARAMS[warpmode]
 		self.image_ref = None if image_ref is None else np.array(image_ref, dtype='float32')
-		if wcs_ref is not None:
+		if wcs_ref is not None and warpmode != 'wcs':
 			_no_wcs()
 		self.wcs_ref = None
+		if wcs_ref is not None:
+			from . import wcs as wcsmod
+			self.wcs_ref = wcsmod.as_wcs(wcs_ref, ctx=ctx)
 		self.ctx = ctx
 		self._template = None
 		self._interpolator = None
@@ -173,7 +182,7 @@ class MovementKernel(object):
 		xy = np.atleast_2d(xy)
 		delta_pos = np.empty_like(xy)
 		if self.warpmode == 'wcs':
-			_no_wcs()
+			return self._wcs_jitters([kernel], xy)[0]
 		elif self.warpmode == 'unchanged':
 			delta_pos.fill(0)
 		elif self.warpmode == 'translation':
@@ -220,7 +229,7 @@ class MovementKernel(object):
 	def load_series(self, times, kernels):
 		"""Time series of kernels and its interpolator (image_motion.py:259-335); non-finite kernels are left out."""
 		if self.warpmode == 'wcs':
-			_no_wcs()
+			return self._wcs_load_series(times, kernels)
 		self.series_times = np.asarray(times)
 		self.series_kernels = np.atleast_2d(kernels)
 		expected = (len(self.series_times), self.n_params)
@@ -234,7 +243,15 @@ class MovementKernel(object):
 	def interpolate(self, time, xy):
 		"""The change of the positions ``xy`` at ``time`` from the loaded series (image_motion.py:338-399)."""
 		if self.warpmode == 'wcs':
-			_no_wcs()
+			self._wcs_needs_series()
+			k1, k2, dt, dx = self._wcs_frame_pairs(np.atleast_1d(np.asarray(time, dtype='float64')))
+			xy = np.atleast_2d(xy)
+			frames = [int(k1[0])] + ([int(k2[0])] if k2[0] >= 0 else [])
+			j = self._wcs_jitters([self.series_kernels[k] for k in frames], xy)
+			if k2[0] < 0:
+				return j[0]
+			# interp1d between the two frames (image_motion.py:383-389): slope * (time - t1) + jitter_1
+			return (j[1] - j[0]) / dt[0] * dx[0] + j[0]
 		if self._interpolator is None:
 			raise ValueError("Interpolator is not defined. ")
 		with warnings.catch_warnings():
@@ -245,9 +262,101 @@ class MovementKernel(object):
 	def jitter(self, time, column, row):
 		"""(T, 2) changes in column and row of the position (column, row) at the timestamps ``time`` (image_motion.py:402-421)."""
 		xy = np.array([column, row])
+		if self.warpmode == 'wcs':
+			return self._wcs_jitter(np.asarray(time, dtype='float64'), xy)
 		out = np.empty((len(time), 2), dtype='float64')
 		for k, t in enumerate(time):
 			out[k, :] = self.interpolate(t, xy)
+		return out
+
+
+	# -- warpmode 'wcs' ---------------------------------------------------------------------------------------------------
+	def _wcs_needs_series(self):
+		if self.wcs_ref is None:
+			_no_wcs()
+		if not getattr(self, '_wcs_loaded', False):
+			raise ValueError("Interpolator is not defined. ")
+
+	def _wcs_jitters(self, kernels, xy, d_params=None):
+		"""(len(kernels), n, 2): all_world2pix(ref.all_pix2world(xy, 0), 0, maxiter=50, quiet=True) - xy per kernel, one launch."""
+		if self.wcs_ref is None:
+			_no_wcs()
+		from . import wcs as wcsmod
+		ctx = self._context()
+		xy = np.atleast_2d(np.asarray(xy, dtype='float64'))
+		if d_params is None:
+			d_params = ctx.array(wcsmod.pack([wcsmod.as_wcs(k) for k in kernels]))
+		d_cos = wcsmod.world_directions(ctx, self.wcs_ref, xy)
+		pix, _, _ = wcsmod.world2pix_frames(ctx, d_params, len(kernels), d_cos, len(xy), np.array([0, len(xy)], dtype='int64'), 0, 1, 1e-4, 50)
+		return pix - xy[None]
+
+	def _wcs_load_series(self, times, kernels):
+		"""image_motion.py:278-313: blank headers dropped, then every frame whose first footprint corner does not come back through
+		all_world2pix(maxiter=50) (one device launch for the whole series)."""
+		if self.wcs_ref is None:
+			_no_wcs()
+		from . import wcs as wcsmod
+		if len(kernels) != len(times):
+			raise ValueError("Wrong shape of kernels.")
+		times = np.asarray(times, dtype='float64')
+		good = np.ones(len(times), dtype='bool')
+		parsed = []
+		for k, h in enumerate(kernels):
+			if isinstance(h, str) and not h.strip():
+				good[k] = False
+				continue
+			parsed.append(wcsmod.as_wcs(h))
+		ctx = self._context()
+		d_params = ctx.array(wcsmod.pack(parsed)) if parsed else None
+		if parsed:
+			ok = wcsmod.footprint_check(ctx, d_params, len(parsed)) == 0
+			idx = np.flatnonzero(good)
+			good[idx[~ok]] = False
+			parsed = [w for w, o in zip(parsed, ok) if o]
+			d_params = ctx.array(wcsmod.pack(parsed)) if parsed else None
+		self.series_times = times[good]
+		self.series_kernels = parsed
+		self._d_series = d_params
+		self._wcs_loaded = True
+
+	def _wcs_frame_pairs(self, t):
+		"""Per time: (k1, k2, t2 - t1, t - t1) of image_motion.py:357-389 (k2 = -1: frame k1's jitter alone)."""
+		st = self.series_times
+		if len(st) == 0:
+			raise ValueError("Timestamp outside timeseries interval")
+		k1 = np.empty(len(t), dtype='int32')
+		k2 = np.full(len(t), -1, dtype='int32')
+		out = (t < st[0]) | (t > st[-1])
+		if np.any(out):
+			with np.errstate(invalid='ignore'):
+				dt = np.median(np.diff(st)) if len(st) > 1 else np.nan
+			first = np.abs(t - st[0]) < dt
+			last = ~first & (np.abs(t - st[-1]) < dt)
+			if np.any(out & ~first & ~last):
+				raise ValueError("Timestamp outside timeseries interval")
+			k1[out & first] = 0
+			k1[out & last] = len(st) - 1
+		if np.any(~np.isfinite(t)):
+			raise ValueError("Timestamp outside timeseries interval")
+		inn = ~out
+		k = np.searchsorted(st, t[inn], side='right')
+		k1[inn] = k - 1
+		miss = st[k - 1] != t[inn]
+		k2i = np.where(miss, k, -1)
+		k2[inn] = k2i
+		t1 = st[k1]
+		t2 = np.where(k2 >= 0, st[np.maximum(k2, 0)], t1)
+		return k1, k2, t2 - t1, t - t1
+
+	def _wcs_jitter(self, time, xy):
+		self._wcs_needs_series()
+		k1, k2, dt, dx = self._wcs_frame_pairs(time)
+		j = self._wcs_jitters(self.series_kernels, xy, d_params=self._d_series)[:, 0, :]    # (F, 2)
+		out = j[k1].copy()
+		two = k2 >= 0
+		if np.any(two):
+			j1, j2 = j[k1[two]], j[k2[two]]
+			out[two] = (j2 - j1) / dt[two, None] * dx[two, None] + j1
 		return out
 
 
@@ -256,9 +365,18 @@ def movement_from_header(header, times=None):
 	A :class:`MovementKernel` with its series loaded from a ``.tpstack`` header (``frameio.read_header``) that carries the
 	``movement_kernel`` of the prepare stage (``attrs['movement_kernel']``: ``kernels``, ``warpmode``, ``ref_frame``) -- what
 	``BasePhotometry.MovementKernel`` builds from the HDF5 dataset (BasePhotometry.py:1185-1221).  ``times``: the timestamps of
-	the series (default: the header's ``time`` vector).  Returns None when the header holds no kernels.
+	the series (default: the header's ``time`` vector).  A header with per-frame WCS headers (``attrs['wcs_headers']``, written by
+	``frameio.write_stack(wcs_headers=...)``) gives a ``'wcs'`` kernel instead.  Returns None when the header holds no kernels.
 	"""
-	mk = (header.get('attrs') or {}).get('movement_kernel')
+	attrs = header.get('attrs') or {}
+	if attrs.get('wcs_headers') is not None:
+		# per-frame WCS headers win, as in BasePhotometry.py:1185-1221
+		times = np.asarray(header['time'] if times is None else times, dtype='float64')
+		m = MovementKernel(warpmode='wcs', wcs_ref=attrs['wcs_ref'])
+		m.load_series(times, list(attrs['wcs_headers']))
+		m.ref_frame = None
+		return m
+	mk = attrs.get('movement_kernel')
 	if mk is None:
 		return None
 	kernels = np.asarray(mk['kernels'], dtype='float64')

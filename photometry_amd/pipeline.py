@@ -10,7 +10,7 @@ for every target of the batch at once.
 import ctypes
 import os
 import numpy as np
-from . import engine, _lib
+from . import engine, _lib, wcs
 from .engine import TESS_DEFAULT_BITMASK
 from ._lib import TessphotError
 from .device import DeviceCube, device_view, round_up
@@ -1239,18 +1239,27 @@ def linpsf_frames(ctx, stack, targets, catalog, time, quality, prf_model, jitter
 	Status and messages follow the plugin: ERROR "All target flux values are NaN.", WARNING "High contamination" above 0.1.
 	``movement``: a translation :class:`~photometry_amd.motion.MovementKernel` with a loaded series instead of ``jitter``: the
 	shifts are ``movement.jitter(time - timecorr, 0.0, 0.0)`` (frames whose ECC failed come out interpolated, as ``load_series`` does).
+	A ``'wcs'`` kernel moves every star by its own shift: ``catalog_attime``'s ``interpolate`` over each stamp's catalogue as one
+	batch, formed on the device (``tp_wcs_star_positions``).
 	Returns a :class:`PSFFramesResult`.
 	"""
 	from . import psf as hpsf
 	n, T = len(targets['starid']), stack.n_cad
+	wcs_pairs = None
 	if movement is not None:
 		if jitter is not None:
 			raise ValueError("give either jitter or movement, not both")
-		if movement.warpmode != 'translation':
-			raise ValueError(f"linpsf_frames: translation movement kernels expected, got '{movement.warpmode}'")
+		if movement.warpmode not in ('translation', 'wcs'):
+			raise ValueError(f"linpsf_frames: translation or wcs movement kernels expected, got '{movement.warpmode}'")
 		t = np.asarray(time, dtype='float64')
-		# float positions: jitter() builds its position array from them, and integer ones would truncate the shifts
-		jitter = movement.jitter(t if timecorr is None else t - np.asarray(timecorr, dtype='float64'), 0.0, 0.0)
+		t = t if timecorr is None else t - np.asarray(timecorr, dtype='float64')
+		if movement.warpmode == 'wcs':
+			# per-star shifts: the frame pair of every cadence (interpolate's rule), the positions formed on the device per stamp
+			movement._wcs_needs_series()
+			wcs_pairs = movement._wcs_frame_pairs(t)
+		else:
+			# float positions: jitter() builds its position array from them, and integer ones would truncate the shifts
+			jitter = movement.jitter(t, 0.0, 0.0)
 	catalog = {k: np.asarray(v) for k, v in catalog.items()}
 	out = PSFFramesResult(n, T, 'linpsf')
 	cur, valid, groups = _psf_frame_groups(stack, targets)
@@ -1268,8 +1277,17 @@ def linpsf_frames(ctx, stack, targets, catalog, time, quality, prf_model, jitter
 		sel, star_offsets, target_index = hpsf.select_stars(cat, cat_offsets, np.asarray(targets['starid'], dtype='int64')[idx])
 		# positions = catalogue position + the cadence's shift, summed in float32 like the plugin's catalogue: formed on the device
 		# (on the host the two arrays -- 75 MB for 2 000 targets -- were most of this entry's time)
-		pos_row = engine.star_positions(ctx, ctx.array(np.ascontiguousarray(cat['row_stamp'][sel], dtype='float32')), d_jr)
-		pos_col = engine.star_positions(ctx, ctx.array(np.ascontiguousarray(cat['column_stamp'][sel], dtype='float32')), d_jc)
+		if wcs_pairs is None:
+			pos_row = engine.star_positions(ctx, ctx.array(np.ascontiguousarray(cat['row_stamp'][sel], dtype='float32')), d_jr)
+			pos_col = engine.star_positions(ctx, ctx.array(np.ascontiguousarray(cat['column_stamp'][sel], dtype='float32')), d_jc)
+		else:
+			# catalog_attime with a 'wcs' kernel: every stamp's catalogue is one batch of interpolate(), the jitter added to the
+			# float32 stamp columns (csrc/wcs.hip, tp_wcs_star_positions)
+			rows = np.arange(len(cat['row']))[sel]
+			out_index = np.full(len(cat['row']), -1, dtype='int64')
+			out_index[rows] = np.arange(len(rows))
+			pos_col, pos_row, _ = wcs.star_positions(ctx, movement._d_series, len(movement.series_kernels), movement.wcs_ref, cat_offsets,
+				np.column_stack((cat['column'], cat['row'])), cat['column_stamp'], cat['row_stamp'], out_index, len(rows), *wcs_pairs)
 		cube = engine.cut_stamps(ctx, stack.dev['images'], ctx.array(cur[idx].astype('int32')), H, W, stack.row0, stack.col0)
 		try:
 			coef = engine.linpsf_prf(ctx, base_coef, ctx.array(prf_model.weights(cur[idx])))

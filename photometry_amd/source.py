@@ -33,14 +33,20 @@ class MemoryStampSource(object):
 		catalog: dict of arrays ``starid, tmag, row, column`` (CCD coordinates) of ALL stars of the region.
 		jitter: optional ``(T, 2)`` per-cadence (column, row) shift used by ``catalog_attime``.
 		movement: optional :class:`photometry_amd.motion.MovementKernel` with a loaded series (the prepare stage's
-			``movement_kernel``): ``catalog_attime`` and ``pos_corr`` then come from it as in BasePhotometry.py:473, :1224-1258.
+			``movement_kernel``, or a ``'wcs'`` kernel): ``catalog_attime`` and ``pos_corr`` then come from it as in
+			BasePhotometry.py:473, :1224-1258.
+		wcs: optional reference WCS (header string, card dict or :class:`photometry_amd.wcs.TanSipWCS`).  A ``catalog`` with
+			``ra`` / ``dec`` and no ``row`` / ``column`` is projected through it (all_world2pix, origin 0, the whole catalogue as
+			one batch) into float32 columns, and ``targets`` with ``ra`` / ``dec`` get float64 positions, one target per call
+			(BasePhotometry.py:461, :1159-1170).  As there, ``all_world2pix`` runs with its defaults (maxiter 20, not quiet): a point
+			that does not converge raises :class:`photometry_amd.wcs.NoConvergence`.  Sources that give pixel positions are left as they are.
 			Not together with ``jitter``.
 		frames may also hold ``pixel_flags`` (uint8 ``(R, C, T)``: the ``pixel_flags/%04d`` images of the prepare stage).
 		backgrounds_pixels_used: optional bool ``(R, C)`` image of the prepare stage (BasePhotometry.py:1052-1061).
 	"""
 
 	def __init__(self, frames, row0, col0, time, timecorr, cadenceno, quality, catalog, sector=1, camera=1, ccd=1,
-		cadence=1800, n_readout=720, jitter=None, prf=None, targets=None, backgrounds_pixels_used=None, movement=None):
+		cadence=1800, n_readout=720, jitter=None, prf=None, targets=None, backgrounds_pixels_used=None, movement=None, wcs=None):
 		if jitter is not None and movement is not None:
 			raise ValueError("give either jitter or movement, not both")
 		self.frames = {k: np.asarray(v, dtype='uint8' if k == 'pixel_flags' else 'float32') for k, v in frames.items()}
@@ -53,6 +59,21 @@ class MemoryStampSource(object):
 		self.cadenceno = np.asarray(cadenceno, dtype='int32')
 		self.quality = np.asarray(quality, dtype='int32')
 		self.catalog = {k: np.asarray(v) for k, v in catalog.items()}
+		self.wcs = None
+		if wcs is not None:
+			from .wcs import as_wcs
+			self.wcs = as_wcs(wcs)
+			if 'row' not in self.catalog and 'column' not in self.catalog and 'ra' in self.catalog and 'dec' in self.catalog:
+				# BasePhotometry.py:1159-1170: the catalogue projected through the reference WCS into float32 pixel columns
+				px = self.wcs.all_world2pix(np.column_stack((self.catalog['ra'], self.catalog['dec'])), 0)
+				self.catalog['column'] = px[:, 0].astype('float32')
+				self.catalog['row'] = px[:, 1].astype('float32')
+			if targets is not None and 'row' not in targets and 'column' not in targets and 'ra' in targets and 'dec' in targets:
+				# BasePhotometry.py:461: each main target's float64 position, projected on its own
+				targets = dict(targets)
+				pos = np.array([self.wcs.all_world2pix(np.array([[r, d]], dtype='float64'), 0)[0]
+					for r, d in zip(np.asarray(targets['ra'], dtype='float64'), np.asarray(targets['dec'], dtype='float64'))]).reshape(-1, 2)
+				targets['column'], targets['row'] = pos[:, 0], pos[:, 1]
 		self.sector, self.camera, self.ccd, self.cadence, self.n_readout = sector, camera, ccd, cadence, n_readout
 		self.jitter = None if jitter is None else np.asarray(jitter, dtype='float64')
 		self.movement = movement
