@@ -23,10 +23,14 @@ issued EVERY step on a second stream from the other half of a double-buffered ou
 step's compute; its duration is reported separately.
 
 The legs live in benchlib/ (one module per leg); this file parses the arguments, runs the timed region and assembles the line.
-Rank 0 prints ONE JSON line.  Besides the contract's fields it carries `roofline` (dominant kernel of the timed step),
+Rank 0 prints ONE JSON line.  Besides the contract's fields it carries `roofline` (dominant kernel of the timed step) and
 `rooflines` (every HBM-bound kernel of the step, necessary bytes / time / 8 TB/s -- a fraction above 1 is impossible by
-construction), `cpu_baseline`, and at N = 1 the extra legs `aperture_premade_cubes` (the per-target stage alone, SURVEY 8d's
-reading), `linpsf` (BASELINE configs[3]) and `end_to_end` (cubes start in pinned host memory: H2D overlapped with compute).
+construction), both from the timed steps' own HIP-event profile.
+A plain run does only that: it sets up, warms up, times the steps, writes the dump if asked and prints the line.  `--full`
+adds what takes runs of its own: `cpu_baseline` (the oracle on a sample of the same cubes), and at N = 1 the extra legs
+`aperture_premade_cubes` (the per-target stage alone, SURVEY 8d's reading), `stages`, `end_to_end` (cubes start in pinned host
+memory: H2D overlapped with compute), `linpsf` (BASELINE configs[3]), the frames-to-results entries, `psf_fit` and
+`fit_background_frames`.
 `--dump-outputs DIR` writes what the last timed step computed under DIR (benchlib/dump.py), to compare two builds output for output.
 """
 
@@ -57,6 +61,8 @@ def parse_args(argv=None):
 	p.add_argument('--scaling', choices=('weak', 'strong'), default='weak', help='c4: weak = 12 500 targets per GPU, strong = 100 000 targets over the N GPUs')
 	p.add_argument('--cadences', type=int, default=1300)
 	p.add_argument('--stamp', type=int, default=15)
+	p.add_argument('--full', action='store_true', help='besides the headline, the CPU baseline (--cpu-sample, --cpu-procs) '
+		'and at N = 1 the extra legs (--no-extra and the leg sizes below); without it a run times the steps and prints the line')
 	p.add_argument('--cpu-sample', type=int, default=4, help='targets per worker process of the CPU baseline (0 = skip)')
 	p.add_argument('--cpu-procs', type=int, default=0, help='worker processes of the all-core CPU baseline (0 = physical cores)')
 	p.add_argument('--seed', type=int, default=1)
@@ -67,7 +73,7 @@ def parse_args(argv=None):
 	p.add_argument('--no-compact', action='store_true', help='N > 1: gather the full float64 block instead of the compact one (flux, flux_err, flux_background as float32)')
 	p.add_argument('--host-group', choices=('socket', 'gloo'), default='socket', help='N > 1: the host-side group (rendezvous, barriers, RCCL id): '
 		'plain TCP sockets (no PyTorch) or torch.distributed gloo')
-	p.add_argument('--no-extra', action='store_true', help='skip the extra legs (premade cubes, LinPSF, end to end, stages)')
+	p.add_argument('--no-extra', action='store_true', help='--full: skip the extra legs (premade cubes, LinPSF, end to end, stages, ...)')
 	p.add_argument('--e2e-targets', type=int, default=2048, help='targets of the end-to-end (H2D included) leg (0 = skip)')
 	p.add_argument('--frame', type=int, default=1024, help='side of the frame stack of the stamp-cutter stage (0 = skip)')
 	p.add_argument('--psf-targets', type=int, default=4096, help='targets of the non-linear PSF photometry leg (0 = skip)')
@@ -128,7 +134,9 @@ def main():
 	P = H * W
 	scene = simulate.make_scene(Nt, T, H, W, seed=args.seed * 1000 + rank)
 	scene.aperture = None
-	extras = (world == 1) and (workload == 'c2') and not args.no_extra
+	# the extra legs need the premade-cube inputs beside the raw cube: a plain run leaves them out (the raw and error cubes, and
+	# so every timed step, are the same either way: tp_synth_fill draws each cube element from its own counter)
+	extras = args.full and (world == 1) and (workload == 'c2') and not args.no_extra
 	worker = sharded.DeviceShardWorker(ctx, scene, capacity=Nt, psf=psf, nbuf=2 if world > 1 else 1, extras=extras)
 	run = sharded.ShardedRun(worker, Nt * world, rank=rank, world=world, group=group,
 		gather='none' if args.no_gather else 'auto', when='step', shared_device=shared_device, compact=not args.no_compact)
@@ -282,7 +290,7 @@ def main():
 		from benchlib.legs.stages import leg_stages
 		result['aperture_premade_cubes'] = leg_premade(ctx, scene, cubes, args, Nt, T, H, W, np, engine, pipeline)
 		result['stages'] = leg_stages(ctx, scene, cubes, batch, work, args, Nt, T, H, W, np, engine, pipeline)
-	if rank == 0 and world == 1 and workload == 'c2' and args.cpu_sample > 0:
+	if rank == 0 and args.full and world == 1 and workload == 'c2' and args.cpu_sample > 0:
 		from benchlib.cpu import cpu_baseline
 		bound = os.sched_getaffinity(0)
 		os.sched_setaffinity(0, all_cpus)     # the CPU baseline gets every core the box gives, not only the GPU's NUMA node

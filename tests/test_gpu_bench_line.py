@@ -31,6 +31,18 @@ def test_single_gpu_line(tmp_path):
 	assert full['value'] == pytest.approx(d['value'], rel=1e-5) and 'kernels' in full
 
 
+def test_plain_run_measures_the_headline_only(tmp_path):
+	"""Without --full nothing runs beside the warm-up and the timed steps: no CPU baseline and no extra leg in the full result."""
+	d = _run([sys.executable, 'bench.py', '--gpus', '1', '--steps', '2', '--warmup', '1', '--targets', '512', '--cadences', '200'], tmp_path)
+	full = json.load(open(os.path.join(ROOT, bl.LEGS_FILE)))
+	assert full['value'] == pytest.approx(d['value'], rel=1e-5) and 'legs' not in d
+	for k in ('cpu_baseline', 'parity_sample', 'aperture_premade_cubes', 'stages', 'end_to_end', 'linpsf', 'frames_to_results',
+			'psf_frames_to_results', 'psf_fit', 'fit_background_frames', 'frames_to_results_large_batch'):
+		assert k not in full, k
+	kernels = full['kernels']
+	assert kernels['tp_bkg_stamp_sum_kernel']['launches'] == 2 and kernels['tp_aperture_fused_kernel']['launches'] == 2
+
+
 def test_dump_outputs_of_the_last_step(tmp_path):
 	"""--dump-outputs: the arrays of the last timed step in float32 / float64, every file finite (the NaN of the light curves in
 	their _nonfinite files), under 64 MB, the same from run to run (seeded inputs); --steps sets the number of timed steps."""

@@ -6,7 +6,7 @@ OUT=$REPO/gpurun_out/fetchcal2
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --pmc TCC_EA0_RDREQ_sum TCC_BUBBLE_sum TCC_MISS_sum TCC_EA0_RDREQ_32B_sum --output-format csv -d $OUT/cal -- $REPO/tools/fetchcal > $OUT/cal.log 2>&1
-rocprofv3 --pmc TCC_EA0_RDREQ_sum TCC_BUBBLE_sum TCC_MISS_sum TCC_EA0_RDREQ_32B_sum --output-format csv -d $OUT/bench -- python3 $REPO/bench.py --steps 2 --warmup 1 --cpu-sample 0 --e2e-targets 0 --frames-targets 0 --frame 0 --psf-targets 0 --fullframe-frames 0 > $OUT/bench.json 2> $OUT/bench.log
+rocprofv3 --pmc TCC_EA0_RDREQ_sum TCC_BUBBLE_sum TCC_MISS_sum TCC_EA0_RDREQ_32B_sum --output-format csv -d $OUT/bench -- python3 $REPO/bench.py --full --steps 2 --warmup 1 --cpu-sample 0 --e2e-targets 0 --frames-targets 0 --frame 0 --psf-targets 0 --fullframe-frames 0 > $OUT/bench.json 2> $OUT/bench.log
 cd $REPO
 python3 - "$OUT" <<'PY'
 import csv, glob, os, re, sys
