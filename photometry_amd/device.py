@@ -246,9 +246,6 @@ class Context(object):
 			if eng is not None:
 				eng.close()
 			self.pinned_trim()
-			for c in self.__dict__.get('_side', []):
-				c.close()
-			self.__dict__['_side'] = []
 			self.lib.tp_ctx_destroy(self.handle)
 			self.handle = None
 
@@ -311,14 +308,6 @@ class Context(object):
 		for free in self.__dict__.get('_pinned_pool', {}).values():
 			while free:
 				free.pop().free()
-
-	def side_contexts(self, n):
-		"""``n`` further contexts (= HIP streams) on this device, created once: independent passes of a batched entry (the groups
-		of stamp sizes of a round) run on them side by side."""
-		side = self.__dict__.setdefault('_side', [])
-		while len(side) < n:
-			side.append(Context(self.device, high_priority=False))
-		return side[:n]
 
 	def download_async(self, pinned, device_array, nbytes=None, host_offset=0):
 		"""Enqueue a device -> pinned-host copy on this context's stream (returns at once)."""

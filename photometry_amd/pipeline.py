@@ -13,7 +13,7 @@ import numpy as np
 from . import engine, _lib, wcs
 from .engine import TESS_DEFAULT_BITMASK
 from ._lib import TessphotError
-from .device import DeviceCube, device_view, round_up
+from .device import DeviceCube, device_view
 
 
 class ApertureBatch(object):
@@ -88,12 +88,6 @@ class ApertureBatch(object):
 			self.aperture.fill_bytes(1)
 		else:
 			self.aperture = ctx.array(np.asarray(ap, dtype='int32'))
-
-	def release_host(self):
-		"""The page-locked block the metadata were uploaded from goes back to the context's pool (call after a synchronisation)."""
-		h = self.__dict__.pop('_meta_host', None)
-		if h is not None:
-			self.ctx.pinned_release(h)
 
 	def __del__(self):
 		# the upload may still be in flight when the last reference goes: wait for the stream, then the block goes back to the pool
@@ -193,7 +187,7 @@ class ApertureWork(object):
 		return v
 
 
-def aperture_step(ctx, batch, work, masks_from=None, fused=True, sumimage_given=False):
+def aperture_step(ctx, batch, work, masks_from=None, fused=True):
 	"""
 	One pass of the aperture hot path over the batch; everything stays in HBM.
 
@@ -203,16 +197,6 @@ def aperture_step(ctx, batch, work, masks_from=None, fused=True, sumimage_given=
 	on-device K2P2 (used by tests that inject the oracle's masks; implies the stand-alone kernels).
 	"""
 	subtract, backgrounds = None, batch.backgrounds
-	if sumimage_given:
-		# ``work.sumimage`` already holds the sum images (the FFI branch of BasePhotometry.sumimage: crops of the region's): A2..A7
-		if batch.raw_mode or masks_from is not None:
-			raise ValueError('sumimage_given: calibrated cubes and the on-device masks only')
-		if fused:
-			engine.aperture_photometry(ctx, batch, work, backgrounds=backgrounds, sumimage_given=True)
-			return work
-		engine.k2p2_masks(ctx, batch, work)
-		engine.aperture_extract(ctx, batch.images, batch.images_err, backgrounds, work.mask, batch.stamps, status=work.status, out=work.lc)
-		return work
 	if batch.raw_mode and fused and masks_from is None:
 		# the raw cube is read ONCE: B*, B2 and the sum image of raw - background (A1 with B3 on the fly) in one pass,
 		# then the mask and the extraction, which read in-mask pixel rows only
@@ -423,34 +407,6 @@ class FrameStack(object):
 			self._time_major = (out, t_pitch)
 		return self._time_major
 
-	def cut_lazy(self, ctx, stamps, height, width):
-		"""The cut cubes of a group on ``ctx``'s stream, the stamp list uploaded there too."""
-		d = ctx.array(np.asarray(stamps, dtype='int32'))
-		cubes = self.cut(d, height, width, ctx=ctx)
-		cubes['_stamps'] = d   # alive until the cut has run
-		return cubes
-
-	def cut(self, stamps_dev, height, width, ctx=None):
-		"""The three stamp cubes of a group of same-sized stamps (``tp_cut_stamps``), on ``ctx``'s stream (default: the stack's)."""
-		ctx = self.ctx if ctx is None else ctx
-		cubes = engine.cut_stamps_multi(ctx, [self.dev[k] for k in self.names], stamps_dev, height, width, self.row0, self.col0)
-		return dict(zip(self.names, cubes))
-
-
-class _Messages(object):
-	"""Collects what the reference's plugin would have logged at WARNING level and above, as ``"LEVEL: message"`` strings."""
-	def __init__(self):
-		self.items = []
-
-	def error(self, msg, *a):
-		self.items.append('ERROR: ' + (msg % a if a else msg))
-
-	def warning(self, msg, *a):
-		self.items.append('WARNING: ' + (msg % a if a else msg))
-
-	def info(self, msg, *a):
-		pass
-
 
 def _catalog_of_stamp(catalog, stamp, buffer_size=5):
 	"""Stars inside the stamp plus its 5-pixel buffer with the float32 stamp coordinates of BasePhotometry.catalog
@@ -529,23 +485,6 @@ def _catalogs_of_stamps(index, stamps, buffer_size=5):
 	return offsets, arrays
 
 
-class _GroupScene(object):
-	"""The metadata of a group of same-sized stamps in the form ``ApertureBatch`` takes (no host cubes)."""
-	def __init__(self, stack, time, quality, cadence_s, stamps_list, cat_offsets, cat_arrays, targets, idx):
-		self.n_targets = len(idx)
-		self.n_cad = stack.n_cad
-		self.height, self.width = stamps_list[0][1] - stamps_list[0][0], stamps_list[0][3] - stamps_list[0][2]
-		self.time, self.quality, self.cadence_s = time, quality, cadence_s
-		self.stamps = np.asarray(stamps_list, dtype='int32')
-		self.cat_offsets = cat_offsets
-		self.catalog = cat_arrays
-		self.target_pos_row = np.asarray(targets['row'], dtype='float64')[idx]
-		self.target_pos_column = np.asarray(targets['column'], dtype='float64')[idx]
-		self.target_tmag = np.asarray(targets['tmag'], dtype='float64')[idx]
-		self.target_starid = np.asarray(targets['starid'], dtype='int64')[idx]
-		self.aperture = None
-
-
 class _RawBlock(object):
 	"""``nbytes`` bytes at ``address`` through the array interface (no ctypes array type per size)."""
 	__slots__ = ('__array_interface__',)
@@ -581,15 +520,11 @@ class FramesResult(object):
 		#: live as long as this result: :meth:`release` (and the result's deletion) hands the blocks to the next job's download.  Copy
 		#: what has to outlive the result (``result[i]`` does: the per-target dict holds copies).
 		self.groups = []
-		self._pinned = []      # (context, block): returned to the context's pool when the result goes
 		self._job = None       # the native job (pipeline.FramesEngine) whose page-locked blocks the group arrays view
 
 	def release(self):
 		"""Give the page-locked blocks behind the group arrays back to their pool: the group arrays must not be used afterwards
 		(they are dropped from ``groups``; a view a caller kept would read the next job's data)."""
-		for ctx, blk in self._pinned:
-			ctx.pinned_release(blk)
-		self._pinned = []
 		self.groups = []
 		job, self._job = self._job, None
 		if job is not None:
@@ -648,7 +583,7 @@ class FramesResult(object):
 		return (self[i] for i in range(self.n))
 
 
-#: what the native engine reports as codes (csrc/frames.cpp) in the words of the reference's plugin / of the Python rounds below
+#: what the native engine reports as codes (csrc/frames.cpp) in the words of the reference's plugin
 _EVENT_TEXT = {1: 'ERROR: No flux above threshold.', 2: 'WARNING: No masks found. Using minimum aperture.',
 	3: 'WARNING: No mask found for main target. Using minimum aperture.', 4: 'ERROR: Too many masks.',
 	6: 'WARNING: Could not resize stamp any further.', 7: 'ERROR: Stamp resize hit limit. Haloswitch quick break.',
@@ -839,7 +774,7 @@ class FramesEngine(object):
 			self.lib.tp_frames_engine_destroy(h)
 
 
-def aperture_frames(ctx, stack, targets, catalog, time, quality, settings=None, cadence_s=1800, datasource='ffi', engine='native'):
+def aperture_frames(ctx, stack, targets, catalog, time, quality, settings=None, datasource='ffi'):
 	"""
 	``AperturePhotometry.do_photometry`` INCLUDING its stamp-resize loop (photometry.py:75-170) for every target of a CCD region
 	held in a :class:`FrameStack`: round after round, the targets still in play are grouped by stamp size, their stamps are cut
@@ -852,313 +787,50 @@ def aperture_frames(ctx, stack, targets, catalog, time, quality, settings=None, 
 	stamp_resizes, errors`` and, unless the target ended in an error before the extraction, ``mask, sumimage, flux, flux_err,
 	flux_background, pos_centroid, contamination, skip_targets, diagnostics``).  The common case -- the mask does not touch an
 	edge and nothing is logged -- is decided for a whole group with array operations; only the targets that resize, warn or fail
-	take the per-target path.
-
-	``engine``: ``'native'`` (default) -- the rounds are driven by a worker thread of the library (``csrc/frames.cpp``,
-	:class:`FramesEngine`): the host submits the batch and collects it; ``'python'`` -- the same rounds as a Python generator
-	(:func:`_frames_job`, the implementation the native engine is held to in ``tests/test_gpu_resize.py``).
+	take the per-target path.  The rounds are driven by a worker thread of the library (``csrc/frames.cpp``, :class:`FramesEngine`):
+	the host submits the batch and collects it.
 	"""
-	if engine == 'python':
-		job = _frames_job(ctx, stack, targets, catalog, time, quality, settings, cadence_s, datasource, [ctx] + ctx.side_contexts(2))
-		while True:
-			try:
-				next(job)
-			except StopIteration as done:
-				return done.value
 	eng = FramesEngine.of(ctx)
 	return eng.submit(stack, targets, eng.catalog(catalog), time, quality, settings=settings, datasource=datasource).collect()
 
 
-def aperture_frames_pipelined(ctx, stack, batches, catalog, time, quality, settings=None, cadence_s=1800, datasource='ffi', in_flight=4, engine='native'):
+def aperture_frames_pipelined(ctx, stack, batches, catalog, time, quality, settings=None, datasource='ffi', in_flight=4):
 	"""
 	:func:`aperture_frames` over consecutive batches of targets of one CCD region (``batches``: an iterable of ``targets`` dicts),
 	``in_flight`` of them at a time, each on its own streams: the rounds of a batch are a strict chain -- queue the passes, wait,
 	decide, queue the next round -- whose later links are a few latency-bound passes over the resized stamps that leave most of
 	the chip idle, so the first round of the next batch runs under them and the host decides one batch while the device works on
 	the other.  Yields one :class:`FramesResult` per batch, in order; every batch gives what a call of its own would.
-	With the native engine (default) every batch is a job of :class:`FramesEngine`: submitted, driven by its own worker thread of
-	the library, collected in order -- the host touches a batch twice.
+	Every batch is a job of :class:`FramesEngine`: submitted, driven by its own worker thread of the library, collected in order --
+	the host touches a batch twice.
 	"""
-	if engine != 'python':
-		from collections import deque
-		# four streams per slot (three of the engine's pool and a copy stream): beyond ~24 streams in the process its hardware queues
-		# are oversubscribed and time-sliced -- measured in round 5: 3.8-4.2 x 10^5 targets/s with four or five jobs in flight, 2.4-2.9 x 10^5 with six
-		in_flight = max(1, min(int(in_flight), FramesEngine.MAX_SLOTS))
-		eng = FramesEngine.of(ctx, slots=in_flight)
-		cat = eng.catalog(catalog)
-		# results are yielded in the order of the batches, but a slot is handed on as soon as ANY job is done: the jobs of a run take
-		# 5 - 15 ms each (three to ten groups, one to five rounds), and waiting for the oldest left finished ones holding their slots
-		queue, finished, serial, next_out = deque(), {}, 0, 0
-		for targets in batches:
-			while len(queue) >= in_flight:
-				# (at most in_flight results wait for an older batch: beyond that the oldest job is waited for)
-				k = 0 if len(finished) >= in_flight else next((k for k, (_, job) in enumerate(queue) if job.done()), 0)
-				s, job = queue[k]
-				del queue[k]
-				finished[s] = job.collect()
-				while next_out in finished:
-					yield finished.pop(next_out)
-					next_out += 1
-			queue.append((serial, eng.submit(stack, targets, cat, time, quality, settings=settings, datasource=datasource, budget_share=1.0 / in_flight)))
-			serial += 1
-		while queue:
-			s, job = queue.popleft()
+	from collections import deque
+	# four streams per slot (three of the engine's pool and a copy stream): beyond ~24 streams in the process its hardware queues
+	# are oversubscribed and time-sliced -- measured in round 5: 3.8-4.2 x 10^5 targets/s with four or five jobs in flight, 2.4-2.9 x 10^5 with six
+	in_flight = max(1, min(int(in_flight), FramesEngine.MAX_SLOTS))
+	eng = FramesEngine.of(ctx, slots=in_flight)
+	cat = eng.catalog(catalog)
+	# results are yielded in the order of the batches, but a slot is handed on as soon as ANY job is done: the jobs of a run take
+	# 5 - 15 ms each (three to ten groups, one to five rounds), and waiting for the oldest left finished ones holding their slots
+	queue, finished, serial, next_out = deque(), {}, 0, 0
+	for targets in batches:
+		while len(queue) >= in_flight:
+			# (at most in_flight results wait for an older batch: beyond that the oldest job is waited for)
+			k = 0 if len(finished) >= in_flight else next((k for k, (_, job) in enumerate(queue) if job.done()), 0)
+			s, job = queue[k]
+			del queue[k]
 			finished[s] = job.collect()
 			while next_out in finished:
 				yield finished.pop(next_out)
 				next_out += 1
-		return
-	catalog = {k: np.asarray(v) for k, v in catalog.items()}
-	cat_index = _CatalogIndex(catalog)
-	every = [ctx] + ctx.side_contexts(3 * in_flight - 1)
-	free_slots = list(range(in_flight))[::-1]
-	source = iter(batches)
-	running, finished, order, exhausted = [], {}, 0, False   # running: [serial, slot, generator]
-	next_out = 0
-	while True:
-		while not exhausted and free_slots:
-			try:
-				targets = next(source)
-			except StopIteration:
-				exhausted = True
-				break
-			slot = free_slots.pop()
-			job = _frames_job(ctx, stack, targets, catalog, time, quality, settings, cadence_s, datasource, every[3 * slot:3 * slot + 3], cat_index, 1.0 / in_flight)
-			running.append([order, slot, job])
-			order += 1
-			try:
-				next(job)   # the first round of the new batch is queued before the older ones are waited for
-			except StopIteration as done:
-				serial, slot, _ = running.pop()
-				finished[serial] = done.value
-				free_slots.append(slot)
-		if not running and exhausted:
-			break
-		for entry in list(running):
-			try:
-				next(entry[2])
-			except StopIteration as done:
-				running.remove(entry)
-				finished[entry[0]] = done.value
-				free_slots.append(entry[1])
+		queue.append((serial, eng.submit(stack, targets, cat, time, quality, settings=settings, datasource=datasource, budget_share=1.0 / in_flight)))
+		serial += 1
+	while queue:
+		s, job = queue.popleft()
+		finished[s] = job.collect()
 		while next_out in finished:
 			yield finished.pop(next_out)
 			next_out += 1
-	while next_out in finished:
-		yield finished.pop(next_out)
-		next_out += 1
-
-
-def _frames_job(ctx, stack, targets, catalog, time, quality, settings, cadence_s, datasource, streams, cat_index=None, budget_share=1.0):
-	"""The rounds of :func:`aperture_frames` as a generator: it yields wherever the host would wait for the device (after the
-	passes of a round are queued; before the last light curves have arrived) and returns the :class:`FramesResult`.  ``streams``:
-	the contexts of this job (the first one takes the large groups); ``cat_index``: a prebuilt index of ``catalog``."""
-	from . import stamps as st
-	from .plugins import load_settings, mag2flux, mask_outcome
-	from ._lib import TessphotError
-	settings = load_settings() if settings is None else settings
-	tmag_limit = settings.getfloat('haloswitch', 'tmag_limit')
-	flux_limit = settings.getfloat('haloswitch', 'flux_limit')
-	n = len(targets['starid'])
-	catalog = {k: np.asarray(v) for k, v in catalog.items()}
-	time = np.asarray(time, dtype='float64')
-	quality = np.asarray(quality, dtype='int32')
-	tmags = np.asarray(targets['tmag'], dtype='float64')
-	out = FramesResult(n)
-	full_sumimage = None if datasource.startswith('tpf:') else stack.sumimage_for(quality)   # (BasePhotometry.py:1001-1019: crop for FFI targets, own sum for stamps)
-	log = {}
-	def logger_of(i):
-		if i not in log:
-			log[i] = _Messages()
-		return log[i]
-	first, valid = st.default_stamps(targets['row'], targets['column'], targets['tmag'], stack.limits)
-	cur = np.asarray(first, dtype='int64').copy()
-	for i in np.flatnonzero(~valid): # BasePhotometry.py:671-672: the constructor raises -> STATUS.ERROR through tessphot
-		out.status[i] = 2
-		out.errors[int(i)] = ['ValueError: Invalid stamp selected']
-		out.stamp[i] = (-1, -2, -1, -2)
-	cat_index = _CatalogIndex(catalog) if cat_index is None else cat_index
-	attempts_left = np.where(tmags < 6, 10, 5).astype('int64')   # photometry.py:70-73 (stamps.retry_limit)
-	active = np.flatnonzero(valid)
-	edge_bits = sum(bit for _name, bit, _idx, _sign in st.SIDES)
-
-	def finish(i, status):
-		out.status[i] = int(status)
-		out.stamp[i] = cur[i]
-		if i in log and log[i].items:
-			out.errors[i] = out.errors.get(i, []) + log[i].items
-			log[i].items = []
-
-	from . import comm as tpcomm
-	events, pending = [], []
-	if '_hbm_bytes' not in ctx.__dict__:
-		ctx.__dict__['_hbm_bytes'] = ctx.info()['hbm_bytes']
-	budget = (float(os.environ.get('TESSPHOT_FRAMES_BUDGET_GB', 0)) * 1e9 or ctx.__dict__['_hbm_bytes'] / 4.0) * budget_share   # (jobs in flight share it)
-	while len(active):
-		heights, widths = cur[active, 1] - cur[active, 0], cur[active, 3] - cur[active, 2]
-		keys = heights * 100000 + widths
-		still = []
-		# the groups of this round (targets that share a stamp size), cut into parts whose cubes and output blocks fit a budget of
-		# device memory: a full CCD has tens of thousands of targets beside 65 GB of resident frame stacks, and an out-of-memory
-		# error would cost every target of the part its result (a quarter of the HBM by default, TESSPHOT_FRAMES_BUDGET_GB)
-		jobs = []
-		for key in np.unique(keys):
-			idx_all = active[keys == key]
-			H, W = int(key // 100000), int(key % 100000)
-			per_target = 3 * H * W * round_up(stack.n_cad, 32) * 4 + 5 * stack.n_cad * 8 + H * W * 9 + 256
-			nmax = max(1, int(budget // per_target))
-			for a0 in range(0, len(idx_all), nmax):
-				jobs.append((idx_all[a0:a0 + nmax], H, W, per_target * len(idx_all[a0:a0 + nmax])))
-		parts, acc = [[]], 0
-		for idx_j, H, W, nbytes_j in jobs:
-			if parts[-1] and acc + nbytes_j > budget:
-				parts.append([])
-				acc = 0
-			parts[-1].append((idx_j, H, W))
-			acc += nbytes_j
-		for part in parts:
-			# ---- the device passes of all groups of this round are queued first, round-robin on a few streams (a group of a few large
-			# stamps is a latency-bound pass of ~1 ms that hides under the pass of the 15 x 15 group), each pass ending with ONE
-			# download of its packed output block into page-locked memory; then the results are decided group by group
-			launched = []
-			for gi, (idx, H, W) in enumerate(part):
-				g = streams[gi % len(streams)] if len(idx) < 256 or gi == 0 else streams[0]
-				cubes = host = None
-				try:
-					if H * W > 32767:
-						raise TessphotError(1, f'a {H}x{W} stamp is beyond the 32 767 pixels of the mask builder')
-					# the stamps are cut while the host selects the catalogue stars of the group
-					cut = stack.cut_lazy(g, cur[idx], H, W)
-					cubes = {k: cut[k] for k in stack.names}
-					cat_offsets, cat_arrays = _catalogs_of_stamps(cat_index, cur[idx])
-					scene = _GroupScene(stack, time, quality, cadence_s, cur[idx], cat_offsets, cat_arrays, targets, idx)
-					batch = ApertureBatch(g, scene, cubes=cut)
-					work = ApertureWork(g, batch, packed=True, cat_capacity=max(int(cat_offsets[-1]), 1), extras=True)
-					# a small group is a latency-bound pass: the three stand-alone kernels spread A1 and A6 over the chip where the fused launch
-					# gives each target one wavefront (8 targets of 25 x 25: 1.03 against 1.47 ms; bit-identical outputs)
-					# the sum images: crops of the region's (BasePhotometry.py:1001-1006), as in the native engine
-					if full_sumimage is not None:
-						engine.crop_sumimage(g, full_sumimage, cut['_stamps'], H, W, stack.row0, stack.col0, out=work.sumimage)
-					aperture_step(g, batch, work, fused=len(idx) >= 1024, sumimage_given=full_sumimage is not None)
-					aperture_diagnostics(g, batch, work)
-					host = g.pinned_block(work.block.nbytes)
-					# two copies: what the decisions of this round read (flags, masks, sum images ...: everything behind the light curves in
-					# the block) first, with an event; the light curves (97 % of the bytes) travel while the next round is decided and queued
-					lc_bytes = work.block_layout['contamination'][0]
-					g.download_async(host, device_view(g, work.block.ptr + lc_bytes, (work.block.nbytes - lc_bytes,), 'uint8'), host_offset=lc_bytes)
-					ev = events.pop() if events else g.event()
-					g.record(ev)
-					g.download_async(host, device_view(g, work.block.ptr, (lc_bytes,), 'uint8'))
-					launched.append((g, idx, H, W, scene, cat_offsets, cat_arrays, cubes, batch, work, host, ev))
-				except TessphotError as e:
-					# e.g. a stamp beyond 32 767 pixels (the mask builder's signed 16-bit labels): Halo territory upstream
-					try:
-						g.sync()
-					except TessphotError:
-						pass
-					if cubes is not None:
-						for c in cubes.values():
-							c.free()
-					if host is not None:
-						g.pinned_release(host)
-					for i in idx:
-						logger_of(int(i)).error('Device pass failed for a %dx%d stamp: %s', H, W, str(e))
-						finish(int(i), 2)
-			yield   # the passes of this part run: the caller may serve another job meanwhile
-			failed = None
-			for (g, idx, H, W, scene, cat_offsets, cat_arrays, cubes, batch, work, host, ev) in launched:
-				try:
-					g.event_sync(ev)      # the small part of the group's block is on the host (its light curves may still be on their way)
-				except TessphotError as e:   # a device error surfaces here: every group of the round is lost
-					failed = e
-				events.append(ev)
-				for c in cubes.values():
-					c.free()
-				pending.append((g, batch, work))   # alive until the light curves have arrived
-				if failed is not None:
-					g.pinned_release(host)
-					for i in idx:
-						logger_of(int(i)).error('Device pass failed for a %dx%d stamp: %s', H, W, str(failed))
-						finish(int(i), 2)
-					continue
-				res = tpcomm.unpack_block(host.array[:work.block.nbytes], work.block_layout)
-				out._pinned.append((g, host))
-				grp = dict(res, cat_offsets=cat_offsets, cat_starid=cat_arrays['starid'], target_starid=scene.target_starid)
-				gid = len(out.groups)
-				out.groups.append(grp)
-				attempts_left[idx] -= 1
-				flags = res['flags'].astype('int64')
-				kind = flags >> 8
-				# ---- the common case, for the whole group at once: nothing to log, no edge touched -> the attempt stands
-				simple = ((flags & (1 | 32 | edge_bits)) == 0) & (kind == 0)
-				done = idx[simple]
-				out.status[done] = res['status'][simple]
-				out.stamp[done] = cur[done]
-				out.has_result[done] = True
-				out.group[done] = gid
-				out.pos[done] = np.flatnonzero(simple)
-				for i in done:   # what an earlier round logged for the target (it went on with a bigger stamp) stays in its details
-					if int(i) in log and log[int(i)].items:
-						finish(int(i), int(out.status[i]))
-				# ---- the others, one by one with the plugin's rules
-				for j in np.flatnonzero(~simple):
-					i = int(idx[j])
-					fl = int(flags[j])
-					try:
-						if mask_outcome(fl, logger_of(i)) == 'error':
-							finish(i, 2)
-							continue
-					except RuntimeError as e: # an uncaught exception of the reference's plugin -> STATUS.ERROR (tessphot.py:37-49)
-						out.errors[i] = out.errors.get(i, []) + ['RuntimeError: ' + str(e)]
-						finish(i, 2)
-						continue
-					wanted = st.edge_requests(fl)
-					if wanted:
-						before = tuple(int(v) for v in cur[i])
-						new = st.moved(before, stack.limits, **wanted)
-						if new == before:
-							logger_of(i).warning("Could not resize stamp any further.")
-						else:
-							out.stamp_resizes[i] += 1
-							cur[i] = new
-							mask = res['mask'][j].astype(bool)
-							bright = tmags[i] <= tmag_limit and not datasource.startswith('tpf:')
-							stuck = st.quick_break_flux(res['sumimage'][j], mask, before, new, wanted) if bright else None
-							if stuck is not None and stuck > flux_limit * mag2flux(tmags[i]):
-								logger_of(i).error('Stamp resize hit limit. Haloswitch quick break.')
-								out.edge_flux[i] = stuck
-								finish(i, 2)
-							elif attempts_left[i] == 0:
-								logger_of(i).error('Too many stamp resizes.')
-								finish(i, 2)
-							else:
-								still.append(i)
-							continue
-					# this attempt stands
-					if fl >> 8 == 6:
-						logger_of(i).error("No targets in mask.")
-					out.has_result[i] = True
-					out.group[i], out.pos[i] = gid, j
-					finish(i, int(res['status'][j]))
-		active = np.asarray(sorted(still), dtype='int64')
-	# the light curves of every round have arrived
-	marks = []
-	for g in streams:
-		ev = events.pop() if events else g.event()
-		g.record(ev)
-		marks.append((g, ev))
-	yield
-	for g, ev in marks:
-		try:
-			g.event_sync(ev)
-		except TessphotError as e:   # a copy of light curves failed: nothing that was extracted can be trusted
-			for i in np.flatnonzero(out.has_result):
-				out.has_result[i] = False
-				out.errors[int(i)] = out.errors.get(int(i), []) + ['ERROR: Device pass failed while the light curves were copied: ' + str(e)]
-				out.status[i] = 2
-	for g, batch, _work in pending:
-		batch.release_host()
-	return out
 
 
 #--------------------------------------------------------------------------------------------------

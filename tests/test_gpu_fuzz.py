@@ -51,13 +51,13 @@ def test_k2p2_fuzz_forty_scenes():
 	assert tot['targets'] >= 1000 and tot['n_razor'] == 0 and tot['n_exact'] + tot['n_error_agree'] == tot['targets'] and tot['n_exact'] > 0
 
 
-def test_frames_engine_fuzz_native_equals_python_rounds():
-	"""The native job engine of the batched drop-in entry against the Python rounds on eight further random regions (crowded
+def test_frames_engine_fuzz_native_equals_the_plugin():
+	"""The native job engine of the batched drop-in entry against the per-target plugin on eight further random regions (crowded
 	fields with bright stars near the frame limits: several resize rounds, size groups, quick breaks, minimum apertures, stamps
-	clipped by the region): every target equal in every field a caller can see."""
-	from photometry_amd import pipeline
+	clipped by the region): every target equal in every field a caller can see (test_gpu_resize._compare_to_plugin)."""
+	from photometry_amd import pipeline, tessphot_frames
 	from photometry_amd.device import Context
-	from test_gpu_resize import _compare_frames_results
+	from test_gpu_resize import _compare_to_plugin
 	ctx = Context(0)
 	tot = {'targets': 0, 'resized': 0, 'messages': 0, 'errors': 0, 'passes': 0}
 	import os
@@ -90,15 +90,15 @@ def test_frames_engine_fuzz_native_equals_python_rounds():
 		sel = rng.permutation(N)[:int(0.8 * N)]
 		tg = {'starid': cat['starid'][sel].copy(), 'tmag': tmag[sel], 'row': rows[sel] + row0, 'column': cols[sel] + col0}
 		stack = pipeline.FrameStack(ctx, fr, row0, col0)
-		py = pipeline.aperture_frames(ctx, stack, tg, cat, tstamp, q, engine='python')
-		nat = pipeline.aperture_frames(ctx, stack, tg, cat, tstamp, q, engine='native')
-		_compare_frames_results(py, nat)
+		batch = tessphot_frames(ctx, stack, tg, cat, tstamp, q)
+		_compare_to_plugin(batch, {k: np.moveaxis(v, 0, 2) for k, v in fr.items()}, row0, col0, tstamp, q, cat, tg, ctx)
+		nat = batch.frames
 		tot['targets'] += nat.n
 		tot['resized'] += int((nat.stamp_resizes > 0).sum())
 		tot['messages'] += len(nat.errors)
 		tot['errors'] += int((nat.status == 2).sum())
 		tot['passes'] += len(nat.groups)
-		del py, nat, stack
+		del batch, nat, stack
 	ctx.close()
 	print('frames engine fuzz:', tot)
 	assert tot['targets'] > 1500 and tot['resized'] > 50 and tot['messages'] > 20 and tot['passes'] > 40

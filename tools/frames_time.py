@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Diagnostic: where the time of the batched drop-in path goes -- tessphot_frames on a synthetic CCD region (N targets on an
-FR x FR x T frame stack resident in HBM): device passes against host-side bookkeeping."""
+FR x FR x T frame stack resident in HBM): device passes against host-side bookkeeping.  The engine's kernels run on the streams of
+its worker threads: profile them with rocprofv3 (profiles/frames_traffic.sh)."""
 import os, sys, time, cProfile, pstats, io
 import numpy as np
 if os.environ.get('NODE') is not None:   # experiment: run on the CPUs of one NUMA node (2 x 64 cores, SMT siblings at +128)
@@ -72,19 +73,6 @@ if NB:
 			pstats.Stats(prp, stream=sp).sort_stats('tottime').print_stats(22)
 			print(sp.getvalue()[:5000])
 		print(f'pipelined, {NB} batches of {N}, {fl} in flight: {dt * 1e3:.1f} ms = {NB * N / dt:.0f} targets/s; OK/WARNING {okc}', flush=True)
-if os.environ.get('KERNELS'):
-	# the device side of one call: per-kernel totals from the library's HIP events (every stream the call used)
-	allc = [ctx] + ctx.side_contexts(2)
-	for c in allc:
-		c.profile(True); c.profile_reset()
-	t0 = time.perf_counter()
-	out = tessphot_frames(ctx, stack, targets, cat, tstamp, quality)
-	dt = time.perf_counter() - t0
-	print(f'with the event profile on: {dt * 1e3:.2f} ms')
-	for ci, c in enumerate(allc):
-		for name, (cnt, ms) in sorted(c.profile_report().items(), key=lambda kv: -kv[1][1]):
-			print(f'  stream {ci}: {name:34s} {cnt:4d} launches {ms:8.3f} ms')
-		c.profile(False)
 s = io.StringIO()
 pstats.Stats(pr, stream=s).sort_stats('tottime').print_stats(28)
 print(s.getvalue()[:6500])

@@ -34,7 +34,7 @@ for _ in range(NB):
 	m = int(rng.choice([1, 7, 60, 300, 1200, 2500, 3000]))
 	sel = rng.permutation(N)[:m]
 	batches.append({k: np.asarray(v)[sel] for k, v in targets.items()})
-alone = [pipeline.aperture_frames(ctx, stack, b, cat, tstamp, quality, engine='native') for b in batches]
+alone = [pipeline.aperture_frames(ctx, stack, b, cat, tstamp, quality) for b in batches]
 for rep in range(int(os.environ.get('REPS', 3))):
 	piped = list(pipeline.aperture_frames_pipelined(ctx, stack, iter(batches), cat, tstamp, quality, in_flight=4))
 	assert len(piped) == NB
