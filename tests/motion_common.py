@@ -103,13 +103,16 @@ def warp_to_kernel(w, warpmode):
 	return np.array([w[0, 2], w[1, 2]])
 
 
-def ecc(template_prepared, image_prepared, warpmode, max_iter=10000, eps=1e-6):
+def ecc(template_prepared, image_prepared, warpmode, max_iter=10000, eps=1e-6, history=False):
 	"""
 	findTransformECC(template, input, eye(2, 3), mode, (EPS | COUNT, max_iter, eps), all-ones mask, gaussFiltSize=5).
 
 	Returns ``(kernel, rho, iterations, status)``: ``kernel`` as calc_kernel returns it (NaN when the frame failed), ``rho``
-	the last measured correlation, ``iterations`` the loop bodies run, ``status`` one of the frame states above.
+	the last measured correlation, ``iterations`` the loop bodies run, ``status`` one of the frame states above.  With
+	``history=True`` a fifth value follows: one dict per loop body run, ``rho``, ``N`` (the mask count), ``cond``
+	(``numpy.linalg.cond(H)``) and ``warp`` (the 2 x 3 warp after the update; as it was before, when the frame failed there).
 	"""
+	hist = []
 	P = N_PARAMS[warpmode]
 	T = blur5(template_prepared).astype('float64')
 	B = blur5(image_prepared)
@@ -153,6 +156,9 @@ def ecc(template_prepared, image_prepared, warpmode, max_iter=10000, eps=1e-6):
 		last_rho = rho
 		with np.errstate(invalid='ignore', divide='ignore'):
 			rho = corr / (img_norm * tmp_norm)
+		if history:
+			with np.errstate(all='ignore'):
+				hist.append({'rho': float(rho), 'N': int(N), 'cond': float(np.linalg.cond(H)) if np.all(np.isfinite(H)) else np.inf, 'warp': w.copy()})
 		if np.isnan(rho):
 			status = FAILED_NAN
 			break
@@ -183,24 +189,41 @@ def ecc(template_prepared, image_prepared, warpmode, max_iter=10000, eps=1e-6):
 			w[1, 1] += dp[3]
 			w[0, 2] += dp[4]
 			w[1, 2] += dp[5]
+		if history:
+			hist[-1]['warp'] = w.copy()
 		i += 1
 	iterations = i - 1 if status == ACTIVE else i
 	if status == ACTIVE:
 		status = CONVERGED if abs(rho - last_rho) < eps else CAP_REACHED
 	if status in (FAILED_NAN, FAILED_LAMBDA):
-		return np.full(P, np.nan), float(rho), int(iterations), status
-	return warp_to_kernel(w, warpmode), float(rho), int(iterations), status
+		out = np.full(P, np.nan), float(rho), int(iterations), status
+	else:
+		out = warp_to_kernel(w, warpmode), float(rho), int(iterations), status
+	return out + (hist,) if history else out
 
 
-def star_field(R, C, shift=(0.0, 0.0), n_stars=60, sigma=1.2, seed=0, background=100.0):
+def ecc_step(template_prepared, image_prepared, warpmode, history=False):
+	"""Exactly one iteration of :func:`ecc` from the identity warp: what the device is held to pixel by pixel (nothing averages away)."""
+	return ecc(template_prepared, image_prepared, warpmode, max_iter=1, history=history)
+
+
+def star_field(R, C, shift=(0.0, 0.0), n_stars=60, sigma=1.2, seed=0, background=100.0, warp=None, margin=8):
 	"""
 	A noise-free field of pixel-integrated Gaussian stars (``simulate._gauss_int``), every star moved by ``shift`` =
 	(column, row): the exact image of the reference field at that sub-pixel offset, no interpolation involved.
+
+	With ``warp`` (2 x 3) every star centre ``p`` = (column, row) of the reference field is drawn at ``warp @ [column, row, 1]``
+	(then moved by ``shift``) -- the convention of the ECC warp, ``dst(x, y) = src(W [x y 1])`` -- so the true kernel of the pair
+	(field, warped field) is ``warp_to_kernel(warp, mode)``.  The stars keep their shape: a warp with scale draws unscaled stars.
+	``margin``: the reference centres are drawn from ``[margin, R - margin] x [margin, C - margin]``.
 	"""
 	from photometry_amd.simulate import _gauss_int
 	rng = np.random.default_rng(seed)
-	rows = rng.uniform(8, R - 8, n_stars)
-	cols = rng.uniform(8, C - 8, n_stars)
+	rows = rng.uniform(margin, R - margin, n_stars)
+	cols = rng.uniform(margin, C - margin, n_stars)
+	if warp is not None:
+		warp = np.asarray(warp, dtype='float64')
+		rows, cols = (warp[1, 0] * cols + warp[1, 1] * rows + warp[1, 2], warp[0, 0] * cols + warp[0, 1] * rows + warp[0, 2])
 	flux = 10 ** rng.uniform(2.5, 5.0, n_stars)
 	img = np.full((R, C), background)
 	r = np.arange(R, dtype='float64')
@@ -210,3 +233,178 @@ def star_field(R, C, shift=(0.0, 0.0), n_stars=60, sigma=1.2, seed=0, background
 		gc = _gauss_int(c, cols[k] + shift[0], sigma)
 		img += flux[k] * np.outer(gr, gc)
 	return img.astype('float32')
+
+
+# ---- the cases the device is held to off the tile grid (tests/test_gpu_motion.py), and their input conditions -------------------------
+# One table for the device tests and for tests/test_motion_host.py, which asserts the conditions below on the restatement alone, so
+# that a case that drifts out of its condition fails on the CPU before any device run.
+
+MODES = ('translation', 'euclidian', 'affine')
+#: prepare / blur tile 16 x 64, iteration tile 32 x 128: none of these but (16, 64) sits on either grid
+RAGGED_SHAPES = [(131, 257), (200, 333), (33, 130), (17, 500), (97, 65), (15, 63), (16, 64), (17, 65), (3, 3), (3, 200), (200, 3), (5, 4)]
+ONE_STEP_SHAPES = [s for s in RAGGED_SHAPES if min(s) >= 15]
+TINY_SHAPES = [(3, 3), (3, 200), (200, 3), (5, 4), (7, 7)]
+CONVERGED_SHAPES = [(131, 257), (200, 333), (97, 65), (33, 130)]
+CAP_SHAPE = (131, 257)
+CAPS = (0, 1, 3, 5, 13, 37)
+MIXED_CAP = 6
+PAD_SHAPE, PAD = (33, 130), 37
+
+#: the device's rho is held to rtol 1e-9 of the restatement's, so |rho - last_rho| differs by at most about 2e-9 between the two:
+#: equal iteration counts are a fair demand only when every value the loop test sees is ten times that away from eps
+RHO_MARGIN = 2e-8
+#: one-step parity on tiny frames: beyond these the device's zero-pivot rule and numpy.linalg.inv legitimately part ways
+TINY_MAX_COND = 1e8
+#: warps that push a band of pixels out of the frame: the mask count must fall to this share of the frame at the latest
+MASK_SHARE = 0.98
+#: iterations (eps = 0) after which the large warps are compared a second time: from the identity warp the first iteration's mask
+#: is the whole frame whatever the pair, so only a later iteration can hold the device to the warped-mask rule
+MASK_STEPS = 4
+
+
+def shift_warp(dx, dy):
+	return np.array([[1.0, 0.0, dx], [0.0, 1.0, dy]])
+
+
+def rot_warp(theta, dx=0.0, dy=0.0):
+	"""Rotation by ``theta`` about the origin (pixel (0, 0)), then the shift."""
+	c, s = np.cos(theta), np.sin(theta)
+	return np.array([[c, -s, dx], [s, c, dy]])
+
+
+SMALL_SHIFTS = [shift_warp(0.37, -0.21), shift_warp(-0.23, 0.41)]
+LARGE_SHIFTS = [shift_warp(3.7, -2.6), shift_warp(-6.1, 7.2)]
+AFFINE_WARP = np.array([[1.002, 0.001, 0.25], [-0.0015, 0.998, -0.3]])
+
+
+def field_margin(R, C):
+	"""How far the reference star centres stay from the border: 8 px as everywhere else, less where the frame has no room for it."""
+	m = min(R, C)
+	return 8 if m >= 33 else (4 if m >= 12 else m / 2 - 0.4)
+
+
+def case_field(R, C, warp=None, seed=11):
+	"""The star field of a case: ``max(12, R * C // 600)`` stars (one smooth star on a frame under 12 pixels a side)."""
+	n = 1 if min(R, C) < 12 else max(12, R * C // 600)
+	return star_field(R, C, n_stars=n, seed=seed, warp=warp, margin=field_margin(R, C))
+
+
+def nan_positions(R, C):
+	"""The NaN pixels of the ragged prepare test: the four corners, one in the last row, one in the last column, and (r0 - 1, c0 - 1),
+	(r0, c0) at the origin of the last (partly filled) prepare / blur tile."""
+	r0, c0 = (R - 1) // 16 * 16, (C - 1) // 64 * 64
+	pos = [(0, 0), (0, C - 1), (R - 1, 0), (R - 1, C - 1), (R - 1, C // 2), (R // 2, C - 1), (r0, c0)]
+	if r0 > 0 and c0 > 0:
+		pos.append((r0 - 1, c0 - 1))
+	return pos
+
+
+def ragged_stack(R, C):
+	"""(4, R, C) float32: a star field with Gaussian noise, another with NaN pixels at :func:`nan_positions`, an all-NaN frame and a
+	constant frame."""
+	rng = np.random.default_rng(1000 * R + C)
+	out = np.empty((4, R, C), dtype='float32')
+	out[0] = case_field(R, C) + rng.normal(0, 3.0, (R, C)).astype('float32')
+	out[1] = case_field(R, C, warp=shift_warp(0.3, -0.2)) + rng.normal(0, 3.0, (R, C)).astype('float32')
+	for r, c in nan_positions(R, C):
+		out[1, r, c] = np.nan
+	out[2] = np.nan
+	out[3] = 42.0
+	return out
+
+
+def one_step_warps(R, C):
+	"""``[(name, warp, leaves_frame)]`` of the one-iteration parity on (R, C); ``leaves_frame``: the pair is compared again after
+	MASK_STEPS iterations, where its mask count must be at most MASK_SHARE of the frame."""
+	# (-6.1, 7.2) is half of a frame of 15 - 17 rows: one step from it is as well defined as any, four are not (the restatement fails
+	# or leaves a tenth of the frame in the mask), so the second comparison takes the frames of 33 pixels a side and more
+	w = [('ref', np.eye(2, 3), False), ('s0', SMALL_SHIFTS[0], False), ('s1', SMALL_SHIFTS[1], False), ('l0', LARGE_SHIFTS[0], True),
+		('l1', LARGE_SHIFTS[1], min(R, C) >= 33)]
+	if (R, C) == (200, 333):
+		w.append(('rot', rot_warp(0.04), True))
+	return w
+
+
+def one_step_prepared(R, C):
+	"""(names, flags, prepared (n, R, C) float32): frame 0 is the template."""
+	ws = one_step_warps(R, C)
+	return [n for n, _, _ in ws], [f for _, _, f in ws], np.stack([prepare_flux(case_field(R, C, warp=w)) for _, w, _ in ws])
+
+
+TINY_SHIFT = shift_warp(0.12, -0.08)
+#: the tiny frames and modes that meet the conditioning condition (asserted in tests/test_motion_host.py): all but the affine mode
+#: on a frame three pixels wide, whose Hessian is singular to rounding (cond 3.5e17 on (3, 3), where N = 9 < 2 P as well, 1.9e25 on
+#: (3, 200), 6.8e20 on (200, 3): the REFLECT_101 gradient across three pixels is zero but on the middle line, so the columns gy * y
+#: and gy, or gx * x and gx, of the Jacobian coincide) -- tests/test_motion_host.py asserts that too, so the exclusion cannot outlive its reason
+TINY_CASES = [(s, m) for s in TINY_SHAPES for m in MODES if not (m == 'affine' and min(s) == 3)]
+TINY_SINGULAR = [(s, 'affine') for s in TINY_SHAPES if min(s) == 3]
+
+
+def tiny_prepared(R, C):
+	"""(2, R, C) prepared: one smooth star and the same star shifted by about (0.12, -0.08)."""
+	return np.stack([prepare_flux(case_field(R, C, seed=3)), prepare_flux(case_field(R, C, warp=TINY_SHIFT, seed=3))])
+
+
+def converged_warps(shape, mode):
+	"""
+	``[(name, warp, known_answer)]`` of the converged parity on ``shape``: frame 0 of the stack is the reference field.
+
+	``known_answer``: the restatement itself recovers the true kernel within the suite's known-answer tolerance (0.01), so the device
+	is asked the same.  That holds for the translations (the (-6.1, 7.2) px shift on the two larger frames only: 0.0099 and 0.0103 on
+	97 x 65 and 33 x 130, where it moves stars up to the border) and for the euclidian mode on 200 x 333 only (0.0091 - 0.0117 on the
+	smaller frames); an affine warp with scale has no known answer, the generator does not rescale the stars.
+	"""
+	big = shape == (200, 333)
+	if mode == 'translation':
+		return [('s0', SMALL_SHIFTS[0], True), ('s1', SMALL_SHIFTS[1], True), ('l0', LARGE_SHIFTS[0], True),
+			('l1', LARGE_SHIFTS[1], shape in ((131, 257), (200, 333)))]
+	if mode == 'euclidian':
+		return [('r004', rot_warp(0.004, 0.3, -0.4), big), ('r01', rot_warp(0.01, -0.3, 0.2), big), ('r04', rot_warp(0.04, 0.5, -0.7), big)]
+	return [('scale', AFFINE_WARP, False), ('r02', rot_warp(0.02, 0.5, -0.7), False), ('s0', SMALL_SHIFTS[0], False)]
+
+
+def converged_stack(shape, mode):
+	"""(names, warps, known flags, frames (1 + n, R, C) float32), frame 0 the reference."""
+	ws = converged_warps(shape, mode)
+	frames = np.stack([case_field(*shape)] + [case_field(*shape, warp=w) for _, w, _ in ws])
+	return ['ref'] + [n for n, _, _ in ws], [np.eye(2, 3)] + [w for _, w, _ in ws], [True] + [k for _, _, k in ws], frames
+
+
+REF_MIDDLE = {'shape': (131, 257), 'mode': 'translation', 'ref_frame': 2,
+	'shifts': [(0.37, -0.21), (-0.4, 0.15), (0.0, 0.0), (0.22, 0.33), (-0.31, -0.12)]}
+
+
+def ref_middle_stack():
+	R, C = REF_MIDDLE['shape']
+	return np.stack([case_field(R, C, warp=shift_warp(*s)) for s in REF_MIDDLE['shifts']])
+
+
+def cap_stack():
+	"""Nine frames of CAP_SHAPE, none of which fails in the restatement: the reference, shifts small and large, rotations, the affine
+	matrix."""
+	R, C = CAP_SHAPE
+	ws = [np.eye(2, 3), SMALL_SHIFTS[0], SMALL_SHIFTS[1], shift_warp(0.11, 0.48), LARGE_SHIFTS[0], LARGE_SHIFTS[1],
+		rot_warp(0.004, 0.3, -0.4), rot_warp(0.01, -0.3, 0.2), AFFINE_WARP]
+	return np.stack([case_field(R, C, warp=w) for w in ws])
+
+
+def mixed_stack():
+	"""The reference itself, a small shift, a large shift (more iterations), a constant frame and an all-NaN frame (both fail)."""
+	R, C = CAP_SHAPE
+	frames = np.stack([case_field(R, C), case_field(R, C, warp=SMALL_SHIFTS[0]), case_field(R, C, warp=LARGE_SHIFTS[0]), case_field(R, C),
+		case_field(R, C)])
+	frames[3] = 42.0
+	frames[4] = np.nan
+	return frames
+
+
+def loop_test_values(hist, eps):
+	"""Every |rho - last_rho| the loop test of :func:`ecc` has seen after its first pass (the first compares -1 with -eps)."""
+	rho = np.array([-eps, -1.0] + [h['rho'] for h in hist])
+	return np.abs(np.diff(rho))[1:]
+
+
+def margin_ok(hist, eps):
+	"""The iteration-count margin: no loop-test value within RHO_MARGIN of ``eps``."""
+	d = loop_test_values(hist, eps)
+	return bool(np.all(np.abs(d - eps) >= RHO_MARGIN))
