@@ -44,7 +44,8 @@ def do_photometry(images, psf, catalog, target_starid, positions, stamp, target_
 			catalog star -- what ``catalog_attime`` returns (BasePhotometry.py:1224-1258);
 			the WCS/jitter interpolation itself is host geometry and an engine *input*.
 
-	Returns dict(status, flux, flux_err, contamination, fluxes_mean, A_last, nstars, staridx, errors).
+	Returns dict(status, flux, flux_err, contamination, fluxes_mean, A_last, nstars, staridx, errors, fluxes_all);
+	``fluxes_all`` is ``(T, nstars)``: the solution ``fluxes`` of every cadence as the loop found it (NaN where there was none).
 	"""
 	T = images.shape[2]
 	indx, staridx = select_stars(catalog, target_starid)
@@ -52,6 +53,7 @@ def do_photometry(images, psf, catalog, target_starid, positions, stamp, target_
 	fluxes_sum = np.zeros(nstars, dtype='float64')
 	flux = np.zeros(T, dtype='float64')
 	flux_err = np.zeros(T, dtype='float64')
+	fluxes_all = np.full((T, nstars), np.nan, dtype='float64')
 	mini_aperture = minimum_aperture(stamp, target_pos_row, target_pos_column, aperture)
 	res = {'errors': [], 'nstars': nstars, 'staridx': int(staridx), 'indx': indx}
 	A = None
@@ -85,9 +87,11 @@ def do_photometry(images, psf, catalog, target_starid, positions, stamp, target_
 			flux[k] = target_flux
 			flux_err[k] = np.nan
 			fluxes_sum += fluxes
+			fluxes_all[k] = fluxes
 
 	res['flux'] = flux
 	res['flux_err'] = flux_err
+	res['fluxes_all'] = fluxes_all
 	res['mini_aperture'] = mini_aperture
 	if allnan(flux):
 		res['errors'].append('All target flux values are NaN.')
