@@ -719,6 +719,43 @@ int tp_halo_tvmin(tp_ctx* ctx, int32_t n_problems, const int64_t* h_p_offset, co
 int tp_halo_objective(tp_ctx* ctx, int32_t n_problems, const int64_t* h_p_offset, const int32_t* h_npix, const int32_t* h_ncad,
 	const float* d_P, const uint8_t* d_fit, const double* d_theta, double* d_f, double* d_grad);
 
+/* ---- Halo photometry of a batch of targets straight from a region's frame stack (the batched entry) --------------------------
+ * The problems of halo_photometry.py:160-196 (one per segment of every target; the definition is tests/halo_common.py::problems)
+ * are built on the device from the image-major stack d_images float32 [n_frames][frame_rows][frame_cols] (contiguous) that covers
+ * the CCD rows / columns from row0 / col0.  h_stamps: HOST int32 [n_targets][4] (row1, row2, col1, col2 in CCD coordinates), all
+ * of height x width (<= 4096 pixels) and inside the stack.  h_seg: HOST int32 [n_frames], the segment of every cadence (-1: no
+ * finite time), n_seg = its largest value + 1 (1 .. 64).  Problem q = target * n_seg + segment.
+ * tp_halo_select_stack: d_mask uint8 [n_targets][height * width] the pixel mask (:118-120), h_quality HOST int32 [n_frames]; a
+ *   cadence is fitted iff quality & bitmask == 0.  A mask pixel is dropped iff nanmedian (float64) of its float32 values over the
+ *   segment's fitted cadences is < minflux (NaN medians keep it); a cadence of the segment is kept iff every kept pixel is finite
+ *   there (all of them when no pixel is kept).  Out: d_pix int32 [n_prob][height * width] (flat stamp indices, ascending, the
+ *   first d_npix[q]), d_cad int32 [n_prob][n_frames] (ascending, the first d_ncad[q]), d_fit uint8 [n_prob][n_frames] (the fit flag
+ *   of every kept cadence), d_cadpos int32 [n_targets][n_frames] (position of the cadence in its problem's list, -1: in none),
+ *   d_npix / d_ncad int32 [n_prob].
+ * tp_halo_gather_stack: for the n_run problems h_index (HOST, indices q) with their counts h_npix / h_ncad (HOST, as read back from
+ *   tp_halo_select_stack; 1 <= npix) and offsets h_p_offset (HOST, multiples of 4): d_P in tp_halo_tvmin's layout (zero padded rows)
+ *   and d_fit_out uint8 [sum ncad], problem r's cadences after those of problems 0 .. r-1.
+ * tp_halo_outputs_stack (:197-219): from d_w / d_l / d_status of tp_halo_tvmin over the same n_run problems and d_images_err (the
+ *   region's error stack): d_median float64 [n_prob] numpy's median of l over the fitted cadences (NaN for a problem not run);
+ *   d_weightmap float64 [n_prob][height * width] = w / median at the kept pixels, zero elsewhere; d_corr float64 [n_targets][n_frames]
+ *   = l / median at the problem's cadences, NaN elsewhere and for a degenerate problem; d_flux = d_corr * h_normfactor[target];
+ *   d_flux_err = |normfactor| sqrt(nansum(weightmap^2 err^2)) over the stamp with the weight map of the cadence's segment, 0 for a
+ *   cadence without one.  Every sum has a fixed order and nothing uses float atomics: results are bit-reproducible and a target
+ *   gives the same bits alone as inside a batch.                                                                              */
+int tp_halo_select_stack(tp_ctx* ctx, const float* d_images, int32_t n_frames, int32_t frame_rows, int32_t frame_cols, int32_t row0,
+	int32_t col0, int32_t n_targets, const int32_t* h_stamps, int32_t height, int32_t width, const uint8_t* d_mask, int32_t n_seg,
+	const int32_t* h_seg, const int32_t* h_quality, int32_t bitmask, double minflux, int32_t* d_pix, int32_t* d_cad, uint8_t* d_fit,
+	int32_t* d_cadpos, int32_t* d_npix, int32_t* d_ncad);
+int tp_halo_gather_stack(tp_ctx* ctx, const float* d_images, int32_t n_frames, int32_t frame_rows, int32_t frame_cols, int32_t row0,
+	int32_t col0, int32_t n_targets, const int32_t* h_stamps, int32_t height, int32_t width, int32_t n_seg, const int32_t* d_pix,
+	const int32_t* d_cad, const uint8_t* d_fit, int32_t n_run, const int32_t* h_index, const int64_t* h_p_offset, const int32_t* h_npix,
+	const int32_t* h_ncad, float* d_P, uint8_t* d_fit_out);
+int tp_halo_outputs_stack(tp_ctx* ctx, const float* d_images_err, int32_t n_frames, int32_t frame_rows, int32_t frame_cols, int32_t row0,
+	int32_t col0, int32_t n_targets, const int32_t* h_stamps, int32_t height, int32_t width, int32_t n_seg, const int32_t* h_seg,
+	const int32_t* d_pix, const int32_t* d_cadpos, int32_t n_run, const int32_t* h_index, const int32_t* h_npix, const int32_t* h_ncad,
+	const uint8_t* d_fit, const double* d_w, const double* d_l, const int32_t* d_status, const double* h_normfactor, double* d_median,
+	double* d_corr, double* d_flux, double* d_flux_err, double* d_weightmap);
+
 /* ---- TAN-SIP world coordinate systems (astropy.wcs as ImageMovementKernel('wcs') uses it, image_motion.py:113-421) ---------
  * One frame's WCS is a block of TP_WCS_PARAMS float64 values packed by photometry_amd/wcs.py: [0:9] the native -> celestial
  * rotation (row-major), [9:11] CRPIX, [11:15] CD, [15:19] CD^-1, [19] A_ORDER, [20] B_ORDER, [21] 1 with SIP, [24:124] A_p_q at

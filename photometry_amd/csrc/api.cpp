@@ -54,6 +54,12 @@ static const char* const kKernelNames[TPK_COUNT] = {
 	"tp_halo_backward_kernel",
 	"tp_halo_finish_kernel",
 	"tp_halo_output_kernel",
+	"tp_halo_select_stat_kernel",
+	"tp_halo_select_cad_kernel",
+	"tp_halo_select_compact_kernel",
+	"tp_halo_gather_kernel",
+	"tp_halo_norm_kernel",
+	"tp_halo_lightcurve_kernel",
 	"tp_wcs_pix2world_kernel",
 	"tp_wcs_radec_kernel",
 	"tp_wcs_world2pix_kernel",

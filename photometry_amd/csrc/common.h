@@ -52,6 +52,12 @@ enum tp_kernel_id {
 	TPK_HALO_BACKWARD,
 	TPK_HALO_FINISH,
 	TPK_HALO_OUTPUT,
+	TPK_HALO_SELECT_STAT,
+	TPK_HALO_SELECT_CAD,
+	TPK_HALO_SELECT_COMPACT,
+	TPK_HALO_GATHER,
+	TPK_HALO_NORM,
+	TPK_HALO_LIGHTCURVE,
 	TPK_WCS_PIX2WORLD,
 	TPK_WCS_RADEC,
 	TPK_WCS_WORLD2PIX,

@@ -769,3 +769,537 @@ extern "C" int tp_halo_objective(tp_ctx* ctx, int32_t n_problems, const int64_t*
 		d_grad);
 	TP_API_END(ctx)
 }
+
+// ===============================================================================================================================
+// The frames path: the problems of a batch of targets built on the device straight from a region's image stack
+// (halo_photometry.py:118-123 the pixel mask handed in, :160-176 the segments, halophot's minflux cut and finite-cadence rule as
+// restated in tests/halo_common.py::problems), and the outputs of :197-219 (normalised light curve, weight maps, flux error).
+//
+// The stack is image-major, float32 [T][frame_rows][frame_cols]; a stamp (r1, r2, c1, c2) in CCD coordinates holds the pixels
+// [r1 - row0, r2 - row0) x [c1 - col0, c2 - col0) of every frame.  Problem q = target * n_seg + segment.
+//   select_stat    (cadence tile, target): per mask pixel over the tile's FITTED cadences the count of non-NaN values n, the count
+//                  c of values < minflux, a = max{x < minflux}, b = min{x >= minflux}; tiles combine through integer atomics and
+//                  max / min atomics on the order-preserving key of the float32 value -- all order-independent;
+//   select_cad     (cadence tile, target): the pixel decision from (n, c, a, b) -- numpy's nanmedian(float64) < minflux without a
+//                  sort, see drop_pixel -- then per cadence of the tile whether every kept pixel is finite;
+//   select_compact (one block per problem): the kept pixels and cadences in ascending order, the fit flags, the counts, and the
+//                  position of every cadence of the target in its problem's list (-1: not part of one); a segment without any
+//                  cadence keeps every mask pixel (no median: NaN), as the restatement does;
+//   gather         (row tile, problem): P in tp_halo_tvmin's layout and the concatenated fit bytes;
+//   norm           (one block per problem): numpy's median of l over the fitted cadences (radix select over the 64-bit key, 256-bin
+//                  integer histogram in LDS per pass) and the weight map w / median placed into the stamp;
+//   lightcurve     (4 cadences per block, one wave each; target): corr_flux, flux, and flux_err as a fixed-order sum over the stamp.
+// No float atomics anywhere: two runs give the same bits, and a target gives the same bits alone as inside a batch.
+namespace {
+
+constexpr int kSelTile = 64;          // cadences per select block
+constexpr int kMaxStamp = 4096;       // pixels per stamp (a Halo stamp is 22 x 22)
+
+struct StackGeom {
+	int32_t n_frames, frame_rows, frame_cols, row0, col0, height, width, n_seg, n_targets;
+};
+
+__device__ inline uint32_t fkey(float v) {
+	const uint32_t u = __float_as_uint(v);
+	return (u >> 31) ? ~u : (u | 0x80000000u);
+}
+__device__ inline float from_fkey(uint32_t k) {
+	return __uint_as_float((k >> 31) ? (k & 0x7fffffffu) : ~k);
+}
+
+// nanmedian(x.astype(float64)) < minflux from the counts: n non-NaN values, c of them < minflux, a the largest of those (key),
+// b the smallest of the others (key).  Odd n: the middle value is below iff c >= (n + 1) / 2.  Even n: both middle values below
+// (c >= n / 2 + 1), neither (c < n / 2), or a and b themselves: numpy's (a + b) / 2 in float64.  No value: NaN, not below.
+__device__ inline bool drop_pixel(int32_t n, int32_t c, uint32_t akey, uint32_t bkey, double minflux) {
+	if (n <= 0) return false;
+	if (n & 1) return c >= (n + 1) / 2;
+	if (c >= n / 2 + 1) return true;
+	if (c < n / 2) return false;
+	const double m = ((double)from_fkey(akey) + (double)from_fkey(bkey)) / 2.0;
+	return m < minflux;
+}
+
+// image offset of stamp pixel p of a target inside one frame
+__device__ inline int64_t stamp_offset(const StackGeom& g, const int32_t* st, int p) {
+	return (int64_t)(st[0] - g.row0 + p / g.width) * g.frame_cols + (st[2] - g.col0 + p % g.width);
+}
+
+// tiles: int32 [n_tiles][3] = segment, first and one-past-last entry of cadlist; stats: int32 [4][n_prob * HW] = n, c, akey, bkey
+__global__ __launch_bounds__(kThreads) void tp_halo_select_stat_kernel(StackGeom g, const float* __restrict__ images,
+	const int32_t* __restrict__ stamps, const uint8_t* __restrict__ mask, const int32_t* __restrict__ tiles,
+	const int32_t* __restrict__ cadlist, const uint8_t* __restrict__ fitlist, double minflux, int32_t* stats)
+{
+	const int i = blockIdx.y;
+	const int k = tiles[3 * blockIdx.x], j0 = tiles[3 * blockIdx.x + 1], j1 = tiles[3 * blockIdx.x + 2];
+	const int HW = g.height * g.width;
+	const int64_t frame = (int64_t)g.frame_rows * g.frame_cols;
+	const int64_t nstat = (int64_t)g.n_targets * g.n_seg * HW;
+	const int64_t q = (int64_t)i * g.n_seg + k;
+	const int32_t* st = stamps + 4 * i;
+	for (int p = threadIdx.x; p < HW; p += kThreads) {
+		if (!mask[(int64_t)i * HW + p]) continue;
+		const int64_t off = stamp_offset(g, st, p);
+		int32_t n = 0, c = 0;
+		uint32_t ak = 0u, bk = 0xffffffffu;
+		for (int j = j0; j < j1; j++) {
+			if (!fitlist[j]) continue;
+			const float x = images[(int64_t)cadlist[j] * frame + off];
+			if (x != x) continue;
+			n++;
+			const uint32_t key = fkey(x);
+			if ((double)x < minflux) { c++; ak = max(ak, key); }
+			else bk = min(bk, key);
+		}
+		const int64_t s = q * HW + p;
+		if (n) atomicAdd(&stats[s], n);
+		if (c) atomicAdd(&stats[nstat + s], c);
+		if (ak != 0u) atomicMax(reinterpret_cast<uint32_t*>(stats) + 2 * nstat + s, ak);
+		if (bk != 0xffffffffu) atomicMin(reinterpret_cast<uint32_t*>(stats) + 3 * nstat + s, bk);
+	}
+}
+
+// pixkeep uint8 [n_prob][HW] (written by the first tile of every segment), cadkeep uint8 [n_prob][T] indexed by the position in the
+// segment's part of cadlist (j - seg_first)
+__global__ __launch_bounds__(kThreads) void tp_halo_select_cad_kernel(StackGeom g, const float* __restrict__ images,
+	const int32_t* __restrict__ stamps, const uint8_t* __restrict__ mask, const int32_t* __restrict__ tiles,
+	const int32_t* __restrict__ cadlist, const int32_t* __restrict__ seg_off, double minflux, const int32_t* __restrict__ stats,
+	uint8_t* pixkeep, uint8_t* cadkeep)
+{
+	__shared__ uint8_t keep[kMaxStamp];
+	__shared__ int32_t bad[kSelTile];
+	const int i = blockIdx.y;
+	const int k = tiles[3 * blockIdx.x], j0 = tiles[3 * blockIdx.x + 1], j1 = tiles[3 * blockIdx.x + 2];
+	const int HW = g.height * g.width;
+	const int64_t frame = (int64_t)g.frame_rows * g.frame_cols;
+	const int64_t nstat = (int64_t)g.n_targets * g.n_seg * HW;
+	const int64_t q = (int64_t)i * g.n_seg + k;
+	const int32_t* st = stamps + 4 * i;
+	const int first = seg_off[k];
+	for (int p = threadIdx.x; p < HW; p += kThreads) {
+		const int64_t s = q * HW + p;
+		const bool kp = mask[(int64_t)i * HW + p] != 0 &&
+			!drop_pixel(stats[s], stats[nstat + s], (uint32_t)stats[2 * nstat + s], (uint32_t)stats[3 * nstat + s], minflux);
+		keep[p] = kp;
+		if (j0 == first) pixkeep[s] = kp;
+	}
+	if (threadIdx.x < kSelTile) bad[threadIdx.x] = 0;
+	__syncthreads();
+	for (int p = threadIdx.x; p < HW; p += kThreads) {
+		if (!keep[p]) continue;
+		const int64_t off = stamp_offset(g, st, p);
+		for (int j = j0; j < j1; j++) {
+			const float x = images[(int64_t)cadlist[j] * frame + off];
+			if (!(fabsf(x) <= 3.402823466e+38f)) bad[j - j0] = 1;   // NaN or infinite (every writer stores the same value)
+		}
+	}
+	__syncthreads();
+	for (int j = j0 + threadIdx.x; j < j1; j += kThreads) cadkeep[q * g.n_frames + (j - first)] = bad[j - j0] ? 0 : 1;
+}
+
+// ascending list of the set flags: out[rank] = value(index); returns the count (every thread)
+template <class F> __device__ int compact_block(const uint8_t* flags, int n, int* wcount, F&& emit) {
+	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+	int base = 0;
+	for (int c0 = 0; c0 < n; c0 += kThreads) {
+		const int t = c0 + threadIdx.x;
+		const bool flag = t < n && flags[t] != 0;
+		const unsigned long long b = __ballot(flag);
+		if (lane == 0) wcount[wave] = __popcll(b);
+		__syncthreads();
+		int before = __popcll(b & ((1ull << lane) - 1ull)), total = 0;
+		for (int k = 0; k < kThreads / 64; k++) {
+			if (k < wave) before += wcount[k];
+			total += wcount[k];
+		}
+		emit(t, flag, base + before);
+		base += total;
+		__syncthreads();
+	}
+	return base;
+}
+
+// pix int32 [n_prob][HW], cad int32 [n_prob][T], fit uint8 [n_prob][T], cadpos int32 [n_targets][T] (preset to -1)
+__global__ __launch_bounds__(kThreads) void tp_halo_select_compact_kernel(StackGeom g, const int32_t* __restrict__ cadlist,
+	const uint8_t* __restrict__ fitlist, const int32_t* __restrict__ seg_off, const uint8_t* __restrict__ mask,
+	const uint8_t* __restrict__ pixkeep, const uint8_t* __restrict__ cadkeep, int32_t* pix, int32_t* cad, uint8_t* fit, int32_t* cadpos,
+	int32_t* npix, int32_t* ncad)
+{
+	__shared__ int wcount[kThreads / 64];
+	const int64_t q = blockIdx.x;
+	const int i = (int)(q / g.n_seg), k = (int)(q % g.n_seg);
+	const int HW = g.height * g.width;
+	const int first = seg_off[k], count = seg_off[k + 1] - first;
+	int32_t* mypix = pix + q * HW;
+	// (a segment without a cadence has no tile that decided its pixels: no median, so every mask pixel is kept)
+	const uint8_t* keep = count > 0 ? pixkeep + q * HW : mask + (int64_t)i * HW;
+	const int np = compact_block(keep, HW, wcount, [&](int t, bool flag, int rank) { if (flag) mypix[rank] = t; });
+	int32_t* mycad = cad + q * g.n_frames;
+	uint8_t* myfit = fit + q * g.n_frames;
+	int32_t* mypos = cadpos + (int64_t)i * g.n_frames;
+	const int nc = compact_block(cadkeep + q * g.n_frames, count, wcount, [&](int t, bool flag, int rank) {
+		if (flag) {
+			const int c = cadlist[first + t];
+			mycad[rank] = c;
+			myfit[rank] = fitlist[first + t];
+			mypos[c] = rank;
+		}
+	});
+	if (threadIdx.x == 0) {
+		npix[q] = np;
+		ncad[q] = nc;
+	}
+}
+
+struct GatherProb {
+	int64_t p_off, c_off;
+	int32_t q, npix, ncad, pitch;
+};
+
+constexpr int kGatherRows = 8;
+
+__global__ __launch_bounds__(kThreads) void tp_halo_gather_kernel(StackGeom g, const float* __restrict__ images,
+	const int32_t* __restrict__ stamps, const GatherProb* __restrict__ probs, const int32_t* __restrict__ pix,
+	const int32_t* __restrict__ cad, const uint8_t* __restrict__ fit, float* P, uint8_t* fit_out)
+{
+	const GatherProb pr = probs[blockIdx.y];
+	const int r0 = blockIdx.x * kGatherRows;
+	if (r0 >= pr.ncad) return;
+	const int r1 = min(r0 + kGatherRows, pr.ncad);
+	const int HW = g.height * g.width;
+	const int64_t frame = (int64_t)g.frame_rows * g.frame_cols;
+	const int32_t* st = stamps + 4 * (pr.q / g.n_seg);
+	const int32_t* mypix = pix + (int64_t)pr.q * HW;
+	const int32_t* mycad = cad + (int64_t)pr.q * g.n_frames;
+	for (int p = threadIdx.x; p < pr.pitch; p += kThreads) {
+		const bool real = p < pr.npix;
+		const int64_t off = real ? stamp_offset(g, st, mypix[p]) : 0;
+		for (int r = r0; r < r1; r++)
+			P[pr.p_off + (int64_t)r * pr.pitch + p] = real ? images[(int64_t)mycad[r] * frame + off] : 0.0f;
+	}
+	if (threadIdx.x < r1 - r0) fit_out[pr.c_off + r0 + threadIdx.x] = fit[(int64_t)pr.q * g.n_frames + r0 + threadIdx.x];
+}
+
+struct NormProb {
+	int64_t c_off, w_off;
+	int32_t q, npix, ncad, pad;
+};
+
+// the key of rank `rank` (0-based, ascending) among the fitted l of one problem: eight passes of eight bits, most significant first
+__device__ uint64_t select_rank(const double* l, const uint8_t* fit, int ncad, int rank, int* hist, uint64_t* found) {
+	uint64_t prefix = 0;
+	for (int shift = 56; shift >= 0; shift -= 8) {
+		for (int b = threadIdx.x; b < 256; b += kThreads) hist[b] = 0;
+		__syncthreads();
+		for (int t = threadIdx.x; t < ncad; t += kThreads) {
+			if (!fit[t]) continue;
+			const uint64_t key = okey(l[t]);
+			if (shift == 56 || (key >> (shift + 8)) == (prefix >> (shift + 8))) atomicAdd(&hist[(key >> shift) & 255], 1);
+		}
+		__syncthreads();
+		if (threadIdx.x == 0) {
+			int b = 0, r = rank;
+			while (b < 255 && r >= hist[b]) { r -= hist[b]; b++; }
+			found[0] = prefix | ((uint64_t)b << shift);
+			found[1] = (uint64_t)r;
+		}
+		__syncthreads();
+		prefix = found[0];
+		rank = (int)found[1];
+		__syncthreads();
+	}
+	return prefix;
+}
+
+// median double [n_prob] (NaN for a problem that was not run), weightmap double [n_prob][HW]; run: the run problem of q, or -1
+__global__ __launch_bounds__(kThreads) void tp_halo_norm_kernel(StackGeom g, const int32_t* __restrict__ run, const NormProb* __restrict__ probs,
+	const int32_t* __restrict__ pix, const uint8_t* __restrict__ fit, const double* __restrict__ w, const double* __restrict__ l,
+	double* median, double* weightmap)
+{
+	__shared__ int hist[256];
+	__shared__ uint64_t found[2];
+	__shared__ int cnt[2];
+	const int64_t q = blockIdx.x;
+	const int HW = g.height * g.width;
+	double* wm = weightmap + q * HW;
+	for (int p = threadIdx.x; p < HW; p += kThreads) wm[p] = 0.0;
+	const int r = run[q];
+	if (r < 0) {
+		if (threadIdx.x == 0) median[q] = NAN;
+		return;
+	}
+	const NormProb pr = probs[r];
+	const double* myl = l + pr.c_off;
+	const uint8_t* myfit = fit + pr.c_off;
+	if (threadIdx.x < 2) cnt[threadIdx.x] = 0;
+	__syncthreads();
+	int nf = 0, nn = 0;
+	for (int t = threadIdx.x; t < pr.ncad; t += kThreads)
+		if (myfit[t]) { nf++; nn += myl[t] != myl[t]; }
+	if (nf) atomicAdd(&cnt[0], nf);
+	if (nn) atomicAdd(&cnt[1], nn);
+	__syncthreads();
+	nf = cnt[0];
+	nn = cnt[1];
+	double med = NAN;   // numpy: the median of nothing, or of anything with a NaN, is NaN
+	if (nf > 0 && nn == 0) {
+		if (nf & 1) med = from_key(select_rank(myl, myfit, pr.ncad, nf / 2, hist, found));
+		else {
+			const double a = from_key(select_rank(myl, myfit, pr.ncad, nf / 2 - 1, hist, found));
+			const double b = from_key(select_rank(myl, myfit, pr.ncad, nf / 2, hist, found));
+			med = (a + b) / 2.0;
+		}
+	}
+	if (threadIdx.x == 0) median[q] = med;
+	__syncthreads();   // the zeros of wm before the weights
+	const int32_t* mypix = pix + q * HW;
+	for (int p = threadIdx.x; p < pr.npix; p += kThreads) wm[mypix[p]] = w[pr.w_off + p] / med;
+}
+
+// corr / flux / flux_err double [n_targets][T]
+__global__ __launch_bounds__(kThreads) void tp_halo_lightcurve_kernel(StackGeom g, const float* __restrict__ images_err,
+	const int32_t* __restrict__ stamps, const int32_t* __restrict__ seg, const int32_t* __restrict__ run, const NormProb* __restrict__ probs,
+	const int32_t* __restrict__ cadpos, const double* __restrict__ l, const int32_t* __restrict__ status, const double* __restrict__ median,
+	const double* __restrict__ weightmap, const double* __restrict__ normfactor, double* corr, double* flux, double* flux_err)
+{
+	const int i = blockIdx.y;
+	const int lane = threadIdx.x & 63;
+	const int t = blockIdx.x * (kThreads / 64) + (threadIdx.x >> 6);
+	if (t >= g.n_frames) return;
+	const int HW = g.height * g.width;
+	const int k = seg[t];
+	const double nf = normfactor[i];
+	const int64_t o = (int64_t)i * g.n_frames + t;
+	if (k < 0) {
+		if (lane == 0) { corr[o] = NAN; flux[o] = NAN; flux_err[o] = 0.0; }
+		return;
+	}
+	const int64_t q = (int64_t)i * g.n_seg + k;
+	const int32_t* st = stamps + 4 * i;
+	const double* wm = weightmap + q * HW;
+	const float* err = images_err + (int64_t)t * g.frame_rows * g.frame_cols;
+	double s = 0.0;
+	for (int p = lane; p < HW; p += 64) {
+		const double e = (double)err[stamp_offset(g, st, p)];
+		const double term = (wm[p] * wm[p]) * (e * e);
+		if (term == term) s += term;   // nansum
+	}
+	s = wave_sum(s);
+	if (lane == 0) {
+		const int r = run[q];
+		const int pos = cadpos[o];
+		double c = NAN;
+		if (r >= 0 && pos >= 0 && status[r] != ST_DEGENERATE) c = l[probs[r].c_off + pos] / median[q];
+		corr[o] = c;
+		flux[o] = c * nf;
+		flux_err[o] = fabs(nf) * sqrt(s);
+	}
+}
+
+int stack_check(tp_ctx* ctx, const StackGeom& g, const void* d_stack, const int32_t* h_stamps)
+{
+	TP_REQUIRE(ctx, d_stack && h_stamps, "tp_halo: null pointer");
+	TP_REQUIRE(ctx, g.n_frames >= 1 && g.frame_rows >= 1 && g.frame_cols >= 1 && g.n_targets >= 1 && g.n_targets <= 65535, "tp_halo: bad stack or batch size");
+	TP_REQUIRE(ctx, g.height >= 1 && g.width >= 1 && (int64_t)g.height * g.width <= kMaxStamp, "tp_halo: a stamp holds 1 .. 4096 pixels");
+	TP_REQUIRE(ctx, g.n_seg >= 1 && g.n_seg <= 64, "tp_halo: 1 .. 64 segments");
+	for (int i = 0; i < g.n_targets; i++) {
+		const int32_t* s = h_stamps + 4 * i;
+		TP_REQUIRE(ctx, s[1] - s[0] == g.height && s[3] - s[2] == g.width, "tp_halo: every stamp of a call has the call's height and width");
+		TP_REQUIRE(ctx, s[0] >= g.row0 && s[1] <= g.row0 + g.frame_rows && s[2] >= g.col0 && s[3] <= g.col0 + g.frame_cols,
+			"tp_halo: stamp outside the frame stack");
+	}
+	return TP_OK;
+}
+
+int seg_check(tp_ctx* ctx, const StackGeom& g, const int32_t* h_seg)
+{
+	TP_REQUIRE(ctx, h_seg, "tp_halo: null pointer");
+	int32_t mx = -1;
+	for (int t = 0; t < g.n_frames; t++) {
+		TP_REQUIRE(ctx, h_seg[t] >= -1, "tp_halo: segment below -1");
+		mx = std::max(mx, h_seg[t]);
+	}
+	TP_REQUIRE(ctx, mx + 1 == g.n_seg, "tp_halo: n_seg must be the largest segment plus one");
+	return TP_OK;
+}
+
+struct DevBlocks {
+	tp_ctx* ctx;
+	std::vector<void*> ptrs;
+	int rc = TP_OK;
+	explicit DevBlocks(tp_ctx* c) : ctx(c) {}
+	void* get(uint64_t bytes) {
+		void* p = nullptr;
+		if (rc == TP_OK) rc = tp_malloc(ctx, std::max<uint64_t>(bytes, 16), &p);
+		if (p) ptrs.push_back(p);
+		return p;
+	}
+	~DevBlocks() { for (void* p : ptrs) tp_free(ctx, p); }
+};
+
+} // namespace
+
+extern "C" int tp_halo_select_stack(tp_ctx* ctx, const float* d_images, int32_t n_frames, int32_t frame_rows, int32_t frame_cols, int32_t row0,
+	int32_t col0, int32_t n_targets, const int32_t* h_stamps, int32_t height, int32_t width, const uint8_t* d_mask, int32_t n_seg,
+	const int32_t* h_seg, const int32_t* h_quality, int32_t bitmask, double minflux, int32_t* d_pix, int32_t* d_cad, uint8_t* d_fit,
+	int32_t* d_cadpos, int32_t* d_npix, int32_t* d_ncad)
+{
+	TP_CHECK_CTX(ctx);
+	TP_API_BEGIN
+	const StackGeom g{n_frames, frame_rows, frame_cols, row0, col0, height, width, n_seg, n_targets};
+	int rc = stack_check(ctx, g, d_images, h_stamps);
+	if (rc == TP_OK) rc = seg_check(ctx, g, h_seg);
+	if (rc != TP_OK) return rc;
+	TP_REQUIRE(ctx, d_mask && h_quality && d_pix && d_cad && d_fit && d_cadpos && d_npix && d_ncad, "tp_halo_select_stack: null pointer");
+	const int T = n_frames, HW = height * width;
+	const int64_t n_prob = (int64_t)n_targets * n_seg;
+	// the cadences of every segment in ascending order, their fit flags, and the tiles of kSelTile of them
+	std::vector<int32_t> cadlist, seg_off(n_seg + 1, 0), tiles;
+	std::vector<uint8_t> fitlist;
+	for (int k = 0; k < n_seg; k++) {
+		for (int t = 0; t < T; t++)
+			if (h_seg[t] == k) {
+				cadlist.push_back(t);
+				fitlist.push_back((h_quality[t] & bitmask) == 0);
+			}
+		seg_off[k + 1] = (int32_t)cadlist.size();
+		for (int j = seg_off[k]; j < seg_off[k + 1]; j += kSelTile) {
+			tiles.push_back(k);
+			tiles.push_back(j);
+			tiles.push_back(std::min(j + kSelTile, seg_off[k + 1]));
+		}
+	}
+	const unsigned n_tiles = (unsigned)(tiles.size() / 3);
+	DevBlocks dev(ctx);
+	int32_t* dstamps = (int32_t*)dev.get((uint64_t)n_targets * 4 * sizeof(int32_t));
+	int32_t* dcadlist = (int32_t*)dev.get(cadlist.size() * sizeof(int32_t));
+	uint8_t* dfitlist = (uint8_t*)dev.get(fitlist.size());
+	int32_t* dsegoff = (int32_t*)dev.get(seg_off.size() * sizeof(int32_t));
+	int32_t* dtiles = (int32_t*)dev.get(tiles.size() * sizeof(int32_t));
+	int32_t* dstats = (int32_t*)dev.get((uint64_t)n_prob * HW * 4 * sizeof(int32_t));
+	uint8_t* dpixkeep = (uint8_t*)dev.get((uint64_t)n_prob * HW);
+	uint8_t* dcadkeep = (uint8_t*)dev.get((uint64_t)n_prob * T);
+	if (dev.rc != TP_OK) return dev.rc;
+	hipStream_t s = ctx->stream;
+	TP_HIP(ctx, hipMemcpyAsync(dstamps, h_stamps, (size_t)n_targets * 4 * sizeof(int32_t), hipMemcpyHostToDevice, s));
+	if (!cadlist.empty()) {
+		TP_HIP(ctx, hipMemcpyAsync(dcadlist, cadlist.data(), cadlist.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+		TP_HIP(ctx, hipMemcpyAsync(dfitlist, fitlist.data(), fitlist.size(), hipMemcpyHostToDevice, s));
+		TP_HIP(ctx, hipMemcpyAsync(dtiles, tiles.data(), tiles.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+	}
+	TP_HIP(ctx, hipMemcpyAsync(dsegoff, seg_off.data(), seg_off.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+	const size_t stat_bytes = (size_t)n_prob * HW * sizeof(int32_t);
+	TP_HIP(ctx, hipMemsetAsync(dstats, 0, 3 * stat_bytes, s));
+	TP_HIP(ctx, hipMemsetAsync(reinterpret_cast<char*>(dstats) + 3 * stat_bytes, 0xff, stat_bytes, s));
+	TP_HIP(ctx, hipMemsetAsync(dpixkeep, 0, (size_t)n_prob * HW, s));
+	TP_HIP(ctx, hipMemsetAsync(d_cadpos, 0xff, (size_t)n_targets * T * sizeof(int32_t), s));
+	if (n_tiles) {
+		TP_LAUNCH(ctx, TPK_HALO_SELECT_STAT, tp_halo_select_stat_kernel, dim3(n_tiles, (unsigned)n_targets), dim3(kThreads), 0, g, d_images,
+			(const int32_t*)dstamps, d_mask, (const int32_t*)dtiles, (const int32_t*)dcadlist, (const uint8_t*)dfitlist, minflux, dstats);
+		TP_LAUNCH_CHECK(ctx, "tp_halo_select_stat_kernel");
+		TP_LAUNCH(ctx, TPK_HALO_SELECT_CAD, tp_halo_select_cad_kernel, dim3(n_tiles, (unsigned)n_targets), dim3(kThreads), 0, g, d_images,
+			(const int32_t*)dstamps, d_mask, (const int32_t*)dtiles, (const int32_t*)dcadlist, (const int32_t*)dsegoff, minflux,
+			(const int32_t*)dstats, dpixkeep, dcadkeep);
+		TP_LAUNCH_CHECK(ctx, "tp_halo_select_cad_kernel");
+	}
+	TP_LAUNCH(ctx, TPK_HALO_SELECT_COMPACT, tp_halo_select_compact_kernel, dim3((unsigned)n_prob), dim3(kThreads), 0, g, (const int32_t*)dcadlist,
+		(const uint8_t*)dfitlist, (const int32_t*)dsegoff, d_mask, (const uint8_t*)dpixkeep, (const uint8_t*)dcadkeep, d_pix, d_cad, d_fit,
+		d_cadpos, d_npix, d_ncad);
+	TP_LAUNCH_CHECK(ctx, "tp_halo_select_compact_kernel");
+	TP_HIP(ctx, hipStreamSynchronize(s));   // the host vectors the asynchronous copies read must outlive them
+	return TP_OK;
+	TP_API_END(ctx)
+}
+
+extern "C" int tp_halo_gather_stack(tp_ctx* ctx, const float* d_images, int32_t n_frames, int32_t frame_rows, int32_t frame_cols, int32_t row0,
+	int32_t col0, int32_t n_targets, const int32_t* h_stamps, int32_t height, int32_t width, int32_t n_seg, const int32_t* d_pix,
+	const int32_t* d_cad, const uint8_t* d_fit, int32_t n_run, const int32_t* h_index, const int64_t* h_p_offset, const int32_t* h_npix,
+	const int32_t* h_ncad, float* d_P, uint8_t* d_fit_out)
+{
+	TP_CHECK_CTX(ctx);
+	TP_API_BEGIN
+	const StackGeom g{n_frames, frame_rows, frame_cols, row0, col0, height, width, n_seg, n_targets};
+	int rc = stack_check(ctx, g, d_images, h_stamps);
+	if (rc != TP_OK) return rc;
+	TP_REQUIRE(ctx, n_run >= 0 && n_run <= 65535, "tp_halo_gather_stack: 0 .. 65535 problems per call");
+	if (n_run == 0) return TP_OK;
+	TP_REQUIRE(ctx, d_pix && d_cad && d_fit && h_index && h_p_offset && h_npix && h_ncad && d_P && d_fit_out, "tp_halo_gather_stack: null pointer");
+	const int HW = height * width;
+	std::vector<GatherProb> probs(n_run);
+	int64_t c_tot = 0;
+	int32_t max_ncad = 0;
+	for (int r = 0; r < n_run; r++) {
+		TP_REQUIRE(ctx, h_index[r] >= 0 && h_index[r] < (int64_t)n_targets * n_seg, "tp_halo_gather_stack: problem index out of range");
+		TP_REQUIRE(ctx, h_npix[r] >= 1 && h_npix[r] <= HW && h_ncad[r] >= 0 && h_ncad[r] <= n_frames, "tp_halo_gather_stack: npix or ncad out of range");
+		TP_REQUIRE(ctx, h_p_offset[r] >= 0 && h_p_offset[r] % 4 == 0, "tp_halo_gather_stack: p_offset must be a non-negative multiple of 4");
+		probs[r] = GatherProb{h_p_offset[r], c_tot, h_index[r], h_npix[r], h_ncad[r], (h_npix[r] + 3) & ~3};
+		c_tot += h_ncad[r];
+		max_ncad = std::max(max_ncad, h_ncad[r]);
+	}
+	if (max_ncad == 0) return TP_OK;
+	DevBlocks dev(ctx);
+	int32_t* dstamps = (int32_t*)dev.get((uint64_t)n_targets * 4 * sizeof(int32_t));
+	GatherProb* dprobs = (GatherProb*)dev.get((uint64_t)n_run * sizeof(GatherProb));
+	if (dev.rc != TP_OK) return dev.rc;
+	hipStream_t s = ctx->stream;
+	TP_HIP(ctx, hipMemcpyAsync(dstamps, h_stamps, (size_t)n_targets * 4 * sizeof(int32_t), hipMemcpyHostToDevice, s));
+	TP_HIP(ctx, hipMemcpyAsync(dprobs, probs.data(), (size_t)n_run * sizeof(GatherProb), hipMemcpyHostToDevice, s));
+	TP_LAUNCH(ctx, TPK_HALO_GATHER, tp_halo_gather_kernel, dim3((unsigned)((max_ncad + kGatherRows - 1) / kGatherRows), (unsigned)n_run), dim3(kThreads), 0,
+		g, d_images, (const int32_t*)dstamps, (const GatherProb*)dprobs, d_pix, d_cad, d_fit, d_P, d_fit_out);
+	TP_LAUNCH_CHECK(ctx, "tp_halo_gather_kernel");
+	TP_HIP(ctx, hipStreamSynchronize(s));
+	return TP_OK;
+	TP_API_END(ctx)
+}
+
+extern "C" int tp_halo_outputs_stack(tp_ctx* ctx, const float* d_images_err, int32_t n_frames, int32_t frame_rows, int32_t frame_cols, int32_t row0,
+	int32_t col0, int32_t n_targets, const int32_t* h_stamps, int32_t height, int32_t width, int32_t n_seg, const int32_t* h_seg,
+	const int32_t* d_pix, const int32_t* d_cadpos, int32_t n_run, const int32_t* h_index, const int32_t* h_npix, const int32_t* h_ncad,
+	const uint8_t* d_fit, const double* d_w, const double* d_l, const int32_t* d_status, const double* h_normfactor, double* d_median,
+	double* d_corr, double* d_flux, double* d_flux_err, double* d_weightmap)
+{
+	TP_CHECK_CTX(ctx);
+	TP_API_BEGIN
+	const StackGeom g{n_frames, frame_rows, frame_cols, row0, col0, height, width, n_seg, n_targets};
+	int rc = stack_check(ctx, g, d_images_err, h_stamps);
+	if (rc == TP_OK) rc = seg_check(ctx, g, h_seg);
+	if (rc != TP_OK) return rc;
+	TP_REQUIRE(ctx, n_run >= 0 && n_run <= 65535, "tp_halo_outputs_stack: 0 .. 65535 problems per call");
+	TP_REQUIRE(ctx, d_pix && d_cadpos && h_normfactor && d_median && d_corr && d_flux && d_flux_err && d_weightmap, "tp_halo_outputs_stack: null pointer");
+	TP_REQUIRE(ctx, n_run == 0 || (h_index && h_npix && h_ncad && d_fit && d_w && d_l && d_status), "tp_halo_outputs_stack: null pointer");
+	const int HW = height * width;
+	const int64_t n_prob = (int64_t)n_targets * n_seg;
+	std::vector<NormProb> probs(std::max(n_run, 1));
+	std::vector<int32_t> run(n_prob, -1);
+	int64_t c_tot = 0, w_tot = 0;
+	for (int r = 0; r < n_run; r++) {
+		TP_REQUIRE(ctx, h_index[r] >= 0 && h_index[r] < n_prob && run[h_index[r]] < 0, "tp_halo_outputs_stack: bad problem index");
+		TP_REQUIRE(ctx, h_npix[r] >= 1 && h_npix[r] <= HW && h_ncad[r] >= 0 && h_ncad[r] <= n_frames, "tp_halo_outputs_stack: npix or ncad out of range");
+		probs[r] = NormProb{c_tot, w_tot, h_index[r], h_npix[r], h_ncad[r], 0};
+		run[h_index[r]] = r;
+		c_tot += h_ncad[r];
+		w_tot += h_npix[r];
+	}
+	DevBlocks dev(ctx);
+	int32_t* dstamps = (int32_t*)dev.get((uint64_t)n_targets * 4 * sizeof(int32_t));
+	NormProb* dprobs = (NormProb*)dev.get(probs.size() * sizeof(NormProb));
+	int32_t* drun = (int32_t*)dev.get((uint64_t)n_prob * sizeof(int32_t));
+	int32_t* dseg = (int32_t*)dev.get((uint64_t)n_frames * sizeof(int32_t));
+	double* dnorm = (double*)dev.get((uint64_t)n_targets * sizeof(double));
+	if (dev.rc != TP_OK) return dev.rc;
+	hipStream_t s = ctx->stream;
+	TP_HIP(ctx, hipMemcpyAsync(dstamps, h_stamps, (size_t)n_targets * 4 * sizeof(int32_t), hipMemcpyHostToDevice, s));
+	TP_HIP(ctx, hipMemcpyAsync(dprobs, probs.data(), probs.size() * sizeof(NormProb), hipMemcpyHostToDevice, s));
+	TP_HIP(ctx, hipMemcpyAsync(drun, run.data(), (size_t)n_prob * sizeof(int32_t), hipMemcpyHostToDevice, s));
+	TP_HIP(ctx, hipMemcpyAsync(dseg, h_seg, (size_t)n_frames * sizeof(int32_t), hipMemcpyHostToDevice, s));
+	TP_HIP(ctx, hipMemcpyAsync(dnorm, h_normfactor, (size_t)n_targets * sizeof(double), hipMemcpyHostToDevice, s));
+	TP_LAUNCH(ctx, TPK_HALO_NORM, tp_halo_norm_kernel, dim3((unsigned)n_prob), dim3(kThreads), 0, g, (const int32_t*)drun, (const NormProb*)dprobs,
+		d_pix, d_fit, d_w, d_l, d_median, d_weightmap);
+	TP_LAUNCH_CHECK(ctx, "tp_halo_norm_kernel");
+	TP_LAUNCH(ctx, TPK_HALO_LIGHTCURVE, tp_halo_lightcurve_kernel, dim3((unsigned)((n_frames + kThreads / 64 - 1) / (kThreads / 64)), (unsigned)n_targets),
+		dim3(kThreads), 0, g, d_images_err, (const int32_t*)dstamps, (const int32_t*)dseg, (const int32_t*)drun, (const NormProb*)dprobs, d_cadpos,
+		d_l, d_status, (const double*)d_median, (const double*)d_weightmap, (const double*)dnorm, d_corr, d_flux, d_flux_err);
+	TP_LAUNCH_CHECK(ctx, "tp_halo_lightcurve_kernel");
+	TP_HIP(ctx, hipStreamSynchronize(s));
+	return TP_OK;
+	TP_API_END(ctx)
+}

@@ -9,8 +9,11 @@ DESIGN.md ("Halo") and restated on the CPU in ``tests/halo_common.py``: non-nega
 weights.  Because the digits cannot be halophot's, the plugin is opt-in: ``[halo] enabled = true`` in the settings.
 
 This module holds the host part of :99-173 (stamp size, pixel mask, split times, segments, the packing of the problems), the
-batched optimiser entry :func:`tvmin` (``tp_halo_tvmin``, csrc/halo.hip), :func:`objective` (``tp_halo_objective``) and
-:func:`photometry`, the whole light-curve extraction of one target that ``plugins.HaloPhotometry`` calls.
+batched optimiser entry :func:`tvmin` (``tp_halo_tvmin``, csrc/halo.hip), :func:`objective` (``tp_halo_objective``),
+:func:`photometry`, the whole light-curve extraction of one target that ``plugins.HaloPhotometry`` calls, and
+:func:`photometry_frames`, the same for a batch of targets of a CCD region whose frames are resident on the device: the problems
+are built there from the stack (``tp_halo_select_stack``, ``tp_halo_gather_stack``), one ``tp_halo_tvmin`` call serves the batch and
+the outputs are formed there too (``tp_halo_outputs_stack``) -- no pixel value passes through the host.
 """
 
 import ctypes
@@ -255,3 +258,218 @@ def photometry(ctx, images, images_err, quality, time, timecorr, cadenceno, mask
 	return {'corr_flux': corr, 'flux': corr * normfactor, 'flux_err': flux_err(wms, seg, np.asarray(images_err), normfactor),
 		'weightmap': {'weightmap': wms, 'initial_cadence': first, 'final_cadence': last, 'sat_pixels': [0] * len(probs)},
 		'w': res['w'], 'status': res['status'], 'iterations': res['iterations'], 'f': res['f'], 'split_times': splits, 'segments': seg}
+
+
+# -- the batched path: problems built on the device from a region's frame stack ---------------------------------------------------
+def frames_stamps(limits, targets):
+	"""The Halo stamp of every target as the plugin forms it (:99-102): a fresh default stamp, then ``resize_stamp(width=22,
+	height=22)``, clipped to ``limits``.  Returns int64 ``(n, 4)`` and a bool vector, False where no stamp is left."""
+	from . import stamps as st
+	n = len(targets['starid'])
+	out, valid = np.full((n, 4), -1, dtype='int64'), np.zeros(n, dtype=bool)
+	for i in range(n):
+		row, col = float(targets['row'][i]), float(targets['column'][i])
+		try:
+			first = st.default_stamp(row, col, float(targets['tmag'][i]), limits)
+			out[i] = st.moved(first, limits, row, col, width=DIST_MAX + 2, height=DIST_MAX + 2)
+			valid[i] = out[i, 1] > out[i, 0] and out[i, 3] > out[i, 2]
+		except ValueError:
+			pass
+	return out, valid
+
+
+def frames_pixel_masks(ctx, stack, stamps, rows, columns, quality):
+	"""The pixel masks (:118-120) of a group of equally sized stamps: ``aperture & 1`` is the finite part of the region's sum image
+	cropped to the stamp (``BasePhotometry.aperture``, FFI branch).  bool ``(n, H, W)``."""
+	from . import engine
+	stamps = np.asarray(stamps, dtype='int64')
+	H, W = int(stamps[0, 1] - stamps[0, 0]), int(stamps[0, 3] - stamps[0, 2])
+	d_st = ctx.array(stamps.astype('int32'))
+	crop = engine.crop_sumimage(ctx, stack.sumimage_for(quality), d_st, H, W, stack.row0, stack.col0)
+	finite = np.isfinite(crop.to_host()).reshape(len(stamps), H, W)
+	crop.free()
+	d_st.free()
+	out = np.zeros((len(stamps), H, W), dtype=bool)
+	for i, st in enumerate(stamps):
+		cols, rws = np.meshgrid(np.arange(st[2] + 1, st[3] + 1, 1, dtype='int32'), np.arange(st[0] + 1, st[1] + 1, 1, dtype='int32'))
+		out[i] = pixel_mask(finite[i], cols, rws, rows[i], columns[i])
+	return out
+
+
+class FramesProblems(object):
+	"""
+	The problems of a group of equally sized stamps, selected on the device (``tp_halo_select_stack``): problem ``q = target * n_seg
+	+ segment``; ``npix`` / ``ncad`` on the host, the lists ``pix`` / ``cad`` / ``fit`` / ``cadpos`` on the device.  :meth:`gather`
+	packs the problems of the usable targets (every segment with 1 .. 4096 pixels) for ``tp_halo_tvmin``.
+	"""
+	def __init__(self, ctx, stack, stamps, masks, seg, quality, minflux=SETTINGS['minflux'], bitmask=None):
+		from .engine import TESS_DEFAULT_BITMASK
+		self.ctx, self.stack = ctx, stack
+		self.stamps = np.ascontiguousarray(stamps, dtype='int32').reshape(-1, 4)
+		self.n = len(self.stamps)
+		self.H, self.W = int(self.stamps[0, 1] - self.stamps[0, 0]), int(self.stamps[0, 3] - self.stamps[0, 2])
+		self.T = stack.n_cad
+		self.seg = np.ascontiguousarray(seg, dtype='int32')
+		self.n_seg = int(self.seg.max()) + 1 if len(self.seg) and self.seg.max() >= 0 else 0
+		if self.n_seg < 1:
+			raise ValueError("Halo photometry: no cadence with a finite time")
+		quality = np.ascontiguousarray(quality, dtype='int32')
+		if len(self.seg) != self.T or len(quality) != self.T:
+			raise ValueError('segments and quality must have one entry per frame of the stack')
+		n_prob, HW = self.n * self.n_seg, self.H * self.W
+		self.n_prob = n_prob
+		d_mask = ctx.array(np.ascontiguousarray(masks, dtype='uint8').reshape(self.n, HW))
+		self.pix = ctx.empty((n_prob, HW), 'int32')
+		self.cad = ctx.empty((n_prob, self.T), 'int32')
+		self.fit = ctx.empty((n_prob, self.T), 'uint8')
+		self.cadpos = ctx.empty((self.n, self.T), 'int32')
+		counts = ctx.empty((2, n_prob), 'int32')
+		ctx._check(ctx.lib.tp_halo_select_stack(ctx.handle, stack.dev['images'].ptr, *self._geometry(), d_mask.ptr, self.n_seg, _host_ptr(self.seg),
+			_host_ptr(quality), int(TESS_DEFAULT_BITMASK if bitmask is None else bitmask), float(minflux), self.pix.ptr, self.cad.ptr, self.fit.ptr,
+			self.cadpos.ptr, counts.ptr, counts.ptr + 4 * n_prob))
+		c = counts.to_host()
+		self.npix, self.ncad = c[0].reshape(self.n, self.n_seg), c[1].reshape(self.n, self.n_seg)
+		counts.free()
+		d_mask.free()
+		self.usable = np.all((self.npix >= 1) & (self.npix <= MAX_PIXELS), axis=1)
+		self.P = self.fitc = None
+
+	def _geometry(self):
+		s = self.stack
+		return (s.n_cad, s.n_rows, s.n_cols, s.row0, s.col0, self.n, _host_ptr(self.stamps), self.H, self.W)
+
+	def gather(self):
+		"""``P`` and the fit bytes of the usable targets' problems on the device, laid out as :func:`pack` does."""
+		ctx = self.ctx
+		self.index = np.ascontiguousarray(np.flatnonzero(np.repeat(self.usable, self.n_seg)), dtype='int32')
+		self.run_npix = np.ascontiguousarray(self.npix.ravel()[self.index], dtype='int32')
+		self.run_ncad = np.ascontiguousarray(self.ncad.ravel()[self.index], dtype='int32')
+		pitch = (self.run_npix.astype('int64') + 3) // 4 * 4
+		sizes = pitch * self.run_ncad
+		self.offset = np.zeros(len(self.index), dtype='int64')
+		self.offset[1:] = np.cumsum(sizes)[:-1]
+		self.P = ctx.empty((max(int(sizes.sum()), 4),), 'float32')
+		self.fitc = ctx.empty((max(int(self.run_ncad.sum()), 1),), 'uint8')
+		ctx._check(ctx.lib.tp_halo_gather_stack(ctx.handle, self.stack.dev['images'].ptr, *self._geometry(), self.n_seg, self.pix.ptr, self.cad.ptr,
+			self.fit.ptr, len(self.index), _host_ptr(self.index), _host_ptr(self.offset), _host_ptr(self.run_npix), _host_ptr(self.run_ncad),
+			self.P.ptr, self.fitc.ptr))
+		return self
+
+	def to_host(self):
+		"""The problems as the restatement lists them (for the tests): per problem ``pix``, ``cad``, ``fit`` and, after
+		:meth:`gather`, the padded block of ``P`` (``None`` for the problems of an unusable target)."""
+		pix, cad, fit = self.pix.to_host(), self.cad.to_host(), self.fit.to_host()
+		P = None if self.P is None else self.P.to_host()
+		run = {int(q): r for r, q in enumerate(self.index)} if P is not None else {}
+		out = []
+		for q in range(self.n_prob):
+			npix, ncad = int(self.npix.ravel()[q]), int(self.ncad.ravel()[q])
+			block = None
+			if q in run:
+				r = run[q]
+				pitch = (npix + 3) // 4 * 4
+				block = P[self.offset[r]:self.offset[r] + pitch * ncad].reshape(ncad, pitch)
+			out.append({'pix': pix[q, :npix], 'cad': cad[q, :ncad], 'fit': fit[q, :ncad].astype(bool), 'P': block})
+		return out
+
+	def free(self):
+		for a in (self.pix, self.cad, self.fit, self.cadpos, self.P, self.fitc):
+			if a is not None:
+				a.free()
+
+
+def _frames_chunk(ctx, stack, stamps, masks, seg, quality, normfactor, maxiter, out, idx):
+	"""select -> counts -> gather -> ONE tp_halo_tvmin -> outputs -> download for the targets ``idx`` (one stamp size)."""
+	from .device import device_view
+	fp = FramesProblems(ctx, stack, stamps, masks, seg, quality)
+	n, n_seg, T, HW = fp.n, fp.n_seg, fp.T, fp.H * fp.W
+	fp.gather()
+	n_run = len(fp.index)
+	n_w, n_c = int(fp.run_npix.sum()), int(fp.run_ncad.sum())
+	# one block of float64 for everything that goes back: w, f, median, corr_flux, flux, flux_err, the weight maps
+	sizes = (n_w, n_run, fp.n_prob, n * T, n * T, n * T, fp.n_prob * HW)
+	starts = np.concatenate([[0], np.cumsum(sizes)])
+	block = ctx.empty((max(int(starts[-1]), 1),), 'float64')
+	d_w, d_f, d_med, d_corr, d_flux, d_err, d_wm = (device_view(ctx, block.ptr + 8 * int(a), (max(int(m), 1),), 'float64', base=block)
+		for a, m in zip(starts[:-1], sizes))
+	d_l = ctx.empty((max(n_c, 1),), 'float64')
+	d_is = ctx.empty((2, max(n_run, 1)), 'int32')
+	if n_run:
+		ctx._check(ctx.lib.tp_halo_tvmin(ctx.handle, n_run, _host_ptr(fp.offset), _host_ptr(fp.run_npix), _host_ptr(fp.run_ncad), fp.P.ptr, fp.fitc.ptr,
+			int(maxiter), int(HISTORY), float(FTOL), float(GTOL), d_w.ptr, d_l.ptr, d_f.ptr, d_is.ptr, d_is.ptr + 4 * n_run))
+	nf = np.ascontiguousarray(normfactor, dtype='float64')
+	ctx._check(ctx.lib.tp_halo_outputs_stack(ctx.handle, stack.dev['images_err'].ptr, *fp._geometry(), n_seg, _host_ptr(fp.seg), fp.pix.ptr,
+		fp.cadpos.ptr, n_run, _host_ptr(fp.index), _host_ptr(fp.run_npix), _host_ptr(fp.run_ncad), fp.fitc.ptr, d_w.ptr, d_l.ptr,
+		d_is.ptr + 4 * n_run, _host_ptr(nf), d_med.ptr, d_corr.ptr, d_flux.ptr, d_err.ptr, d_wm.ptr))
+	host, ints = block.to_host(), d_is.to_host()
+	w, f, med, corr, flux, err, wm = (host[int(a):int(a) + int(m)] for a, m in zip(starts[:-1], sizes))
+	out['corr_flux'][idx], out['flux'][idx], out['flux_err'][idx] = corr.reshape(n, T), flux.reshape(n, T), err.reshape(n, T)
+	wm = wm.reshape(n, n_seg, fp.H, fp.W)
+	wo = np.concatenate([[0], np.cumsum(fp.run_npix)])
+	r = 0
+	for j, i in enumerate(idx):
+		out['npix'][i], out['ncad'][i] = fp.npix[j], fp.ncad[j]
+		out['usable'][i] = fp.usable[j]
+		if not fp.usable[j]:
+			continue
+		out['weightmap'][i] = [np.array(wm[j, k]) for k in range(n_seg)]
+		out['w'][i] = [np.array(w[wo[r + k]:wo[r + k + 1]]) for k in range(n_seg)]
+		out['f'][i], out['iterations'][i], out['status'][i] = f[r:r + n_seg], ints[0, r:r + n_seg], ints[1, r:r + n_seg]
+		r += n_seg
+	for a in (block, d_l, d_is):
+		a.free()
+	fp.free()
+
+
+def photometry_frames(ctx, stack, targets, time, quality, sector=None, timecorr=None, cadenceno=None, maxiter=SETTINGS['maxiter'],
+	budget_bytes=None):
+	"""
+	:func:`photometry` for every target of a CCD region held in a ``pipeline.FrameStack``, without a host copy of any pixel: per
+	target the Halo stamp and pixel mask as the plugin forms them, the split times and segments once per batch (``sector=None``:
+	the gap rule; ``timecorr=None``: zeros; ``cadenceno=None``: ``arange(T)``), then per stamp size select -> counts -> gather ->
+	one ``tp_halo_tvmin`` -> outputs -> one download.  A batch whose ``P`` could exceed ``budget_bytes`` (default: a quarter of the
+	device's memory) runs in chunks of targets; every target's result is independent of the chunking, to the bit.
+
+	Returns a dict of columns: ``stamp`` int64 ``(n, 4)``, ``valid`` (a stamp exists), ``usable`` (every segment has 1 .. 4096
+	pixels), ``pixel_mask`` (list of bool images), ``corr_flux`` / ``flux`` / ``flux_err`` float64 ``(n, T)``, ``weightmap`` and ``w``
+	(lists per target of one entry per segment), ``f`` / ``iterations`` / ``status`` / ``npix`` / ``ncad`` ``(n, n_seg)``,
+	``initial_cadence`` / ``final_cadence`` (per segment), ``split_times``, ``segments``.
+	"""
+	from .plugins import mag2flux
+	n, T = len(targets['starid']), stack.n_cad
+	time = np.asarray(time, dtype='float64')
+	timecorr = np.zeros(T) if timecorr is None else np.asarray(timecorr, dtype='float64')
+	cadenceno = np.arange(T) if cadenceno is None else np.asarray(cadenceno)
+	splits = split_times(-1 if sector is None else sector, time, timecorr)
+	seg = segments(time, splits)
+	n_seg = int(seg.max()) + 1 if len(seg) and seg.max() >= 0 else 0
+	stamps, valid = frames_stamps(stack.limits, targets)
+	rows, cols = np.asarray(targets['row'], dtype='float64'), np.asarray(targets['column'], dtype='float64')
+	out = {'stamp': stamps, 'valid': valid, 'usable': np.zeros(n, dtype=bool), 'pixel_mask': [None] * n, 'weightmap': [None] * n, 'w': [None] * n,
+		'corr_flux': np.full((n, T), np.nan), 'flux': np.full((n, T), np.nan), 'flux_err': np.zeros((n, T)),
+		'f': np.full((n, n_seg), np.nan), 'iterations': np.zeros((n, n_seg), dtype='int32'), 'status': np.zeros((n, n_seg), dtype='int32'),
+		'npix': np.zeros((n, n_seg), dtype='int32'), 'ncad': np.zeros((n, n_seg), dtype='int32'), 'split_times': splits, 'segments': seg,
+		# (a segment may hold no cadence -- three split times and a gap in the frames: 0 then, as halo.photometry writes it)
+		'initial_cadence': [int(cadenceno[seg == k].min()) if np.any(seg == k) else 0 for k in range(n_seg)],
+		'final_cadence': [int(cadenceno[seg == k].max()) if np.any(seg == k) else 0 for k in range(n_seg)]}
+	if n_seg == 0:
+		return out
+	# (one scalar call per target, as the plugin makes it: the array form of the power function may round differently)
+	normfactor = np.array([mag2flux(t) for t in np.asarray(targets['tmag'], dtype='float64')], dtype='float64')
+	if budget_bytes is None:
+		budget_bytes = ctx.info()['hbm_bytes'] / 4.0
+	active = np.flatnonzero(valid)
+	keys = (stamps[active, 1] - stamps[active, 0]) * 100000 + (stamps[active, 3] - stamps[active, 2])
+	for key in np.unique(keys):
+		idx = active[keys == key]
+		HW = int(key // 100000) * int(key % 100000)
+		masks = frames_pixel_masks(ctx, stack, stamps[idx], rows[idx], cols[idx], quality)
+		# the most P a target can need: every cadence with a segment, every stamp pixel
+		bound = 4.0 * ((HW + 3) // 4 * 4) * int(np.count_nonzero(seg >= 0))
+		per = max(1, min(len(idx), int(budget_bytes // bound), 65535 // n_seg))
+		for a in range(0, len(idx), per):
+			sub = idx[a:a + per]
+			for j, i in enumerate(sub):
+				out['pixel_mask'][i] = masks[a + j]
+			_frames_chunk(ctx, stack, stamps[sub], masks[a:a + per], seg, quality, normfactor[sub], maxiter, out, sub)
+	return out

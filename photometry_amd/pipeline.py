@@ -14,6 +14,7 @@ from . import engine, _lib, wcs
 from .engine import TESS_DEFAULT_BITMASK
 from ._lib import TessphotError
 from .device import DeviceCube, device_view
+from .status import STATUS
 
 
 class ApertureBatch(object):
@@ -1046,4 +1047,137 @@ def psf_frames(ctx, stack, targets, catalog, time, quality, prf_model, readnoise
 		out.pos_centroid[idx, :, 0] = crow[:, :T]
 		out.pos_centroid[idx, :, 1] = ccol[:, :T]
 		out.status[idx] = 1
+	return out
+
+
+#--------------------------------------------------------------------------------------------------
+# Halo photometry of many targets of one CCD region (the batched counterpart of the Halo plugin)
+#--------------------------------------------------------------------------------------------------
+class HaloFramesResult(object):
+	"""
+	Columnar results of :func:`halo_frames`: ``status`` int32 (values of ``STATUS``), ``stamp`` int64 ``(n, 4)``, ``flux`` /
+	``flux_err`` / ``corr_flux`` float64 ``(n, T)``, ``pos_centroid`` float64 ``(n, T, 2)`` as (column, row), per target the lists
+	``pixel_mask`` (= ``final_phot_mask``), ``weightmap`` (the dict ``halo.photometry`` returns), ``w``, ``skip_targets`` and
+	``diagnostics`` (OK targets), ``f`` / ``iterations`` / ``tv_status`` ``(n, n_seg)``, ``split_times``, ``segments``, ``headers``
+	(the ``HALO_*`` cards), ``errors``: target index -> messages.  ``result[i]`` is the per-target dict.
+	"""
+	def __init__(self, n, T):
+		self.n = int(n)
+		self.status = np.zeros(n, dtype='int32')
+		self.stamp = np.full((n, 4), -1, dtype='int64')
+		self.flux, self.flux_err, self.corr_flux = np.zeros((n, T)), np.zeros((n, T)), np.full((n, T), np.nan)
+		self.pos_centroid = np.zeros((n, T, 2))
+		self.pixel_mask, self.weightmap, self.w = [None] * n, [None] * n, [None] * n
+		self.skip_targets, self.diagnostics = [[] for _ in range(n)], [None] * n
+		self.f = self.iterations = self.tv_status = None
+		self.split_times = self.segments = None
+		self.headers = {}
+		self.errors = {}
+
+	def __len__(self):
+		return self.n
+
+	def __getitem__(self, i):
+		i = int(i)
+		if i < 0:
+			i += self.n
+		if not 0 <= i < self.n:
+			raise IndexError(i)
+		r = {'status': int(self.status[i]), 'stamp': tuple(int(v) for v in self.stamp[i]), 'errors': list(self.errors.get(i, [])),
+			'flux': self.flux[i], 'flux_err': self.flux_err[i], 'corr_flux': self.corr_flux[i], 'pos_centroid': self.pos_centroid[i],
+			'pixel_mask': self.pixel_mask[i], 'weightmap': self.weightmap[i], 'w': self.w[i], 'skip_targets': list(self.skip_targets[i]),
+			'diagnostics': self.diagnostics[i], 'headers': self.headers}
+		if self.f is not None:
+			r.update(f=self.f[i], iterations=self.iterations[i], tv_status=self.tv_status[i])
+		return r
+
+	def __iter__(self):
+		return (self[i] for i in range(self.n))
+
+
+def halo_frames(ctx, stack, targets, catalog, time, quality, sector=None, timecorr=None, cadenceno=None, jitter=None, settings=None,
+	budget_bytes=None):
+	"""
+	``HaloPhotometry.do_photometry`` (halo/halo_photometry.py:99-265) for every target of a CCD region held in a :class:`FrameStack`
+	-- ``tessphot('halo', ...)`` for a batch: the Halo stamps and pixel masks as the plugin forms them, the problems of all targets
+	built on the device from the stack, ONE ``tp_halo_tvmin`` call, light curves, flux errors and weight maps formed on the device
+	(``halo.photometry_frames``).  ``jitter``: ``(T, 2)`` column / row shifts (``pos_corr``) added to the target position for
+	``pos_centroid``; no centroid is computed (:162-164).  Status and messages follow the plugin: ERROR "Halo optimization failed"
+	for a degenerate segment, ERROR "no usable pixels in the pixel mask".  Raises ``NotImplementedError`` while ``[halo] enabled``
+	is off.  Returns a :class:`HaloFramesResult`.
+	"""
+	from . import halo
+	from .plugins import load_settings
+	settings = load_settings() if settings is None else settings
+	if not halo.enabled(settings):
+		raise NotImplementedError("HaloPhotometry is off: set '[halo] enabled = true' in the settings file named by "
+			"TESSPHOT_SETTINGS to run this engine's TV-min implementation")
+	n, T = len(targets['starid']), stack.n_cad
+	time = np.asarray(time, dtype='float64')
+	res = halo.photometry_frames(ctx, stack, targets, time, quality, sector=sector, timecorr=timecorr, cadenceno=cadenceno, budget_bytes=budget_bytes)
+	out = HaloFramesResult(n, T)
+	out.stamp[:] = res['stamp']
+	out.split_times, out.segments = res['split_times'], res['segments']
+	out.f, out.iterations, out.tv_status = res['f'], res['iterations'], res['status']
+	out.corr_flux, out.flux_err = res['corr_flux'], res['flux_err']
+	out.pixel_mask, out.w = res['pixel_mask'], res['w']
+	out.headers = {'HALO_VER': (halo.VERSION, 'Version of halo photometry'), 'HALO_OBJ': (halo.SETTINGS['objective'], 'Halophot objective function'),
+		'HALO_THR': (halo.SETTINGS['thresh'], 'Halophot saturated pixel threshold'), 'HALO_MXI': (halo.SETTINGS['maxiter'], 'Halophot maximum optimisation iterations'),
+		'HALO_SCL': (halo.SETTINGS['sigclip'], 'Halophot sigma clipping enabled'), 'HALO_MFL': (halo.SETTINGS['minflux'], 'Halophot minimum flux')}
+	good = np.isfinite(time)
+	jit = np.zeros((T, 2)) if jitter is None else np.asarray(jitter, dtype='float64')
+	rows, cols = np.asarray(targets['row'], dtype='float64'), np.asarray(targets['column'], dtype='float64')
+	n_seg = res['f'].shape[1]
+	catalog = {k: np.asarray(v) for k, v in catalog.items()}
+	for i in range(n):
+		if not res['valid'][i]:
+			out.status[i] = STATUS.ERROR.value
+			out.errors[i] = ['ValueError: Invalid stamp selected']
+			out.stamp[i] = (-1, -2, -1, -2)
+		elif n_seg == 0 or not res['usable'][i]:
+			out.status[i] = STATUS.ERROR.value
+			out.errors[i] = ['ValueError: Halo photometry: no usable pixels in the pixel mask']
+		elif np.any(res['status'][i] == halo.DEGENERATE):
+			out.status[i] = STATUS.ERROR.value
+			out.errors[i] = ['ERROR: Halo optimization failed']
+		else:
+			out.status[i] = STATUS.OK.value
+			out.flux[i, good] = res['flux'][i, good]
+			# the target position per cadence; no centroids are calculated (:162-164, :221-222)
+			out.pos_centroid[i, :, 0] = cols[i] + jit[:, 0]
+			out.pos_centroid[i, :, 1] = rows[i] + jit[:, 1]
+			out.weightmap[i] = {'weightmap': res['weightmap'][i], 'initial_cadence': list(res['initial_cadence']),
+				'final_cadence': list(res['final_cadence']), 'sat_pixels': [0] * n_seg}
+			# other targets in the mask (:257-262)
+			st, mask = out.stamp[i], res['pixel_mask'][i]
+			cat = _catalog_of_stamp(catalog, st)
+			cc, rr = np.meshgrid(np.arange(st[2] + 1, st[3] + 1, 1, dtype='int32'), np.arange(st[0] + 1, st[1] + 1, 1, dtype='int32'))
+			out.skip_targets[i] = [int(sid) for sid, r, c in zip(cat['starid'], cat['row'], cat['column'])
+				if sid != targets['starid'][i] and np.any(mask & (rr == np.round(r) + 1) & (cc == np.round(c) + 1))]
+	# the light-curve diagnostics of the OK targets (BasePhotometry.py:1343-1407), one device call per stamp size
+	ok = np.flatnonzero(out.status == STATUS.OK.value)
+	if len(ok):
+		d_time, d_q = ctx.array(time), ctx.array(np.ascontiguousarray(quality, dtype='int32'))
+		keys = (out.stamp[ok, 1] - out.stamp[ok, 0]) * 100000 + (out.stamp[ok, 3] - out.stamp[ok, 2])
+		for key in np.unique(keys):
+			idx = ok[keys == key]
+			H, W = int(key // 100000), int(key % 100000)
+			block = np.zeros((5, len(idx), T))
+			block[0], block[1] = out.flux[idx], out.flux_err[idx]
+			block[3], block[4] = out.pos_centroid[idx, :, 0], out.pos_centroid[idx, :, 1]
+			d_st = ctx.array(out.stamp[idx].astype('int32'))
+			d_sum = engine.crop_sumimage(ctx, stack.sumimage_for(quality), d_st, H, W, stack.row0, stack.col0)
+			d_mask = ctx.array(np.stack([out.pixel_mask[i] for i in idx]).astype('uint8'))
+			d_status = ctx.array(np.full(len(idx), STATUS.OK.value, dtype='int32'))
+			d_block = ctx.array(block)
+			lc = engine.LightCurves(ctx, len(idx), T, block=d_block)
+			diag = engine.lightcurve_diagnostics(ctx, lc, d_time, d_q, status=d_status, sumimage=device_view(ctx, d_sum.ptr, (len(idx), H, W), 'float64', base=d_sum),
+				mask=d_mask)
+			host = diag.to_host()
+			for j, i in enumerate(idx):
+				out.diagnostics[i] = dict(zip(engine.DIAGNOSTICS_COLUMNS, host[j]))
+			for a in (diag, d_block, d_status, d_mask, d_sum, d_st):
+				a.free()
+		d_time.free()
+		d_q.free()
 	return out

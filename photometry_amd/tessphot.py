@@ -66,23 +66,42 @@ def run_plugin(plugin, *args, before_save=None, **kwargs):
 	return FailedTask(lost) if pho is None else pho
 
 
+#: the two reasons of the switch (tessphot.py:94, :101), by the code :func:`halo_switch_codes` returns
+_SWITCH_TEXT = {1: "Too many stamp resizes. Let us try Halo instead.", 2: "Target is still touching the edge. Let us try Halo instead."}
+
+
+def halo_switch_codes(tmag, is_tpf, failed, is_error, gave_up, edge_flux, tmag_limit, flux_limit):
+	"""
+	The predicate of tessphot.py:81-102 on columns (arrays of one length): ``tmag``, ``is_tpf`` (a ``tpf:`` datasource), ``failed``
+	(the task never produced a photometry object), ``is_error`` (status ERROR), ``gave_up`` (one of the two resize messages is among
+	the details' errors), ``edge_flux`` (NaN: none).  Returns int8: 0 no switch, else a key of the reasons.  The one predicate of
+	the per-target entry (:func:`halo_switch_reason`) and of the batched one (:func:`tessphot_frames`).
+	"""
+	# (the expected flux and the ratio one scalar at a time, in the operands' own types: the expressions of tessphot.py:98-99 as the
+	# per-target entry has always evaluated them -- the array form of the power function may round differently)
+	tmag, edge_flux = list(tmag), list(edge_flux)
+	with np.errstate(invalid='ignore', divide='ignore'):
+		edge = np.array([bool(e / mag2flux(t) > flux_limit) for e, t in zip(edge_flux, tmag)], dtype=bool)
+		faint = np.array([bool(t > tmag_limit) for t in tmag], dtype=bool)
+	bright = ~np.asarray(failed, dtype=bool) & ~faint & ~np.asarray(is_tpf, dtype=bool)
+	resize = np.asarray(is_error, dtype=bool) & np.asarray(gave_up, dtype=bool)
+	return np.where(bright & resize, 1, np.where(bright & edge, 2, 0)).astype('int8')
+
+
 def halo_switch_reason(pho, settings=None):
 	"""
 	Why the aperture result ``pho`` of a bright target should be redone with Halo photometry, or ``None``
-	(the predicate of tessphot.py:81-102).
+	(the predicate of tessphot.py:81-102, :func:`halo_switch_codes` on one record).
 	"""
 	if isinstance(pho, FailedTask):
 		return None
 	settings = load_settings() if settings is None else settings
-	if pho.target['tmag'] > settings.getfloat('haloswitch', 'tmag_limit') or pho.datasource.startswith('tpf:'):
-		return None
 	messages = pho._details.get('errors', [])
-	if pho.status == STATUS.ERROR and any(m in messages for m in _RESIZE_GAVE_UP):
-		return "Too many stamp resizes. Let us try Halo instead."
 	edge_flux = pho._details.get('edge_flux')
-	if edge_flux is not None and edge_flux / mag2flux(pho.target['tmag']) > settings.getfloat('haloswitch', 'flux_limit'):
-		return "Target is still touching the edge. Let us try Halo instead."
-	return None
+	code = halo_switch_codes([pho.target['tmag']], [pho.datasource.startswith('tpf:')], [False], [pho.status == STATUS.ERROR],
+		[any(m in messages for m in _RESIZE_GAVE_UP)], [float('nan') if edge_flux is None else edge_flux],
+		settings.getfloat('haloswitch', 'tmag_limit'), settings.getfloat('haloswitch', 'flux_limit'))[0]
+	return _SWITCH_TEXT.get(int(code))
 
 
 def tessphot(method=None, *args, **kwargs):
@@ -131,6 +150,8 @@ class BatchResult(object):
 		self._details = details
 		self.lightcurve = lightcurve
 		self.final_phot_mask = mask
+		#: the weight maps of a target done with Halo photometry (``halo.photometry``'s ``weightmap`` dict), else None
+		self.halo_weightmap = None
 
 
 def _diagnostics_into(details, d, status):
@@ -161,6 +182,8 @@ class BatchResults(object):
 	integers -- what ``todolist.status`` stores, taskmanager.py:538-541 --, ``starid``, ``stamp``, ``stamp_resizes`` and, through
 	:meth:`column`, ``mask_size`` / ``contamination`` / the diagnostics), and the per-target objects a scheduler's ``save_result``
 	takes only when asked for: ``results[i]`` (or iteration) builds the :class:`BatchResult` of target ``i``.
+	For a target that was switched to Halo photometry ``status`` and ``stamp`` are the Halo run's; ``stamp_resizes`` and
+	:meth:`column` keep reporting the aperture run that led to the switch (the Halo values are in ``results[i]`` and ``self.halo``).
 	"""
 
 	def __init__(self, frames_result, starid):
@@ -175,9 +198,73 @@ class BatchResults(object):
 			self._problems[sel] = fr.column('flags', fill=0)[sel].astype('int64')
 			status[sel[(self._problems[sel] & 7) != 0]] = STATUS.ERROR.value
 		self.status = status
+		#: targets redone with Halo photometry (:meth:`switch_to_halo`): target -> row of ``self.halo``
+		self.halo, self.halo_rows, self._stamp = None, {}, None
 
 	def __len__(self):
 		return len(self.frames)
+
+	def edge_flux_column(self):
+		"""``details['edge_flux']`` of every target as a column (NaN: none): the flux on the stuck edge of the haloswitch quick break,
+		else the diagnostics' edge flux of a finished light curve -- what :meth:`__getitem__` puts into the details."""
+		fr = self.frames
+		out = np.full(len(fr), np.nan)
+		for i, v in fr.edge_flux.items():
+			out[i] = v
+		sel = np.flatnonzero(fr.has_result & ((fr.status == STATUS.OK.value) | (fr.status == STATUS.WARNING.value)) & ((self._problems & 7) == 0))
+		if len(sel):
+			out[sel] = fr.column('edge_flux')[sel]
+		return out
+
+	def halo_switch(self, tmag, settings, datasource='ffi'):
+		"""The targets the predicate of tessphot.py:81-102 sends to Halo photometry: indices and reason codes."""
+		fr = self.frames
+		gave_up = np.zeros(len(fr), dtype=bool)
+		for i, messages in fr.errors.items():
+			gave_up[i] = any(m in messages for m in _RESIZE_GAVE_UP)
+		codes = halo_switch_codes(tmag, np.full(len(fr), datasource.startswith('tpf:')), np.zeros(len(fr), dtype=bool),
+			self.status == STATUS.ERROR.value, gave_up, self.edge_flux_column(), settings.getfloat('haloswitch', 'tmag_limit'),
+			settings.getfloat('haloswitch', 'flux_limit'))
+		idx = np.flatnonzero(codes)
+		return idx, codes[idx]
+
+	def switch_to_halo(self, idx, halo_result):
+		"""Targets ``idx`` are what ``halo_result`` (a ``pipeline.HaloFramesResult`` over exactly them) says: tessphot.py:95-109."""
+		self._aperture_edge_flux = self.edge_flux_column()
+		self.halo = halo_result
+		self.halo_rows = {int(i): j for j, i in enumerate(idx)}
+		status = np.array(halo_result.status, dtype='int32')
+		# the diagnostics' ValueErrors turn OK into ERROR here too (as __init__ does for the aperture targets): the column and
+		# results[i].status agree
+		for j, d in enumerate(halo_result.diagnostics):
+			if d is not None and status[j] in (STATUS.OK.value, STATUS.WARNING.value) and int(d['flags']) & 7:
+				status[j] = STATUS.ERROR.value
+		self.status[idx] = status
+		self._stamp = np.array(self.frames.stamp, copy=True)
+		self._stamp[idx] = halo_result.stamp
+
+	def _halo_item(self, i):
+		r = self.halo[self.halo_rows[i]]
+		status = STATUS(r['status'])
+		details = {'stamp': r['stamp']}
+		errors = list(r['errors'])
+		lc = mask = None
+		if status == STATUS.OK:
+			mask = r['pixel_mask']
+			T = len(r['flux'])
+			lc = {'flux': r['flux'], 'flux_err': r['flux_err'], 'flux_background': np.zeros(T), 'pos_centroid': r['pos_centroid']}
+			if r['skip_targets']:
+				details['skip_targets'] = r['skip_targets']
+			status = _diagnostics_into(details, r['diagnostics'], status)
+			details['mask_size'] = int(mask.sum())
+			errors += details.pop('errors', [])
+		# the diagnostics that led to the switch are kept (tessphot.py:104-109)
+		details['errors'] = errors + ['Automatically switched to Halo photometry']
+		ef = self._aperture_edge_flux[i]
+		details['edge_flux'] = None if np.isnan(ef) else float(ef)
+		out = BatchResult(int(self.starid[i]), status, 'halo', details, lc, mask)
+		out.halo_weightmap = r['weightmap']
+		return out
 
 	def column(self, name):
 		"""Per-target float64 column: ``mask_size``, ``contamination`` or one of ``engine.DIAGNOSTICS_COLUMNS``; NaN without a result."""
@@ -185,13 +272,18 @@ class BatchResults(object):
 
 	@property
 	def stamp(self):
-		return self.frames.stamp
+		"""The final stamp of every target: the Halo stamp for a target that was switched to Halo photometry."""
+		return self.frames.stamp if self._stamp is None else self._stamp
 
 	@property
 	def stamp_resizes(self):
 		return self.frames.stamp_resizes
 
 	def __getitem__(self, i):
+		if self.halo_rows:
+			i = int(i) + len(self) if int(i) < 0 else int(i)
+			if i in self.halo_rows:
+				return self._halo_item(i)
 		r = self.frames[i]
 		status = STATUS(r['status'])
 		details = {'stamp': r.get('stamp'), 'stamp_resizes': r['stamp_resizes']}
@@ -216,33 +308,57 @@ class BatchResults(object):
 		return (self[i] for i in range(len(self)))
 
 
-def tessphot_frames(ctx, stack, targets, catalog, time, quality, settings=None):
+def _halo_switch_frames(ctx, stack, results, targets, catalog, time, quality, settings, sector, timecorr, cadenceno):
+	"""The method switch of ``tessphot(None, ...)`` (tessphot.py:76-109) for a finished aperture batch: with ``[halo] enabled`` the
+	bright targets whose aperture run gave up or left flux on a stuck edge go through ``pipeline.halo_frames`` in one call."""
+	from . import pipeline, halo
+	settings = load_settings() if settings is None else settings
+	if not halo.enabled(settings):
+		return results
+	logger = logging.getLogger(__name__)
+	idx, codes = results.halo_switch(np.asarray(targets['tmag']), settings)
+	if len(idx) == 0:
+		return results
+	for code in codes:
+		logger.warning(_SWITCH_TEXT[int(code)])
+	sub = {k: np.asarray(targets[k])[idx] for k in ('starid', 'tmag', 'row', 'column')}
+	res = pipeline.halo_frames(ctx, stack, sub, catalog, time, quality, sector=sector, timecorr=timecorr, cadenceno=cadenceno, settings=settings)
+	results.switch_to_halo(idx, res)
+	return results
+
+
+def tessphot_frames(ctx, stack, targets, catalog, time, quality, settings=None, sector=None, timecorr=None, cadenceno=None):
 	"""
 	Aperture photometry of every target of a CCD region resident in HBM (:class:`photometry_amd.pipeline.FrameStack`), stamp
 	resizes included: what ``tessphot('aperture', ...)`` returns per target, for the whole batch in a few device passes.
+	With ``[halo] enabled = true`` in the settings it is ``tessphot(None, ...)``: the bright targets whose aperture run gave up on
+	stamp resizes or left flux on a stuck edge (:func:`halo_switch_codes`) are redone with Halo photometry in one batched call
+	(``pipeline.halo_frames``; ``sector`` / ``timecorr`` / ``cadenceno`` as there) and their results are the Halo ones
+	(``method == 'halo'``, ``halo_weightmap``).
 	Returns a :class:`BatchResults`: columns for the whole batch, one :class:`BatchResult` per target on demand (``results[i]``).
 	"""
 	from . import pipeline
 	res = pipeline.aperture_frames(ctx, stack, targets, catalog, time, quality, settings=settings)
-	return BatchResults(res, targets['starid'])
+	return _halo_switch_frames(ctx, stack, BatchResults(res, targets['starid']), targets, catalog, time, quality, settings, sector, timecorr, cadenceno)
 
 
-def tessphot_frames_pipelined(ctx, stack, batches, catalog, time, quality, settings=None, in_flight=4):
+def tessphot_frames_pipelined(ctx, stack, batches, catalog, time, quality, settings=None, in_flight=4, sector=None, timecorr=None, cadenceno=None):
 	"""
 	:func:`tessphot_frames` over consecutive batches of targets of one CCD region -- what a run over a whole CCD does, a few
 	thousand targets per call -- with ``in_flight`` batches on the device at a time (``pipeline.aperture_frames_pipelined``: the
 	first round of a batch runs under the latency-bound resize rounds of the one before it).  ``batches``: an iterable of
-	``targets`` dicts; yields one :class:`BatchResults` per batch, in order, equal to what a call of its own returns.
+	``targets`` dicts; yields one :class:`BatchResults` per batch, in order, equal to what a call of its own returns (the switch to
+	Halo photometry included, applied to each batch before it is yielded).
 	"""
 	from . import pipeline
 	batches = list(batches) if not hasattr(batches, '__next__') else batches
-	ids = []
+	seen = []
 	def feed():
 		for t in batches:
-			ids.append(t['starid'])
+			seen.append(t)
 			yield t
 	for k, res in enumerate(pipeline.aperture_frames_pipelined(ctx, stack, feed(), catalog, time, quality, settings=settings, in_flight=in_flight)):
-		yield BatchResults(res, ids[k])
+		yield _halo_switch_frames(ctx, stack, BatchResults(res, seen[k]['starid']), seen[k], catalog, time, quality, settings, sector, timecorr, cadenceno)
 
 
 def tessphot_batch(ctx, scene, cubes='host'):
