@@ -272,6 +272,23 @@ int tp_background_sumimage(tp_ctx* ctx, const tp_cube_desc* desc, const float* d
 
 /* ---- B1 + full-frame B2 / B3 / A1: the prepare stage on a frame stack ----------------------------------------
  * Frames: float32 [n_frames][frame_rows][row_pitch] resident in HBM (frame k at + k * frame_stride), as for tp_cut_stamps.
+ * Layout of every pointer of this family (tests/test_gpu_frame_layouts.py holds each entry to it):
+ *   - an entry that takes row_pitch and frame_stride addresses pixel (k, r, c) at k * frame_stride + r * row_pitch + c and requires
+ *     row_pitch >= frame_cols and frame_stride >= frame_rows * row_pitch; an entry that takes n_pixels and frame_stride only reads
+ *     contiguous images (pixel p of frame k at k * frame_stride + p, frame_stride >= n_pixels).  Elements between the rows, between
+ *     the frames and after the last frame are never read and, in an output, never written.  The base pointer may point into a
+ *     larger allocation (a window of a wider stack: row_pitch = the full width); no entry assumes an alignment of the base
+ *     pointer, the pitch or the stride beyond that of a float (all loads and stores are single elements).
+ *   - tp_background_mesh / _mesh_radial: d_frames with row_pitch / frame_stride.  d_exclude and d_subtract are DENSE
+ *     [frame_rows][frame_cols] whatever row_pitch is, frame k at + k * exclude_frame_stride / subtract_frame_stride; each stride is
+ *     0 (one image for all frames) or >= frame_rows * frame_cols, anything else is rejected.  d_mesh, d_nmasked dense [n_frames][ny][nx].
+ *   - tp_background_zoom: d_background is written with row_pitch / frame_stride (the image pixels only); frame_stride below
+ *     frame_rows * row_pitch is rejected, and so is a mesh that does not cover the frame (mesh_rows * box_size < frame_rows, or
+ *     the same for the columns).  d_coef dense [n_frames][mesh_rows][mesh_cols], d_vmin / d_vmax [n_frames].
+ *   - tp_frames_smooth_time: d_in and d_out have the SAME layout, frame k at + k * frame_stride in both; of d_out the n_pixels values
+ *     of every frame are written, the frame_stride - n_pixels elements after them are not.
+ *   - tp_frames_sumimage: d_images with frame_stride; d_quality [n_frames]; d_sumimage dense [n_pixels].
+ *   - tp_frames_subtract: every pointer dense [n_values] (no pitch).
  * tp_background_mesh (B1, first half): the low-resolution mesh of backgrounds.fit_background for a plain image
  *   (photometry/backgrounds.py:89-97 pixel mask; :200-206 photutils Background2D on box_size x box_size cells with
  *   SigmaClip(3, maxiters = 5) and the SExtractor estimator): d_mesh float64 [n_frames][ny][nx] (NaN for a cell without an
@@ -316,8 +333,14 @@ int tp_frames_sumimage(tp_ctx* ctx, int32_t n_frames, int64_t n_pixels, int64_t 
  *   scipy.ndimage.median_filter(img - SumImage, size) with the default 'reflect' boundary, for every frame of a stack;
  *   d_reference: float64 [frame_rows][frame_cols] (the sum image) or NULL; size odd, <= 15 (the reference uses 15);
  *   float32 output (what prepare.py:533-537 stores); non-finite input values sort to the end of a window.
+ *   Layout: d_frames with row_pitch / frame_stride; d_reference DENSE [frame_rows][frame_cols], shared by all frames; d_out has
+ *   the layout of d_frames -- output pixel (k, r, c) at k * frame_stride + r * row_pitch + c, NOT a dense [n_frames][rows][cols]
+ *   buffer: it must be as large as the input stack; the padding between its rows and frames is not written.  Every size runs one
+ *   of three kernels (15 on frames of at least 15 x 15; 9, 11, 13 on frames at least as large as the window; everything else).
  * tp_frames_block_median_accumulate: one block of the "mean shenanigans" (prepare.py:558-575): acc += nanmedian over the
  *   n_block <= 32 frames listed in d_frame_index (per pixel, NaN result -> 0); the caller divides by the number of blocks.
+ *   d_frames: contiguous images, frame k at + k * frame_stride (>= n_pixels); d_frame_index int32 [n_block], every entry a frame
+ *   of the stack (not checked); d_accumulator dense float64 [n_pixels].
  * tp_frames_threshold_flags: prepare.py:594-607: clears flag_bit in every pixel flag and sets it where
  *   |indicator - mean| > threshold (PixelQualityFlags.BackgroundShenanigans, bkgshe_threshold = 40).              */
 /* tp_frames_pixel_flags: the per-frame pixel flags of the prepare stage (prepare.py:296-297, 406-408): bit_background
@@ -326,6 +349,9 @@ int tp_frames_sumimage(tp_ctx* ctx, int32_t n_frames, int64_t n_pixels, int64_t 
  *   columns >= d_first_excluded_column[k] (the host evaluates the header rules; NULL = no rule fires), and the whole frame when
  *   every pixel of it is zero and zero_is_excluded (TESS data).  d_all_zero int32 [n_frames] (out): the zero test per frame.
  *   d_pixel_flags uint8 [n_frames][rows][cols]; passed as d_exclude to tp_background_mesh / tp_radial_* it is exactly the mask.
+ *   Layout: the zero test walks a frame as one run of rows * cols values, so the rows must be contiguous: row_pitch != frame_cols
+ *   is rejected ("frames must be contiguous images") before anything is written; frame_stride may exceed rows * cols.  d_all_zero
+ *   and d_pixel_flags are dense.
  * tp_frames_used_in_background: backgrounds_pixels_used (prepare.py:435, 464-466): d_used uint8 [n_pixels] = the pixel's
  *   bit_background is clear in more than threshold of the frames.                                                    */
 int tp_frames_pixel_flags(tp_ctx* ctx, const float* d_frames, int32_t n_frames, int32_t frame_rows, int32_t frame_cols,
@@ -341,7 +367,13 @@ int tp_frames_threshold_flags(tp_ctx* ctx, const float* d_indicator, const doubl
 	int64_t n_pixels, int32_t n_frames, uint8_t* d_pixel_flags);
 
 /* ---- B1, TESS branch: the radial component of fit_background (photometry/backgrounds.py:104-197) ---------------
- * Frames: float32 [n_frames][n_pixels] contiguous images (row_pitch == frame_cols), frame k at + k * frame_stride.  The
+ * Frames: float32 [n_frames][n_pixels] contiguous images (row_pitch == frame_cols), frame k at + k * frame_stride (>= n_pixels).
+ * The images beside the frames -- d_square, d_exclude (tp_radial_zeropoint / _ring_modes and their _zoom forms) and d_add
+ * (tp_radial_evaluate) -- are contiguous too, frame k at + k * square_frame_stride / exclude_frame_stride / add_frame_stride: each
+ * stride is 0 (one image for all frames) or >= n_pixels, anything else is rejected; a stride that comes with a NULL pointer is
+ * ignored.  d_out of tp_radial_evaluate(_zoom) is written with frame_stride (the n_pixels values of every frame only).  A
+ * tp_zoom_image must cover the frame (mesh_rows * box_size >= rows, mesh_cols * box_size >= frame_cols) or is rejected.
+ * d_ring_pixels holds pixel indices below n_pixels (not checked).  The
  * pixel mask (:89-97) is evaluated on d_frames; values are d_frames - d_square (float64) once a square (mesh) component of
  * a previous iteration exists, d_frames alone (float32 arithmetic, as numpy does it) when d_square is NULL.
  * tp_radial_zeropoint: d_zeropoint[k] = -min(values over the unmasked pixels) + 1.0 (:166-168); NaN when everything is
@@ -543,7 +575,12 @@ int tp_lightcurve_diagnostics(tp_ctx* ctx, int32_t n_targets, int32_t n_cad,
  *   d_stamps: int32 [n_targets][4] = (row_min, row_max, col_min, col_max) in CCD coordinates; every stamp must be
  *             desc->height x desc->width; pixels outside the frame become NaN;
  *   d_cube:   float32 cube with the layout of desc (n_cad == n_frames); the padding of the time axis (cadences n_cad ..
- *             t_pitch of every pixel) is written as zeros: the caller need not clear the cube.             */
+ *             t_pitch of every pixel) is written as zeros: the caller need not clear the cube.
+ *   Layout: row_pitch >= frame_cols and frame_stride >= frame_rows * row_pitch (else rejected); only the frame_rows x frame_cols
+ *   pixels of every frame are read -- d_frames may be a window of a larger stack (base pointer inside the allocation, row_pitch
+ *   its full width), and what lies beside the window never reaches a cube: a stamp pixel outside the window is NaN.  No alignment
+ *   of the base pointer or the pitch is assumed.  The same holds for tp_cut_stamps_multi / _masked (one geometry for all stacks)
+ *   and for d_full of tp_crop_sumimage (float64, row_pitch >= frame_cols).                                        */
 int tp_cut_stamps(tp_ctx* ctx, const float* d_frames, int32_t n_frames, int32_t frame_rows, int32_t frame_cols,
 	int64_t row_pitch, int64_t frame_stride, int32_t row_offset, int32_t col_offset,
 	const int32_t* d_stamps, const tp_cube_desc* desc, float* d_cube);
@@ -620,7 +657,8 @@ typedef struct tp_frames_stack {
 	const float* d_backgrounds_t;
 	int64_t t_pitch;
 } tp_frames_stack;
-/* [n_frames][n_pixels] (frame_stride elements from frame to frame) -> [n_pixels][t_pitch], cadences past n_frames zero */
+/* [n_frames][n_pixels] (frame_stride >= n_pixels elements from frame to frame, the elements past n_pixels never read) ->
+ * d_out dense [n_pixels][t_pitch], t_pitch >= n_frames, cadences n_frames .. t_pitch of every pixel written as zeros */
 int tp_frames_transpose(tp_ctx* ctx, const float* d_frames, int32_t n_frames, int64_t n_pixels, int64_t frame_stride, float* d_out, int64_t t_pitch);
 /* tp_aperture_extract (A6, photometry.py:172-201) with the pixels' series taken from the time-major stacks of a region: stamp
  * pixel (r, c) of target t is row (d_stamps[4 t] - stack_row0 + r) * stack_cols + d_stamps[4 t + 2] - stack_col0 + c of the

@@ -557,6 +557,12 @@ static int background_mesh_launch(tp_ctx* ctx, const char* who, const float* d_f
 	TP_REQUIRE(ctx, d_frames && d_mesh && d_nmasked, "tp_background_mesh: null pointer");
 	TP_REQUIRE(ctx, n_frames >= 0 && frame_rows > 0 && frame_cols > 0 && row_pitch >= frame_cols && frame_stride >= (int64_t)frame_rows * row_pitch, "tp_background_mesh: bad frame geometry");
 	TP_REQUIRE(ctx, box_size >= 1 && box_size * box_size <= kMeshKeys, "tp_background_mesh: box_size must be 1..64");
+	// the exclude and subtract images are dense [frame_rows][frame_cols] whatever the frames' row_pitch: one for all frames or one per frame
+	const int64_t n_dense = (int64_t)frame_rows * frame_cols;
+	TP_REQUIRE(ctx, d_exclude == nullptr || exclude_frame_stride == 0 || exclude_frame_stride >= n_dense,
+		"tp_background_mesh: exclude_frame_stride must be 0 or at least frame_rows * frame_cols");
+	TP_REQUIRE(ctx, d_subtract == nullptr || subtract_frame_stride == 0 || subtract_frame_stride >= n_dense,
+		"tp_background_mesh: subtract_frame_stride must be 0 or at least frame_rows * frame_cols");
 	if (n_frames == 0) return TP_OK;
 	MeshArgs a;
 	a.frames = d_frames; a.n_rows = frame_rows; a.n_cols = frame_cols; a.row_pitch = row_pitch; a.frame_stride = frame_stride;
@@ -633,6 +639,9 @@ extern "C" int tp_background_zoom(tp_ctx* ctx, const double* d_coef, const doubl
 	TP_API_BEGIN
 	TP_REQUIRE(ctx, d_coef && d_vmin && d_vmax && d_background, "tp_background_zoom: null pointer");
 	TP_REQUIRE(ctx, mesh_rows > 0 && mesh_cols > 0 && box_size > 0 && frame_rows > 0 && frame_cols > 0 && row_pitch >= frame_cols, "tp_background_zoom: bad geometry");
+	TP_REQUIRE(ctx, frame_stride >= (int64_t)frame_rows * row_pitch, "tp_background_zoom: frame_stride below frame_rows * row_pitch");
+	// (the spline indices are reflected once: a mesh that does not reach the last pixel would be read beyond its end)
+	TP_REQUIRE(ctx, (int64_t)mesh_rows * box_size >= frame_rows && (int64_t)mesh_cols * box_size >= frame_cols, "tp_background_zoom: the mesh does not cover the frame");
 	TP_REQUIRE(ctx, frame_rows <= 65535 && n_frames <= 65535, "tp_background_zoom: too many rows / frames for one launch");
 	if (n_frames == 0) return TP_OK;
 	dim3 grid((unsigned)((frame_cols + 255) / 256), (unsigned)((frame_rows + kZoomRows - 1) / kZoomRows), (unsigned)n_frames);

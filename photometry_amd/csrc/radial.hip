@@ -626,8 +626,15 @@ static bool radial_image_ok(int32_t n_frames, int64_t n_pixels, int64_t frame_st
 	return n_frames >= 0 && n_frames <= 65535 && n_pixels > 0 && n_pixels <= 0x7fffffff && frame_stride >= n_pixels;
 }
 
-static bool zoom_image_ok(const tp_zoom_image* z) {
-	return z && z->d_coef && z->d_vmin && z->d_vmax && z->mesh_rows > 0 && z->mesh_cols > 0 && z->box_size > 0 && z->frame_cols > 0;
+// (the spline indices are reflected once: the mesh must reach the last row and column of the frame it is evaluated on)
+static bool zoom_image_ok(const tp_zoom_image* z, int64_t n_pixels) {
+	return z && z->d_coef && z->d_vmin && z->d_vmax && z->mesh_rows > 0 && z->mesh_cols > 0 && z->box_size > 0 && z->frame_cols > 0
+		&& n_pixels % z->frame_cols == 0 && (int64_t)z->mesh_cols * z->box_size >= z->frame_cols
+		&& (int64_t)z->mesh_rows * z->box_size >= n_pixels / z->frame_cols;
+}
+// an optional image beside the frames, dense [n_pixels]: one for all frames (stride 0) or one per frame
+static bool side_image_ok(const void* d_image, int64_t stride, int64_t n_pixels) {
+	return d_image == nullptr || stride == 0 || stride >= n_pixels;
 }
 static ZoomImage zoom_of(const tp_zoom_image* z) {
 	return ZoomImage{z->d_coef, z->d_vmin, z->d_vmax, z->mesh_rows, z->mesh_cols, z->box_size, z->frame_cols};
@@ -640,7 +647,9 @@ static int radial_zeropoint_launch(tp_ctx* ctx, const float* d_frames, int32_t n
 	TP_REQUIRE(ctx, d_frames && d_partial && d_zeropoint, "tp_radial_zeropoint: null pointer");
 	TP_REQUIRE(ctx, radial_image_ok(n_frames, n_pixels, frame_stride), "tp_radial_zeropoint: bad frame geometry");
 	TP_REQUIRE(ctx, n_partial >= 1 && n_partial <= 65535, "tp_radial_zeropoint: n_partial must be 1..65535");
-	TP_REQUIRE(ctx, zoom == nullptr || (zoom_image_ok(zoom) && d_square == nullptr && n_pixels % zoom->frame_cols == 0), "tp_radial_zeropoint_zoom: bad mesh image");
+	TP_REQUIRE(ctx, zoom == nullptr || (zoom_image_ok(zoom, n_pixels) && d_square == nullptr), "tp_radial_zeropoint_zoom: bad mesh image");
+	TP_REQUIRE(ctx, side_image_ok(d_square, square_frame_stride, n_pixels), "tp_radial_zeropoint: square_frame_stride must be 0 or at least n_pixels");
+	TP_REQUIRE(ctx, side_image_ok(d_exclude, exclude_frame_stride, n_pixels), "tp_radial_zeropoint: exclude_frame_stride must be 0 or at least n_pixels");
 	if (n_frames == 0) return TP_OK;
 	RadialImage img{d_frames, frame_stride, d_square, square_frame_stride, zoom != nullptr, zoom ? zoom_of(zoom) : ZoomImage{}, d_exclude, exclude_frame_stride, (float)flux_cutoff};
 	int n_used = n_partial;
@@ -695,7 +704,9 @@ static int radial_ring_launch(tp_ctx* ctx, const float* d_frames, int32_t n_fram
 	TP_REQUIRE(ctx, d_frames && d_zeropoint && d_ring_pixels && d_ring_offsets && d_scratch && d_modes, "tp_radial_ring_modes: null pointer");
 	TP_REQUIRE(ctx, radial_image_ok(n_frames, n_pixels, frame_stride), "tp_radial_ring_modes: bad frame geometry");
 	TP_REQUIRE(ctx, n_rings >= 0 && n_rings <= 65535 && n_ring_pixels >= 0, "tp_radial_ring_modes: bad ring list");
-	TP_REQUIRE(ctx, zoom == nullptr || (zoom_image_ok(zoom) && d_square == nullptr && n_pixels % zoom->frame_cols == 0), "tp_radial_ring_modes_zoom: bad mesh image");
+	TP_REQUIRE(ctx, zoom == nullptr || (zoom_image_ok(zoom, n_pixels) && d_square == nullptr), "tp_radial_ring_modes_zoom: bad mesh image");
+	TP_REQUIRE(ctx, side_image_ok(d_square, square_frame_stride, n_pixels), "tp_radial_ring_modes: square_frame_stride must be 0 or at least n_pixels");
+	TP_REQUIRE(ctx, side_image_ok(d_exclude, exclude_frame_stride, n_pixels), "tp_radial_ring_modes: exclude_frame_stride must be 0 or at least n_pixels");
 	if (n_frames == 0 || n_rings == 0) return TP_OK;
 	RingArgs a;
 	a.img = RadialImage{d_frames, frame_stride, d_square, square_frame_stride, zoom != nullptr, zoom ? zoom_of(zoom) : ZoomImage{}, d_exclude, exclude_frame_stride, (float)flux_cutoff};
@@ -742,7 +753,8 @@ static int radial_evaluate_launch(tp_ctx* ctx, int32_t n_frames, int32_t frame_r
 	TP_REQUIRE(ctx, n_frames >= 0 && n_frames <= 65535 && frame_rows > 0 && frame_rows <= 65535 && frame_cols > 0
 		&& frame_stride >= (int64_t)frame_rows * frame_cols, "tp_radial_evaluate: bad frame geometry");
 	TP_REQUIRE(ctx, max_knots >= 8 && max_knots <= 1024, "tp_radial_evaluate: max_knots must be 8..1024");
-	TP_REQUIRE(ctx, zoom == nullptr || (zoom_image_ok(zoom) && d_add == nullptr && zoom->frame_cols == frame_cols), "tp_radial_evaluate_zoom: bad mesh image");
+	TP_REQUIRE(ctx, zoom == nullptr || (zoom_image_ok(zoom, (int64_t)frame_rows * frame_cols) && d_add == nullptr && zoom->frame_cols == frame_cols), "tp_radial_evaluate_zoom: bad mesh image");
+	TP_REQUIRE(ctx, side_image_ok(d_add, add_frame_stride, (int64_t)frame_rows * frame_cols), "tp_radial_evaluate: add_frame_stride must be 0 or at least frame_rows * frame_cols");
 	if (n_frames == 0) return TP_OK;
 	EvalArgs a;
 	a.n_rows = frame_rows; a.n_cols = frame_cols; a.frame_stride = frame_stride;
