@@ -732,6 +732,35 @@ int tp_motion_ecc(tp_ctx* ctx, const float* d_template, const float* d_frames, i
 	int64_t frame_stride, int32_t n_params, int32_t max_iter, double eps, int64_t chunk_bytes, double* d_warp, double* d_rho,
 	int32_t* d_iters, int32_t* d_status);
 
+/* A loaded series of kernels applied to many positions at many times (ImageMovementKernel.load_series / interpolate / jitter,
+ * image_motion.py:259-421).  The series: n_series (>= 2) finite times d_times float64, ascending, their finite kernels d_kernels
+ * [n_series][P] float64 (P = 0, 2, 3, 6 for TP_MOTION_UNCHANGED, _TRANSLATION, _EUCLIDIAN, _AFFINE) and the fill kernels
+ * d_fill_first / d_fill_last [P]: the first and last kernels of the series as given, finite or not.  d_query: n_times float64
+ * times.  With P = 0 the three kernel pointers are not read.
+ * tp_motion_interpolate: d_out [n_times][P] = scipy's interp1d(d_times, d_kernels, axis=0, assume_sorted=True,
+ *   bounds_error=False, fill_value=(first, last))(d_query), operation for operation and without FMA contraction: hi =
+ *   clip(searchsorted(x, t), 1, n_series - 1), lo = hi - 1, slope = (y_hi - y_lo) / (x_hi - x_lo), y = slope * (t - x_lo) + y_lo,
+ *   then t < x[0] -> first, t > x[-1] -> last; a NaN time gives NaN.  Bit-defined.
+ * tp_motion_star_positions: n positions d_xy [n][2] float64 (CCD column, row).  Per query time the 2 x 3 matrix M of
+ *   apply_kernel (image_motion.py:113-179) is formed once; jitter = M [x y 1] - [x y] (a translation's shift and an unchanged
+ *   field's zero are copies).  Position i with d_out_index[i] = o in [0, n_out) gets d_pos_col[o * pos_pitch + k] =
+ *   float64(float32(d_base_col[i] + jitter column)) and the same for rows (the base columns are the float32 stamp coordinates);
+ *   d_jitter (may be NULL) [n][n_times][2] float64 gets the jitter itself.  With n_out = 0 the base, index and position pointers
+ *   are not read.  single = 1: the arithmetic apply_kernel does for float32 positions -- the product is rounded to float32 before
+ *   the float32 position is subtracted and the base is added in float32 -- which is what catalog_attime (BasePhotometry.py:
+ *   1246-1256) gets for the float32 catalogue columns; d_jitter then holds float32 values.  A position's output does not depend
+ *   on the other positions of the call.                                                                                        */
+#define TP_MOTION_UNCHANGED 0
+#define TP_MOTION_TRANSLATION 1
+#define TP_MOTION_EUCLIDIAN 2
+#define TP_MOTION_AFFINE 3
+int tp_motion_interpolate(tp_ctx* ctx, int32_t warpmode, int32_t n_series, const double* d_times, const double* d_kernels,
+	const double* d_fill_first, const double* d_fill_last, int32_t n_times, const double* d_query, double* d_out);
+int tp_motion_star_positions(tp_ctx* ctx, int32_t warpmode, int32_t n_series, const double* d_times, const double* d_kernels,
+	const double* d_fill_first, const double* d_fill_last, int32_t n_times, const double* d_query, int64_t n, const double* d_xy,
+	int32_t single, const float* d_base_col, const float* d_base_row, const int64_t* d_out_index, int64_t n_out, double* d_pos_col,
+	double* d_pos_row, int64_t pos_pitch, double* d_jitter);
+
 /* ---- Halo photometry (photometry/halo/halo_photometry.py) -------------------------------------------------------------
  * The TV-min pixel weights that halo_photometry.py:179-196 obtains from halophot's do_lc (settings of :86-97: objective 'tv',
  * sub 1, thresh -1, no sigma clipping, uniform start), defined in DESIGN.md ("Halo") and tests/halo_common.py.  One problem is

@@ -179,6 +179,9 @@ SIGNATURES = {
 	'tp_frames_release': (c_int, [c_void_p]),
 	'tp_motion_prepare': (c_int, [c_void_p, _p, c_int32, c_int32, c_int32, c_int64, _p]),
 	'tp_motion_ecc': (c_int, [c_void_p, _p, _p, c_int32, c_int32, c_int32, c_int64, c_int32, c_int32, c_double, c_int64, _p, _p, _p, _p]),
+	'tp_motion_interpolate': (c_int, [c_void_p, c_int32, c_int32, _p, _p, _p, _p, c_int32, _p, _p]),
+	'tp_motion_star_positions': (c_int, [c_void_p, c_int32, c_int32, _p, _p, _p, _p, c_int32, _p, c_int64, _p, c_int32, _p, _p, _p, c_int64, _p, _p,
+		c_int64, _p]),
 	'tp_halo_tvmin': (c_int, [c_void_p, c_int32, _p, _p, _p, _p, _p, c_int32, c_int32, c_double, c_double, _p, _p, _p, _p, _p]),
 	'tp_halo_objective': (c_int, [c_void_p, c_int32, _p, _p, _p, _p, _p, _p, _p, _p]),
 	'tp_halo_select_stack': (c_int, [c_void_p, _p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, _p, c_int32, c_int32, _p, c_int32, _p, _p, c_int32,

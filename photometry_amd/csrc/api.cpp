@@ -66,6 +66,8 @@ static const char* const kKernelNames[TPK_COUNT] = {
 	"tp_wcs_footprint_kernel",
 	"tp_wcs_widen_kernel",
 	"tp_wcs_positions_kernel",
+	"tp_motion_interp_kernel",
+	"tp_motion_positions_kernel",
 };
 
 extern "C" {

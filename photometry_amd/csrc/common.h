@@ -64,6 +64,8 @@ enum tp_kernel_id {
 	TPK_WCS_FOOTPRINT,
 	TPK_WCS_WIDEN,
 	TPK_WCS_POSITIONS,
+	TPK_MOTION_INTERP,
+	TPK_MOTION_POSITIONS,
 	TPK_COUNT
 };
 

@@ -13,6 +13,11 @@
 //   the raw moments N, sum I, I^2, T, T^2, IT, J_k, J_k I, J_k T, J_k J_l) plus one wave per frame that sums the partials in a fixed
 //   order and does the P x P algebra (rho, lambda, delta p, the warp update, the frame's state).  No float atomics: the series is
 //   bit-reproducible.  A frame that has stopped is frozen: the tile pass and the finish skip it.
+// tp_motion_interpolate / tp_motion_star_positions: a loaded series of translation / euclidian / affine kernels
+//   (ImageMovementKernel.load_series, image_motion.py:259-335) applied to many positions at many times (interpolate / jitter,
+//   :338-421).  One thread per query time evaluates scipy's linear interp1d operation for operation (the file is compiled
+//   without contraction into FMAs, so the kernels are bit-defined) and forms the cadence's 2 x 3 matrix once; the star pass
+//   streams over (stars, tile of cadences) with the tile's matrices in registers, cadence the fast axis of every store.
 #include "common.h"
 #include <cmath>
 #include <vector>
@@ -459,6 +464,147 @@ int ecc_chunks(tp_ctx* ctx, const float* d_tmpl_blur, const float* d_frames, int
 	return TP_OK;
 }
 
+// ---- a loaded series applied to positions ---------------------------------------------------------------------------------
+
+constexpr int kPosStars = 16;   // stars per block of the star pass: the tile's matrices are read once for all of them
+
+// numpy's ordering of searchsorted: NaN sorts behind every number
+__device__ inline bool sorts_before(double a, double b) { return a < b || (b != b && a == a); }
+
+// One thread per query time.  kernels (may be NULL) [n_times][P]: scipy's interp1d(times, series, axis=0, assume_sorted=True,
+// bounds_error=False, fill_value=(first, last)), _call_linear and _evaluate operation for operation.  mats (may be NULL)
+// [6][n_times]: the rows m00 m01 m02 m10 m11 m12 of the warp of image_motion.py:147-177.
+template <int P>
+__global__ __launch_bounds__(kThreads) void tp_motion_interp_kernel(int n_series, const double* __restrict__ times,
+	const double* __restrict__ series, const double* __restrict__ first, const double* __restrict__ last, int n_times,
+	const double* __restrict__ query, double* __restrict__ kernels, double* __restrict__ mats)
+{
+	const int k = blockIdx.x * kThreads + threadIdx.x;
+	if (k >= n_times) return;
+	const double t = query[k];
+	// searchsorted(times, t) (side 'left'), clipped to [1, n_series - 1]
+	int lo = 0, hi = n_series;
+	while (lo < hi) {
+		const int mid = (lo + hi) >> 1;
+		if (sorts_before(times[mid], t)) lo = mid + 1; else hi = mid;
+	}
+	hi = min(max(lo, 1), n_series - 1);
+	lo = hi - 1;
+	const double x_lo = times[lo], x_hi = times[hi];
+	const bool below = t < times[0], above = t > times[n_series - 1];
+	double v[P > 0 ? P : 1];
+#pragma unroll
+	for (int p = 0; p < P; p++) {
+		const double y_lo = series[(int64_t)lo * P + p], y_hi = series[(int64_t)hi * P + p];
+		const double slope = (y_hi - y_lo) / (x_hi - x_lo);
+		double y = slope * (t - x_lo) + y_lo;
+		if (below) y = first[p];
+		if (above) y = last[p];
+		v[p] = y;
+		if (kernels) kernels[(int64_t)k * P + p] = y;
+	}
+	if (!mats) return;
+	double m[6] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0};
+	if constexpr (P == 2) {
+		m[2] = v[0]; m[5] = v[1];
+	} else if constexpr (P == 3) {
+		const double c = cos(v[2]), s = sin(v[2]);
+		m[0] = c; m[1] = -s; m[2] = v[0]; m[3] = s; m[4] = c; m[5] = v[1];
+	} else if constexpr (P == 6) {
+#pragma unroll
+		for (int j = 0; j < 6; j++) m[j] = v[j];
+	}
+#pragma unroll
+	for (int j = 0; j < 6; j++) mats[(int64_t)j * n_times + k] = m[j];
+}
+
+struct StarArgs {
+	int mode, single, n_times;
+	const double* mats;        // [6][n_times]
+	int64_t n;
+	const double* xy;          // [n][2] column, row
+	const float *base_col, *base_row;
+	const int64_t* out_index;
+	int64_t n_out;
+	double *pos_col, *pos_row;
+	int64_t pitch;
+	double* jitter;            // [n][n_times][2] or NULL
+	int tiles;
+};
+
+// block = (chunk of kPosStars stars, tile of kThreads cadences); thread = cadence.  jitter = M [x y 1] - [x y], the products
+// summed in the order of a row-times-vector loop; a translation's shift and an unchanged field's zero are copies.  single: the
+// arithmetic apply_kernel does for float32 positions (np.empty_like(xy): the product is stored as float32, the position
+// subtracted and the base added in float32 -- what catalog_attime gets for the float32 catalogue, BasePhotometry.py:1246-1256).
+__global__ __launch_bounds__(kThreads) void tp_motion_positions_kernel(StarArgs A)
+{
+	const int tile = blockIdx.x % A.tiles;
+	const int64_t i0 = (int64_t)(blockIdx.x / A.tiles) * kPosStars;
+	const int k = tile * kThreads + threadIdx.x;
+	if (k >= A.n_times) return;
+	double m[6];
+#pragma unroll
+	for (int j = 0; j < 6; j++) m[j] = A.mats[(int64_t)j * A.n_times + k];
+	const int64_t i1 = min(i0 + kPosStars, A.n);
+	for (int64_t i = i0; i < i1; i++) {
+		const double x = A.xy[2 * i], y = A.xy[2 * i + 1];
+		double jx, jy;
+		if (A.mode == TP_MOTION_UNCHANGED) {
+			jx = jy = 0.0;
+		} else if (A.mode == TP_MOTION_TRANSLATION) {
+			jx = m[2]; jy = m[5];
+			if (A.single) { jx = (double)(float)jx; jy = (double)(float)jy; }
+		} else {
+			const double dx = m[0] * x + m[1] * y + m[2] * 1.0;
+			const double dy = m[3] * x + m[4] * y + m[5] * 1.0;
+			if (A.single) {
+				jx = (double)((float)dx - (float)x);
+				jy = (double)((float)dy - (float)y);
+			} else {
+				jx = dx - x;
+				jy = dy - y;
+			}
+		}
+		if (A.jitter) {
+			double* j = A.jitter + ((int64_t)i * A.n_times + k) * 2;
+			j[0] = jx;
+			j[1] = jy;
+		}
+		const int64_t o = A.n_out > 0 ? A.out_index[i] : -1;
+		if (o >= 0 && o < A.n_out) {
+			const float bc = A.base_col[i], br = A.base_row[i];
+			if (A.single) {
+				A.pos_col[o * A.pitch + k] = (double)(bc + (float)jx);
+				A.pos_row[o * A.pitch + k] = (double)(br + (float)jy);
+			} else {
+				A.pos_col[o * A.pitch + k] = (double)(float)((double)bc + jx);
+				A.pos_row[o * A.pitch + k] = (double)(float)((double)br + jy);
+			}
+		}
+	}
+}
+
+inline int warp_params(int32_t mode) {
+	return mode == TP_MOTION_UNCHANGED ? 0 : (mode == TP_MOTION_TRANSLATION ? 2 : (mode == TP_MOTION_EUCLIDIAN ? 3 : (mode == TP_MOTION_AFFINE ? 6 : -1)));
+}
+
+int launch_interp(tp_ctx* ctx, int32_t mode, int32_t n_series, const double* d_times, const double* d_series, const double* d_first,
+	const double* d_last, int32_t n_times, const double* d_query, double* d_kernels, double* d_mats)
+{
+	const dim3 grid((unsigned)((n_times + kThreads - 1) / kThreads)), block(kThreads);
+#define INTERP(P) TP_LAUNCH(ctx, TPK_MOTION_INTERP, tp_motion_interp_kernel<P>, grid, block, 0, (int)n_series, d_times, d_series, d_first, \
+	d_last, (int)n_times, d_query, d_kernels, d_mats)
+	switch (warp_params(mode)) {
+		case 0: INTERP(0); break;
+		case 2: INTERP(2); break;
+		case 3: INTERP(3); break;
+		default: INTERP(6); break;
+	}
+#undef INTERP
+	TP_LAUNCH_CHECK(ctx, "tp_motion_interp_kernel");
+	return TP_OK;
+}
+
 } // namespace
 
 extern "C" int tp_motion_prepare(tp_ctx* ctx, const float* d_frames, int32_t n_frames, int32_t frame_rows, int32_t frame_cols, int64_t frame_stride,
@@ -530,6 +676,53 @@ extern "C" int tp_motion_ecc(tp_ctx* ctx, const float* d_template, const float* 
 				(double*)partial, (int32_t*)list, d_warp, d_rho, (double*)last, d_iters, d_status);
 	}
 	for (void* p : {tmpl, blur, partial, list, last}) if (p) tp_free(ctx, p);
+	return rc;
+	TP_API_END(ctx)
+}
+
+extern "C" int tp_motion_interpolate(tp_ctx* ctx, int32_t warpmode, int32_t n_series, const double* d_times, const double* d_kernels,
+	const double* d_fill_first, const double* d_fill_last, int32_t n_times, const double* d_query, double* d_out)
+{
+	TP_CHECK_CTX(ctx);
+	TP_API_BEGIN
+	const int P = warp_params(warpmode);
+	TP_REQUIRE(ctx, P >= 0, "tp_motion_interpolate: warpmode must be TP_MOTION_UNCHANGED, _TRANSLATION, _EUCLIDIAN or _AFFINE");
+	TP_REQUIRE(ctx, n_series >= 2 && n_times >= 0, "tp_motion_interpolate: a series of at least two kernels and n_times >= 0 expected");
+	if (n_times == 0 || P == 0) return TP_OK;
+	TP_REQUIRE(ctx, d_times && d_kernels && d_fill_first && d_fill_last && d_query && d_out, "tp_motion_interpolate: null pointer");
+	return launch_interp(ctx, warpmode, n_series, d_times, d_kernels, d_fill_first, d_fill_last, n_times, d_query, d_out, nullptr);
+	TP_API_END(ctx)
+}
+
+extern "C" int tp_motion_star_positions(tp_ctx* ctx, int32_t warpmode, int32_t n_series, const double* d_times, const double* d_kernels,
+	const double* d_fill_first, const double* d_fill_last, int32_t n_times, const double* d_query, int64_t n, const double* d_xy, int32_t single,
+	const float* d_base_col, const float* d_base_row, const int64_t* d_out_index, int64_t n_out, double* d_pos_col, double* d_pos_row,
+	int64_t pos_pitch, double* d_jitter)
+{
+	TP_CHECK_CTX(ctx);
+	TP_API_BEGIN
+	const int P = warp_params(warpmode);
+	TP_REQUIRE(ctx, P >= 0, "tp_motion_star_positions: warpmode must be TP_MOTION_UNCHANGED, _TRANSLATION, _EUCLIDIAN or _AFFINE");
+	TP_REQUIRE(ctx, n_series >= 2 && n_times >= 0 && n >= 0 && n_out >= 0 && pos_pitch >= n_times && (single == 0 || single == 1),
+		"tp_motion_star_positions: bad arguments (a series of at least two kernels, sizes >= 0, pos_pitch >= n_times expected)");
+	if (n_times == 0 || n == 0) return TP_OK;
+	TP_REQUIRE(ctx, d_times && d_query && d_xy && (P == 0 || (d_kernels && d_fill_first && d_fill_last))
+		&& (n_out == 0 || (d_base_col && d_base_row && d_out_index && d_pos_col && d_pos_row)), "tp_motion_star_positions: null pointer");
+	const int tiles = (n_times + kThreads - 1) / kThreads;
+	const int64_t blocks = ((n + kPosStars - 1) / kPosStars) * tiles;
+	TP_REQUIRE(ctx, blocks <= 0x7fffffff, "tp_motion_star_positions: too many positions times cadences for one launch");
+	double* mats = nullptr;
+	int rc = tp_malloc(ctx, (uint64_t)n_times * 6 * sizeof(double), (void**)&mats);
+	if (rc != TP_OK) return rc;
+	rc = launch_interp(ctx, warpmode, n_series, d_times, d_kernels, d_fill_first, d_fill_last, n_times, d_query, nullptr, mats);
+	if (rc == TP_OK) {
+		StarArgs A{(int)warpmode, (int)single, (int)n_times, mats, n, d_xy, d_base_col, d_base_row, d_out_index, n_out, d_pos_col, d_pos_row, pos_pitch,
+			d_jitter, tiles};
+		TP_LAUNCH(ctx, TPK_MOTION_POSITIONS, tp_motion_positions_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, A);
+		hipError_t e = hipGetLastError();
+		if (e != hipSuccess) rc = ctx->fail(TP_ERR_HIP, "tp_motion_positions_kernel", e);
+	}
+	tp_free(ctx, mats);
 	return rc;
 	TP_API_END(ctx)
 }

@@ -13,6 +13,11 @@ The prepare stage of the reference measures where the stars are at every cadence
 restatement the device is held to is ``tests/motion_common.py``; DESIGN.md section 9 lists the deliberate differences from
 OpenCV.
 
+A loaded series is applied to many positions on the device too: ``jitter_many`` (``tp_motion_interpolate`` /
+``tp_motion_star_positions``: scipy's interp1d bit for bit, one 2 x 3 matrix per cadence, a streaming pass over the positions), which
+``linpsf_frames`` uses for euclidian and affine kernels and ``tessphot_frames(movement=)`` for ``pos_corr``.  ``interpolate``,
+``jitter`` and ``apply_kernel`` stay the reference's host arithmetic.
+
 The ``'wcs'`` warpmode -- the reference's default whenever the FFIs carry per-frame WCS headers (BasePhotometry.py:1185-1221) --
 takes its kernels from TAN-SIP WCS headers through :mod:`photometry_amd.wcs` (csrc/wcs.hip) instead of astropy.wcs: with a
 ``wcs_ref`` (header string, card dict or :class:`~photometry_amd.wcs.TanSipWCS`), ``apply_kernel``, ``load_series``,
@@ -29,6 +34,9 @@ logger = logging.getLogger(__name__)
 
 #: per-frame states written by tp_motion_ecc
 STATUS_CONVERGED, STATUS_CAP_REACHED, STATUS_FAILED_NAN, STATUS_FAILED_LAMBDA = 1, 2, 3, 4
+
+#: warpmode -> the TP_MOTION_* code of tp_motion_interpolate / tp_motion_star_positions ('wcs' has its own entries, csrc/wcs.hip)
+WARPMODE_CODE = {'unchanged': 0, 'translation': 1, 'euclidian': 2, 'affine': 3}
 
 _WCS_MESSAGE = "warpmode 'wcs' needs astropy.wcs, which this build does not provide"
 
@@ -167,6 +175,8 @@ class MovementKernel(object):
 		self.ctx = ctx
 		self._template = None
 		self._interpolator = None
+		self._series_good = None
+		self._d_loaded = None
 
 	def __call__(self, *args, **kwargs):
 		return self.apply_kernel(*args, **kwargs)
@@ -239,6 +249,9 @@ class MovementKernel(object):
 		# the fill values are the first and last kernels of the series as given, finite or not
 		self._interpolator = interp1d(times[good], kernels[good, :], axis=0, assume_sorted=True, bounds_error=False,
 			fill_value=(kernels[0, :], kernels[-1, :]))
+		# what the device entries read: the finite series and the two fill kernels in float64 (uploaded on first use, device_series)
+		self._series_good = tuple(np.ascontiguousarray(a, dtype='float64') for a in (times[good], kernels[good, :], kernels[0, :], kernels[-1, :]))
+		self._d_loaded = None
 
 	def interpolate(self, time, xy):
 		"""The change of the positions ``xy`` at ``time`` from the loaded series (image_motion.py:338-399)."""
@@ -268,6 +281,86 @@ class MovementKernel(object):
 		for k, t in enumerate(time):
 			out[k, :] = self.interpolate(t, xy)
 		return out
+
+	def device_series(self, ctx=None):
+		"""
+		The loaded series on the device, uploaded once per ``load_series``: ``(code, S, d_times, d_kernels, d_first, d_last)``, the
+		leading arguments of ``tp_motion_interpolate`` / ``tp_motion_star_positions`` (finite series, fill kernels as given).
+		"""
+		if self.warpmode not in WARPMODE_CODE:
+			raise ValueError(f"no kernel series on the device for warpmode '{self.warpmode}'")
+		if self._series_good is None:
+			raise ValueError("Interpolator is not defined. ")
+		ctx = self._context() if ctx is None else ctx
+		if self._d_loaded is None or self._d_loaded[0] is not ctx:
+			# (an 'unchanged' series has no parameters: one unread value stands in for the empty arrays)
+			self._d_loaded = (ctx,) + tuple(ctx.array(a if a.size else np.zeros(1)) for a in self._series_good)
+		return (WARPMODE_CODE[self.warpmode], len(self._series_good[0])) + self._d_loaded[1:]
+
+	def interpolate_many(self, time, ctx=None):
+		"""``(T, n_params)`` float64 kernels of the loaded series at the timestamps ``time`` (``tp_motion_interpolate``): the values
+		``interpolate`` applies, bit for bit."""
+		ctx = self._context() if ctx is None else ctx
+		code, S, d_t, d_k, d_f, d_l = self.device_series(ctx)
+		time = np.ascontiguousarray(np.atleast_1d(time), dtype='float64')
+		T = len(time)
+		out = ctx.empty((max(T, 1), max(self.n_params, 1)), 'float64')
+		d_q = ctx.array(time)
+		ctx._check(ctx.lib.tp_motion_interpolate(ctx.handle, code, S, d_t.ptr, d_k.ptr, d_f.ptr, d_l.ptr, T, d_q.ptr, out.ptr))
+		return out.to_host()[:T, :self.n_params]
+
+	def star_positions(self, time, xy, base_col=None, base_row=None, out_index=None, n_out=0, pitch=None, single=False, want_jitter=False,
+		ctx=None, pos=None):
+		"""
+		``tp_motion_star_positions``: the positions ``xy`` ``(n, 2)`` (CCD column, row) under the loaded series at the timestamps
+		``time``.  Returns ``(pos_col, pos_row, jitter)``: float64 DeviceArrays ``(n_out, pitch)`` holding
+		float64(float32(base + jitter)) for the rows with ``out_index >= 0`` (None with ``n_out = 0``) and, with ``want_jitter``, the
+		float64 jitter ``(n, T, 2)`` (else None).  ``single``: the float32 arithmetic ``apply_kernel`` does for float32 positions --
+		what ``catalog_attime`` computes from the float32 catalogue.  ``pos``: a pair of DeviceArrays to write into instead of new ones.
+		"""
+		ctx = self._context() if ctx is None else ctx
+		code, S, d_t, d_k, d_f, d_l = self.device_series(ctx)
+		time = np.ascontiguousarray(np.atleast_1d(time), dtype='float64')
+		xy = np.ascontiguousarray(xy, dtype='float64').reshape(-1, 2)
+		n, T = len(xy), len(time)
+		pitch = max(T, 1) if pitch is None else int(pitch)
+		n_out = int(n_out)
+		keep = [ctx.array(time), ctx.array(xy)]
+		p_bc = p_br = p_oi = p_pc = p_pr = p_j = None
+		pos_col = pos_row = jit = None
+		if n_out > 0:
+			out_index = np.ascontiguousarray(out_index, dtype='int64')
+			if len(out_index) != n or np.any(out_index >= n_out):
+				raise ValueError("out_index: one entry < n_out per position expected")
+			base_col, base_row = np.ascontiguousarray(base_col, dtype='float32'), np.ascontiguousarray(base_row, dtype='float32')
+			if base_col.shape != (n,) or base_row.shape != (n,):
+				raise ValueError("base_col / base_row: one float32 value per position expected")
+			if pos is not None and any(tuple(a.shape) != (n_out, pitch) or np.dtype(a.dtype) != np.dtype('float64') for a in pos):
+				raise ValueError("pos: two float64 DeviceArrays (n_out, pitch) expected")
+			keep += [ctx.array(base_col), ctx.array(base_row), ctx.array(out_index)]
+			p_bc, p_br, p_oi = keep[2].ptr, keep[3].ptr, keep[4].ptr
+			pos_col, pos_row = pos if pos is not None else (ctx.empty((n_out, pitch), 'float64'), ctx.empty((n_out, pitch), 'float64'))
+			p_pc, p_pr = pos_col.ptr, pos_row.ptr
+		if want_jitter:
+			jit = ctx.empty((max(n, 1), max(T, 1), 2), 'float64')
+			p_j = jit.ptr
+		ctx._check(ctx.lib.tp_motion_star_positions(ctx.handle, code, S, d_t.ptr, d_k.ptr, d_f.ptr, d_l.ptr, T, keep[0].ptr, n, keep[1].ptr, int(bool(single)),
+			p_bc, p_br, p_oi, n_out, p_pc, p_pr, pitch, p_j))
+		return pos_col, pos_row, jit
+
+	def jitter_many(self, time, columns, rows):
+		"""
+		``jitter(time, column, row)`` of many positions at once: a float64 DeviceArray ``(N, T, 2)`` of the changes in column and row
+		(``tp_motion_star_positions``; for ``'wcs'`` the device path of ``jitter`` with every position a batch of its own).
+		"""
+		time = np.asarray(time, dtype='float64')
+		xy = np.column_stack((np.asarray(columns, dtype='float64').ravel(), np.asarray(rows, dtype='float64').ravel()))
+		if self.warpmode == 'wcs':
+			return self._context().array(self._wcs_jitter_many(time, xy))
+		if len(xy) == 0 or len(time) == 0:
+			self.device_series()
+			return self._context().zeros((len(xy), len(time), 2), 'float64')
+		return self.star_positions(time, xy, want_jitter=True)[2]
 
 
 	# -- warpmode 'wcs' ---------------------------------------------------------------------------------------------------
@@ -347,6 +440,23 @@ class MovementKernel(object):
 		t1 = st[k1]
 		t2 = np.where(k2 >= 0, st[np.maximum(k2, 0)], t1)
 		return k1, k2, t2 - t1, t - t1
+
+	def _wcs_jitter_many(self, time, xy):
+		"""(N, T, 2): ``_wcs_jitter`` of every position, each a batch of its own (the iteration's stopping test is taken per batch)."""
+		self._wcs_needs_series()
+		from . import wcs as wcsmod
+		k1, k2, dt, dx = self._wcs_frame_pairs(time)
+		ctx = self._context()
+		n = len(xy)
+		d_cos = wcsmod.world_directions(ctx, self.wcs_ref, xy)
+		pix, _, _ = wcsmod.world2pix_frames(ctx, self._d_series, len(self.series_kernels), d_cos, n, np.arange(n + 1, dtype='int64'), 0, 1, 1e-4, 50)
+		j = np.moveaxis(pix - xy[None], 0, 1)    # (N, F, 2)
+		out = j[:, k1].copy()
+		two = k2 >= 0
+		if np.any(two):
+			j1, j2 = j[:, k1[two]], j[:, k2[two]]
+			out[:, two] = (j2 - j1) / dt[None, two, None] * dx[None, two, None] + j1
+		return out
 
 	def _wcs_jitter(self, time, xy):
 		self._wcs_needs_series()

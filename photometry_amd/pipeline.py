@@ -910,26 +910,31 @@ def linpsf_frames(ctx, stack, targets, catalog, time, quality, prf_model, jitter
 	the plugin does (:93-104), their positions at every cadence = catalogue position + ``jitter[k]`` (``(T, 2)`` column / row
 	shifts: what ``catalog_attime`` returns for a translation), one ``tp_linpsf_prf`` + ``tp_linpsf_fit`` per group.
 	Status and messages follow the plugin: ERROR "All target flux values are NaN.", WARNING "High contamination" above 0.1.
-	``movement``: a translation :class:`~photometry_amd.motion.MovementKernel` with a loaded series instead of ``jitter``: the
+	``movement``: a :class:`~photometry_amd.motion.MovementKernel` with a loaded series instead of ``jitter``.  For a translation the
 	shifts are ``movement.jitter(time - timecorr, 0.0, 0.0)`` (frames whose ECC failed come out interpolated, as ``load_series`` does).
-	A ``'wcs'`` kernel moves every star by its own shift: ``catalog_attime``'s ``interpolate`` over each stamp's catalogue as one
-	batch, formed on the device (``tp_wcs_star_positions``).
+	Under a ``'euclidian'`` or ``'affine'`` kernel every star moves by its own shift (``'unchanged'``: by none): ``catalog_attime``'s
+	``interpolate`` over each stamp's catalogue, formed on the device in its float32 arithmetic (``tp_motion_star_positions``).
+	A ``'wcs'`` kernel does the same through the headers, each stamp's catalogue one batch (``tp_wcs_star_positions``).
 	Returns a :class:`PSFFramesResult`.
 	"""
 	from . import psf as hpsf
 	n, T = len(targets['starid']), stack.n_cad
-	wcs_pairs = None
+	wcs_pairs = series_times = None
 	if movement is not None:
 		if jitter is not None:
 			raise ValueError("give either jitter or movement, not both")
-		if movement.warpmode not in ('translation', 'wcs'):
-			raise ValueError(f"linpsf_frames: translation or wcs movement kernels expected, got '{movement.warpmode}'")
+		if movement.warpmode not in ('unchanged', 'translation', 'euclidian', 'affine', 'wcs'):
+			raise ValueError(f"linpsf_frames: unknown warpmode '{movement.warpmode}'")
 		t = np.asarray(time, dtype='float64')
 		t = t if timecorr is None else t - np.asarray(timecorr, dtype='float64')
 		if movement.warpmode == 'wcs':
 			# per-star shifts: the frame pair of every cadence (interpolate's rule), the positions formed on the device per stamp
 			movement._wcs_needs_series()
 			wcs_pairs = movement._wcs_frame_pairs(t)
+		elif movement.warpmode != 'translation':
+			# per-star shifts from the loaded series (on the device once per load_series), the positions formed there per stamp group
+			movement.device_series(ctx)
+			series_times = t
 		else:
 			# float positions: jitter() builds its position array from them, and integer ones would truncate the shifts
 			jitter = movement.jitter(t, 0.0, 0.0)
@@ -950,7 +955,15 @@ def linpsf_frames(ctx, stack, targets, catalog, time, quality, prf_model, jitter
 		sel, star_offsets, target_index = hpsf.select_stars(cat, cat_offsets, np.asarray(targets['starid'], dtype='int64')[idx])
 		# positions = catalogue position + the cadence's shift, summed in float32 like the plugin's catalogue: formed on the device
 		# (on the host the two arrays -- 75 MB for 2 000 targets -- were most of this entry's time)
-		if wcs_pairs is None:
+		if series_times is not None:
+			# catalog_attime with a euclidian / affine kernel: interpolate() over the float32 catalogue positions, the float32 changes
+			# added to the float32 stamp columns (csrc/motion.hip, tp_motion_star_positions)
+			rows = np.arange(len(cat['row']))[sel]
+			out_index = np.full(len(cat['row']), -1, dtype='int64')
+			out_index[rows] = np.arange(len(rows))
+			pos_col, pos_row, _ = movement.star_positions(series_times, np.column_stack((cat['column'], cat['row'])), cat['column_stamp'],
+				cat['row_stamp'], out_index, len(rows), single=True, ctx=ctx)
+		elif wcs_pairs is None:
 			pos_row = engine.star_positions(ctx, ctx.array(np.ascontiguousarray(cat['row_stamp'][sel], dtype='float32')), d_jr)
 			pos_col = engine.star_positions(ctx, ctx.array(np.ascontiguousarray(cat['column_stamp'][sel], dtype='float32')), d_jc)
 		else:

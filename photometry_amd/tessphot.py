@@ -200,6 +200,9 @@ class BatchResults(object):
 		self.status = status
 		#: targets redone with Halo photometry (:meth:`switch_to_halo`): target -> row of ``self.halo``
 		self.halo, self.halo_rows, self._stamp = None, {}, None
+		#: ``(N, T, 2)`` changes in column and row of every target's position (``lightcurve['pos_corr']``, BasePhotometry.py:473) when
+		#: the entry was given movement kernels, else None
+		self.pos_corr = None
 
 	def __len__(self):
 		return len(self.frames)
@@ -253,6 +256,8 @@ class BatchResults(object):
 			mask = r['pixel_mask']
 			T = len(r['flux'])
 			lc = {'flux': r['flux'], 'flux_err': r['flux_err'], 'flux_background': np.zeros(T), 'pos_centroid': r['pos_centroid']}
+			if self.pos_corr is not None:
+				lc['pos_corr'] = self.pos_corr[i]
 			if r['skip_targets']:
 				details['skip_targets'] = r['skip_targets']
 			status = _diagnostics_into(details, r['diagnostics'], status)
@@ -300,6 +305,8 @@ class BatchResults(object):
 			if not np.isnan(r['contamination']):
 				details['contamination'] = r['contamination']
 			lc = {k: r[k] for k in ('flux', 'flux_err', 'flux_background', 'pos_centroid')}
+			if self.pos_corr is not None:
+				lc['pos_corr'] = self.pos_corr[int(i)]
 			if status in (STATUS.OK, STATUS.WARNING):
 				status = _diagnostics_into(details, r['diagnostics'], status)
 		return BatchResult(int(self.starid[int(i)]), status, 'aperture', details, lc, mask)
@@ -327,7 +334,16 @@ def _halo_switch_frames(ctx, stack, results, targets, catalog, time, quality, se
 	return results
 
 
-def tessphot_frames(ctx, stack, targets, catalog, time, quality, settings=None, sector=None, timecorr=None, cadenceno=None):
+def _pos_corr(ctx, movement, targets, time, timecorr):
+	"""``(N, T, 2)``: ``movement.jitter(time - timecorr, column, row)`` of every target (BasePhotometry.py:473), formed on the device."""
+	t = np.asarray(time, dtype='float64')
+	t = t if timecorr is None else t - np.asarray(timecorr, dtype='float64')
+	if movement.ctx is None:
+		movement.ctx = ctx
+	return movement.jitter_many(t, targets['column'], targets['row']).to_host()
+
+
+def tessphot_frames(ctx, stack, targets, catalog, time, quality, settings=None, sector=None, timecorr=None, cadenceno=None, movement=None):
 	"""
 	Aperture photometry of every target of a CCD region resident in HBM (:class:`photometry_amd.pipeline.FrameStack`), stamp
 	resizes included: what ``tessphot('aperture', ...)`` returns per target, for the whole batch in a few device passes.
@@ -335,20 +351,26 @@ def tessphot_frames(ctx, stack, targets, catalog, time, quality, settings=None, 
 	stamp resizes or left flux on a stuck edge (:func:`halo_switch_codes`) are redone with Halo photometry in one batched call
 	(``pipeline.halo_frames``; ``sector`` / ``timecorr`` / ``cadenceno`` as there) and their results are the Halo ones
 	(``method == 'halo'``, ``halo_weightmap``).
+	``movement``: a :class:`~photometry_amd.motion.MovementKernel` with a loaded series: ``BatchResults.pos_corr`` and every light
+	curve's ``'pos_corr'`` are then its jitter at the targets' positions at ``time - timecorr``, as the plugins write it.
 	Returns a :class:`BatchResults`: columns for the whole batch, one :class:`BatchResult` per target on demand (``results[i]``).
 	"""
 	from . import pipeline
 	res = pipeline.aperture_frames(ctx, stack, targets, catalog, time, quality, settings=settings)
-	return _halo_switch_frames(ctx, stack, BatchResults(res, targets['starid']), targets, catalog, time, quality, settings, sector, timecorr, cadenceno)
+	out = _halo_switch_frames(ctx, stack, BatchResults(res, targets['starid']), targets, catalog, time, quality, settings, sector, timecorr, cadenceno)
+	if movement is not None:
+		out.pos_corr = _pos_corr(ctx, movement, targets, time, timecorr)
+	return out
 
 
-def tessphot_frames_pipelined(ctx, stack, batches, catalog, time, quality, settings=None, in_flight=4, sector=None, timecorr=None, cadenceno=None):
+def tessphot_frames_pipelined(ctx, stack, batches, catalog, time, quality, settings=None, in_flight=4, sector=None, timecorr=None, cadenceno=None,
+	movement=None):
 	"""
 	:func:`tessphot_frames` over consecutive batches of targets of one CCD region -- what a run over a whole CCD does, a few
 	thousand targets per call -- with ``in_flight`` batches on the device at a time (``pipeline.aperture_frames_pipelined``: the
 	first round of a batch runs under the latency-bound resize rounds of the one before it).  ``batches``: an iterable of
 	``targets`` dicts; yields one :class:`BatchResults` per batch, in order, equal to what a call of its own returns (the switch to
-	Halo photometry included, applied to each batch before it is yielded).
+	Halo photometry included, applied to each batch before it is yielded; ``movement`` as there).
 	"""
 	from . import pipeline
 	batches = list(batches) if not hasattr(batches, '__next__') else batches
@@ -358,7 +380,10 @@ def tessphot_frames_pipelined(ctx, stack, batches, catalog, time, quality, setti
 			seen.append(t)
 			yield t
 	for k, res in enumerate(pipeline.aperture_frames_pipelined(ctx, stack, feed(), catalog, time, quality, settings=settings, in_flight=in_flight)):
-		yield _halo_switch_frames(ctx, stack, BatchResults(res, seen[k]['starid']), seen[k], catalog, time, quality, settings, sector, timecorr, cadenceno)
+		out = _halo_switch_frames(ctx, stack, BatchResults(res, seen[k]['starid']), seen[k], catalog, time, quality, settings, sector, timecorr, cadenceno)
+		if movement is not None:
+			out.pos_corr = _pos_corr(ctx, movement, seen[k], time, timecorr)
+		yield out
 
 
 def tessphot_batch(ctx, scene, cubes='host'):
