@@ -24,7 +24,7 @@
 // The normal equations (A^T A, A^T b) are accumulated on the fly; x = pinv(A^T A) A^T b via a cyclic
 // Jacobi eigen-decomposition with numpy's pinv cutoff (rcond = 1e-15 * largest singular value).
 //
-// Roofline: the FP64 pipe, not HBM: the image cube is read once (P*T*4 bytes per target).  Since round 3 the fit of a target
+// Roofline: the FP64 pipe, not HBM: the image cube is read once (P*T*4 bytes per target).  The fit of a target
 // with up to 4 stars runs on the matrix cores (linpsf_mfma.hip: ONE quartic spline per star and pixel over the knot intervals the
 // star visits, cadences in natural order); the kernels of this file plan it (tp_linpsf_plan_kernel), build its coefficients
 // (tp_linpsf_coef_kernel) and finalise it (tp_linpsf_finalize_m_kernel), and fit the targets that do not qualify on the vector
@@ -85,6 +85,56 @@ __global__ __launch_bounds__(256) void tp_linpsf_prf_fixed_kernel(const double* 
 	}
 }
 
+// ---- What the direct, the many-star and the finalise kernels share, each rule stated once.  (The build sets -ffp-contract=off:
+// an expression gives the same bits in a helper as written out in a kernel.)
+// pixel p of a cadence's frame (img: its pixel 0) as the fit sees it, lowered by `sub` where a.subtract is set; false unless it is
+// finite: good_pixels = isfinite(img) (linpsf_photometry.py:123)
+__device__ __forceinline__ bool fetch_pixel(const FitArgs& a, const float* img, int p, float sub, float& bf)
+{
+	bf = img[(int64_t)p * a.t_pitch];
+	if (a.subtract) bf = bf - sub;
+	return fabsf(bf) <= 3.402823466e+38f;
+}
+
+// psf.py:142  sqrt((j-col)^2 + (i-row)^2) < cutoff_radius  (a NaN position is never inside: zero column)
+__device__ __forceinline__ bool inside_cutoff(double dc, double dr, double cutoff) { return sqrt(dc * dc + dr * dr) < cutoff; }
+
+// the pixel-integrated PRF of a star at pixel (i, j) on the uniform grid: the table origin moved by 9 knots per pixel, clamped to the table
+__device__ __forceinline__ double star_pixel_uniform(const double* __restrict__ C, int n, int ax0, int by0, int i, int j, double h2,
+	const double (&mx)[4], const double (&my)[4])
+{
+	int ax = ax0 + 9 * j, by = by0 + 9 * i;
+	ax = ax < 0 ? 0 : (ax > n - 13 ? n - 13 : ax);
+	by = by < 0 ? 0 : (by > n - 13 ? n - 13 : by);
+	return h2 * prf_pixel(C, n, ax, by, mx, my);
+}
+
+// the same on any grid, (dc, dr) the pixel centre: psf.py:146  integral(column_cen - 0.5, column_cen + 0.5, row_cen - 0.5, row_cen + 0.5)
+__device__ __forceinline__ double star_pixel_general(const double* __restrict__ C, int n, int ny, const double* __restrict__ kn, const double* __restrict__ kny, double dc, double dr)
+{ return prf_pixel_general(C, n, ny, kn, kny, dc - 0.5, dc + 0.5, dr - 0.5, dr + 0.5); }
+
+// per register-resident star at one cadence: position, edge weights (the same for every pixel) and table origin of pixel 0
+template <int S> struct StarEdges { double mx[S][4], my[S][4], srow[S], scol[S]; int ax0[S], by0[S]; };
+
+template <int S>
+__device__ __forceinline__ void star_edges(const FitArgs& a, const double* kn, const double* kny, int n, double h, double hy, int64_t s0, int ns, int k, StarEdges<S>& e)
+{
+#pragma unroll
+	for (int s = 0; s < S; ++s) {
+		if (s < ns) {
+			e.srow[s] = a.pos_row[(s0 + s) * a.pos_pitch + k];
+			e.scol[s] = a.pos_col[(s0 + s) * a.pos_pitch + k];
+			// x <-> column (first spline axis), y <-> row  (psf.py:146)
+			axis_weights(kn, n, e.scol[s], h, e.mx[s], e.ax0[s]);
+			axis_weights(kny, n, e.srow[s], hy, e.my[s], e.by0[s]);
+		} else {
+			e.srow[s] = e.scol[s] = 0.0; e.ax0[s] = e.by0[s] = 4;
+#pragma unroll
+			for (int q = 0; q < 4; ++q) { e.mx[s][q] = 0.0; e.my[s][q] = 0.0; }
+		}
+	}
+}
+
 // General path: direct evaluation of the 13x13 contraction per star, pixel and cadence.  Runs only for the
 // targets that the polynomial path could not take (`todo` flag set, or todo == nullptr).
 template <int S, int SLO>
@@ -113,23 +163,8 @@ __global__ __launch_bounds__(512) void tp_linpsf_fit_direct_kernel(FitArgs a, co
 	const double h = kn[5] - kn[4], hy = kny[5] - kny[4];
 	const double cutoff = a.cutoff;
 
-	// per star: edge weights (same for every pixel) and table origin of pixel 0
-	double mx[S][4], my[S][4], srow[S], scol[S];
-	int ax0[S], by0[S];
-#pragma unroll
-	for (int s = 0; s < S; ++s) {
-		if (s < ns) {
-			srow[s] = a.pos_row[(s0 + s) * a.pos_pitch + k];
-			scol[s] = a.pos_col[(s0 + s) * a.pos_pitch + k];
-			// x <-> column (first spline axis), y <-> row  (psf.py:146)
-			axis_weights(kn, n, scol[s], h, mx[s], ax0[s]);
-			axis_weights(kny, n, srow[s], hy, my[s], by0[s]);
-		} else {
-			srow[s] = scol[s] = 0.0; ax0[s] = by0[s] = 4;
-#pragma unroll
-			for (int q = 0; q < 4; ++q) { mx[s][q] = 0.0; my[s][q] = 0.0; }
-		}
-	}
+	StarEdges<S> e;
+	star_edges<S>(a, kn, kny, n, h, hy, s0, ns, k, e);
 
 	double G[S][S], g[S];
 #pragma unroll
@@ -142,24 +177,16 @@ __global__ __launch_bounds__(512) void tp_linpsf_fit_direct_kernel(FitArgs a, co
 	const double h2 = h * hy;
 	for (int i = 0; i < H; ++i) {
 		for (int j = 0; j < W; ++j) {
-			float bf = img[(int64_t)(i * W + j) * a.t_pitch];
-			if (a.subtract) bf = bf - sub;
-			if (!(fabsf(bf) <= 3.402823466e+38f)) continue; // good_pixels = isfinite(img) (linpsf_photometry.py:123)
+			float bf;
+			if (!fetch_pixel(a, img, i * W + j, sub, bf)) continue;
 			const double b = (double)bf;
 			double av[S];
 #pragma unroll
 			for (int s = 0; s < S; ++s) {
 				av[s] = 0.0;
 				if (s < ns) {
-					const double dc = (double)j - scol[s], dr = (double)i - srow[s];
-					// psf.py:142  sqrt((j-col)^2 + (i-row)^2) < cutoff_radius  (a NaN position is never inside: zero column)
-					const bool inside = sqrt(dc * dc + dr * dr) < cutoff;
-					if (inside) {
-						int ax = ax0[s] + 9 * j, by = by0[s] + 9 * i;
-						ax = ax < 0 ? 0 : (ax > n - 13 ? n - 13 : ax);
-						by = by < 0 ? 0 : (by > n - 13 ? n - 13 : by);
-						av[s] = h2 * prf_pixel(C, n, ax, by, mx[s], my[s]);
-					}
+					const double dc = (double)j - e.scol[s], dr = (double)i - e.srow[s];
+					if (inside_cutoff(dc, dr, cutoff)) av[s] = star_pixel_uniform(C, n, e.ax0[s], e.by0[s], i, j, h2, e.mx[s], e.my[s]);
 				}
 			}
 #pragma unroll
@@ -207,7 +234,7 @@ __global__ __launch_bounds__(512) void tp_linpsf_fit_direct_kernel(FitArgs a, co
 struct StarBox { int axmin, axmax, bymin, bymax, jmin, jmax, imin, imax; };
 
 //--------------------------------------------------------------------------------------------------
-// Three kernels (round 2; the round-1 kernel kept the 110 KB table in LDS, one 768-thread workgroup per CU, and read the 25
+// Three kernels (a single kernel that kept the 110 KB table in LDS, one 768-thread workgroup per CU, and read the 25
 // coefficients of every Horner evaluation from LDS in every lane: 4 SIMDs share one LDS, so the coefficient reads, not the
 // FMAs, set its pace -- 24 ms for the C3 batch):
 //   plan  per target the boxes of its stars over ALL cadences (table origins visited, pixels that can be inside the
@@ -221,13 +248,13 @@ struct StarBox { int axmin, axmax, bymin, bymax, jmin, jmax, imin, imax; };
 //         wave-uniform address (3 x s_load_dwordx16 + 1) and enter the Horner FMAs as SGPR addends (v_fma_f64 with a scalar
 //         source) -- no LDS read, no barrier, and the occupancy is set by the registers.  Lanes of a wavefront that still
 //         differ in origin are served in turn (ballot loop).  One instantiation per star count (1, 2, 3, 4, 5-8).
-// The coefficient arithmetic and the accumulation order (pixels row-major) are those of the round-1 kernel: same results.
-// Measured (C3: 10 000 targets, 18 057 fitted stars): plan 0.65 ms, coef 1.23 ms, fit 10.9 ms (24.2 ms in round 1's kernel).
+// The coefficient arithmetic and the accumulation order (pixels row-major) are those of that single kernel: same results.
+// Measured (C3: 10 000 targets, 18 057 fitted stars): plan 0.65 ms, coef 1.23 ms, fit 10.9 ms (24.2 ms in the single kernel).
 // Also measured: the coefficients by per-lane vector loads of one address instead of scalar loads (17.7 ms: the texture
 // addresser handles 64 lanes whatever they read); natural cadence order (18.6 ms: three origins per wavefront on average);
 // the cadence's pixels fetched a row ahead through LDS (13.6 against 12.5: the loop is not waiting for its pixels); two or four
 // cadences per lane sharing the scalar loads and the uniform tests (10.9 - 11.9 ms for the combinations tried: no gain, the
-// extra registers cost what the shared work saves).  Round 3: the cadences sorted by origin only inside windows of 256 / 512
+// extra registers cost what the shared work saves).  Also: the cadences sorted by origin only inside windows of 256 / 512
 // consecutive cadences (a 128-byte line of a pixel's series is then touched by one workgroup: the PMC passes show 34 GB of
 // line fills per step against 12 GB of necessary bytes for the global sort): 14.2 / 12.6 ms against 10.9 -- the extra origins
 // per wavefront cost more than the re-fetched lines.
@@ -1091,8 +1118,80 @@ struct FinArgs {
 	const int32_t* todo;   // targets marked kPathMfma are finalised by tp_linpsf_finalize_m_kernel (nullptr: none are)
 };
 
+constexpr int kFinThreads = 256;   // every finalise kernel: four wavefronts
+
+// Count of the cadences with a valid target flux (returned) and the mean flux of every star over them: one pass, every thread its
+// cadences in order, then a fixed tree (lanes, then the four wavefronts in order).  red: [4 * (S + 1)] in LDS, free again on return.
+template <int S>
+__device__ __forceinline__ double mean_fluxes(const FitArgs& a, int target, int64_t s0, int ns, double* red, double (&mean)[S])
+{
+	const int tid = threadIdx.x;
+	const double* ftar = a.flux + (int64_t)target * a.out_pitch;
+	double part[S + 1];
+#pragma unroll
+	for (int u = 0; u <= S; ++u) part[u] = 0.0;
+	for (int k = tid; k < a.n_cad; k += kFinThreads) {
+		const bool ok = ftar[k] == ftar[k];
+		part[0] += ok ? 1.0 : 0.0;
+#pragma unroll
+		for (int s = 0; s < S; ++s) if (s < ns) { const double v = a.fluxes_all[(s0 + s) * a.out_pitch + k]; part[1 + s] += ok ? v : 0.0; }
+	}
+#pragma unroll
+	for (int u = 0; u <= S; ++u) {
+#pragma unroll
+		for (int off = 32; off > 0; off >>= 1) part[u] += __shfl_xor(part[u], off, 64);
+		if ((tid & 63) == 0) red[(tid >> 6) * (S + 1) + u] = part[u];
+	}
+	__syncthreads();
+	double cntd = 0.0;
+	for (int w = 0; w < kFinThreads / 64; ++w) cntd += red[w * (S + 1)];
+#pragma unroll
+	for (int s = 0; s < S; ++s) {
+		double tot = 0.0;
+		for (int w = 0; w < kFinThreads / 64; ++w) tot += red[w * (S + 1) + 1 + s];
+		mean[s] = tot / cntd;
+	}
+	__syncthreads();
+	return cntd;
+}
+
+// A thread's `acc` summed over the workgroup by the same tree: the lanes here, then sum4 of the wavefronts' partials in red[4] (LDS).
+// (A sum that starts from +0.0 is never -0.0, so adding the four partials to 0.0 in order gives the bits of sum4 too.)
+__device__ __forceinline__ void wave_partials(double acc, double* red)
+{
+#pragma unroll
+	for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
+	if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+	__syncthreads();
+}
+__device__ __forceinline__ double sum4(const double* red) { return ((red[0] + red[1]) + red[2]) + red[3]; }
+
+// allnan(flux) -> ERROR (linpsf_photometry.py:198-200)
+__device__ __forceinline__ void finish_all_nan(const FinArgs& fa, int target) { fa.status[target] = TP_STATUS_ERROR; fa.contamination[target] = __builtin_nan(""); }
+
+// contamination = sum_p (A[p, others] . mean[others]) * A[p, target] / mean[target] (`tot`: the sum over p), the status it decides
+// (linpsf_photometry.py:214-219) and the mean fluxes.  SMAX > 0: `mean` is a register array of SMAX stars (its loops must unroll);
+// SMAX == 0: it lies in memory, any number of stars.
+template <int SMAX>
+__device__ __forceinline__ void finish_target(const FinArgs& fa, int target, double tot, int ti, int64_t s0, int ns, const double* mean)
+{
+	double mt = 0.0;
+	if constexpr (SMAX > 0) {
+#pragma unroll
+		for (int u = 0; u < SMAX; ++u) if (u == ti) mt = mean[u];
+	} else mt = mean[ti];
+	const double cont = tot / mt;
+	fa.contamination[target] = cont;
+	fa.status[target] = (cont > 0.1) ? TP_STATUS_WARNING : TP_STATUS_OK;
+	if (!fa.fluxes_mean) return;
+	if constexpr (SMAX > 0) {
+#pragma unroll
+		for (int u = 0; u < SMAX; ++u) if (u < ns) fa.fluxes_mean[s0 + u] = mean[u];
+	} else for (int u = 0; u < ns; ++u) fa.fluxes_mean[s0 + u] = mean[u];
+}
+
 template <int S, int SLO>
-__global__ __launch_bounds__(256) void tp_linpsf_finalize_kernel(FinArgs fa)
+__global__ __launch_bounds__(kFinThreads) void tp_linpsf_finalize_kernel(FinArgs fa)
 {
 	{ const int nst = (int)(fa.f.star_offsets[blockIdx.x + 1] - fa.f.star_offsets[blockIdx.x]); if (nst < SLO || nst > S) return; } // another instantiation's targets
 	if (fa.todo && fa.todo[blockIdx.x] == kPathMfma) return;
@@ -1107,116 +1206,47 @@ __global__ __launch_bounds__(256) void tp_linpsf_finalize_kernel(FinArgs fa)
 	double* kn = lds;
 	double* kny = kn + n + 4;
 	double* red = kny + n + 4;           // [256]
-	for (int i = tid; i < n + 4; i += blockDim.x) { kn[i] = a.knots_x[i]; kny[i] = a.knots_y[i]; }
+	for (int i = tid; i < n + 4; i += kFinThreads) { kn[i] = a.knots_x[i]; kny[i] = a.knots_y[i]; }
 	__syncthreads();
 	const int64_t s0 = a.star_offsets[target];
 	int ns = (int)(a.star_offsets[target + 1] - s0);
 	if (ns > S) ns = S;
 	const int ti = a.target_index[target];
-	const double* ftar = a.flux + (int64_t)target * a.out_pitch;
-
-	// count of valid cadences and per-star flux sums (only over cadences whose fit succeeded): one pass, every thread its
-	// cadences in order, then a fixed tree (lanes, then the wavefronts in order)
 	double mean[S];
-	double part[S + 1];
-#pragma unroll
-	for (int u = 0; u <= S; ++u) part[u] = 0.0;
-	for (int k = tid; k < a.n_cad; k += blockDim.x) {
-		const bool ok = ftar[k] == ftar[k];
-		part[0] += ok ? 1.0 : 0.0;
-#pragma unroll
-		for (int s = 0; s < S; ++s) if (s < ns) { const double v = a.fluxes_all[(s0 + s) * a.out_pitch + k]; part[1 + s] += ok ? v : 0.0; }
-	}
-#pragma unroll
-	for (int u = 0; u <= S; ++u) {
-#pragma unroll
-		for (int off = 32; off > 0; off >>= 1) part[u] += __shfl_xor(part[u], off, 64);
-		if ((tid & 63) == 0) red[(tid >> 6) * (S + 1) + u] = part[u];
-	}
-	__syncthreads();
-	double cntd = 0.0;
-	{
-		const int nw = (int)blockDim.x >> 6;
-		for (int w = 0; w < nw; ++w) cntd += red[w * (S + 1)];
-#pragma unroll
-		for (int s = 0; s < S; ++s) {
-			double tot = 0.0;
-			for (int w = 0; w < nw; ++w) tot += red[w * (S + 1) + 1 + s];
-			mean[s] = tot / cntd;
-		}
-	}
-	__syncthreads();
-	if (cntd == 0.0) { // allnan(flux) -> ERROR (linpsf_photometry.py:198-200)
-		if (tid == 0) { fa.status[target] = TP_STATUS_ERROR; fa.contamination[target] = __builtin_nan(""); }
-		return;
-	}
-	// contamination = sum_p (A[p, others] . mean[others]) * A[p, target] / mean[target], A of the last cadence
+	const double cntd = mean_fluxes<S>(a, target, s0, ns, red, mean);
+	if (cntd == 0.0) { if (tid == 0) finish_all_nan(fa, target); return; }
 	const int k = a.n_cad - 1;
 	const int H = a.height, W = a.width;
 	const double h = kn[5] - kn[4], hy = kny[5] - kny[4], h2 = h * hy;
-	double mx[S][4], my[S][4], srow[S], scol[S];
-	int ax0[S], by0[S];
-#pragma unroll
-	for (int s = 0; s < S; ++s) {
-		if (s < ns) {
-			srow[s] = a.pos_row[(s0 + s) * a.pos_pitch + k];
-			scol[s] = a.pos_col[(s0 + s) * a.pos_pitch + k];
-			axis_weights(kn, n, scol[s], h, mx[s], ax0[s]);
-			axis_weights(kny, n, srow[s], hy, my[s], by0[s]);
-		} else { srow[s] = scol[s] = 0.0; ax0[s] = by0[s] = 4;
-#pragma unroll
-			for (int q = 0; q < 4; ++q) { mx[s][q] = 0.0; my[s][q] = 0.0; } }
-	}
+	StarEdges<S> e;
+	star_edges<S>(a, kn, kny, n, h, hy, s0, ns, k, e);
 	const float* img = a.images + (int64_t)target * H * W * a.t_pitch + k;
 	const float sub = a.subtract ? a.subtract[(int64_t)target * a.subtract_pitch + k] : 0.f;
 	double acc = 0.0;
-	for (int p = tid; p < H * W; p += blockDim.x) {
+	for (int p = tid; p < H * W; p += kFinThreads) {
 		const int i = p / W, j = p - i * W;
-		float bf = img[(int64_t)p * a.t_pitch];
-		if (a.subtract) bf = bf - sub;
-		if (!(fabsf(bf) <= 3.402823466e+38f)) continue;
+		float bf;
+		if (!fetch_pixel(a, img, p, sub, bf)) continue;
 		double others = 0.0, at = 0.0;
 #pragma unroll
 		for (int s = 0; s < S; ++s) {
 			if (s >= ns) continue;
-			const double dc = (double)j - scol[s], dr = (double)i - srow[s];
+			const double dc = (double)j - e.scol[s], dr = (double)i - e.srow[s];
 			double v = 0.0;
-			if (sqrt(dc * dc + dr * dr) < a.cutoff) {
-				int ax = ax0[s] + 9 * j, by = by0[s] + 9 * i;
-				ax = ax < 0 ? 0 : (ax > n - 13 ? n - 13 : ax);
-				by = by < 0 ? 0 : (by > n - 13 ? n - 13 : by);
-				v = h2 * prf_pixel(C, n, ax, by, mx[s], my[s]);
-			}
+			if (inside_cutoff(dc, dr, a.cutoff)) v = star_pixel_uniform(C, n, e.ax0[s], e.by0[s], i, j, h2, e.mx[s], e.my[s]);
 			if (s == ti) at = v; else others += v * mean[s];
 		}
 		acc += others * at;
 	}
-#pragma unroll
-	for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
-	if ((tid & 63) == 0) red[tid >> 6] = acc;
-	__syncthreads();
-	if (tid == 0) {
-		double tot = 0.0;
-		for (int w = 0; w < ((int)blockDim.x >> 6); ++w) tot += red[w];
-		double mt = 0.0;
-#pragma unroll
-		for (int u = 0; u < S; ++u) if (u == ti) mt = mean[u];
-		const double cont = tot / mt;
-		fa.contamination[target] = cont;
-		fa.status[target] = (cont > 0.1) ? TP_STATUS_WARNING : TP_STATUS_OK; // :214-219
-		if (fa.fluxes_mean) {
-#pragma unroll
-			for (int u = 0; u < S; ++u) if (u < ns) fa.fluxes_mean[s0 + u] = mean[u];
-		}
-	}
+	wave_partials(acc, red);
+	if (tid == 0) finish_target<S>(fa, target, sum4(red), ti, s0, ns, mean);
 }
 
-
-// Finalise for the targets of the matrix-core fit: the same rules, with the design matrix of the last cadence as the fit
-// kernel left it (alast[target][star][pixel of the list U], zero outside the cut-off and where the pixel is not finite) instead
-// of a second evaluation of the PRF.
+// Finalise for the targets of the matrix-core fit (class S - 1: exactly S stars): the same rules, with the design matrix of the
+// last cadence as the fit kernel left it (alast[target][star][pixel of the list U], zero outside the cut-off and where the pixel
+// is not finite) instead of a second evaluation of the PRF.
 template <int S>
-__global__ __launch_bounds__(256) void tp_linpsf_finalize_m_kernel(FinArgs fa, const int32_t* __restrict__ targets, const MPlan* __restrict__ mplans,
+__global__ __launch_bounds__(kFinThreads) void tp_linpsf_finalize_m_kernel(FinArgs fa, const int32_t* __restrict__ targets, const MPlan* __restrict__ mplans,
 	const double* __restrict__ alast)
 {
 	__shared__ double red[4 * (S + 1)];
@@ -1225,41 +1255,13 @@ __global__ __launch_bounds__(256) void tp_linpsf_finalize_m_kernel(FinArgs fa, c
 	const int tid = threadIdx.x;
 	const int64_t s0 = a.star_offsets[target];
 	const int ti = a.target_index[target];
-	const double* ftar = a.flux + (int64_t)target * a.out_pitch;
-	double mean[S], part[S + 1];
-#pragma unroll
-	for (int u = 0; u <= S; ++u) part[u] = 0.0;
-	for (int k = tid; k < a.n_cad; k += 256) {
-		const bool ok = ftar[k] == ftar[k];
-		part[0] += ok ? 1.0 : 0.0;
-#pragma unroll
-		for (int s = 0; s < S; ++s) { const double v = a.fluxes_all[(s0 + s) * a.out_pitch + k]; part[1 + s] += ok ? v : 0.0; }
-	}
-#pragma unroll
-	for (int u = 0; u <= S; ++u) {
-#pragma unroll
-		for (int off = 32; off > 0; off >>= 1) part[u] += __shfl_xor(part[u], off, 64);
-		if ((tid & 63) == 0) red[(tid >> 6) * (S + 1) + u] = part[u];
-	}
-	__syncthreads();
-	double cntd = 0.0;
-	for (int w = 0; w < 4; ++w) cntd += red[w * (S + 1)];
-#pragma unroll
-	for (int s = 0; s < S; ++s) {
-		double tot = 0.0;
-		for (int w = 0; w < 4; ++w) tot += red[w * (S + 1) + 1 + s];
-		mean[s] = tot / cntd;
-	}
-	__syncthreads();
-	if (cntd == 0.0) { // allnan(flux) -> ERROR (linpsf_photometry.py:198-200)
-		if (tid == 0) { fa.status[target] = TP_STATUS_ERROR; fa.contamination[target] = __builtin_nan(""); }
-		return;
-	}
-	// contamination = sum_p (A[p, others] . mean[others]) * A[p, target] / mean[target]
+	double mean[S];
+	const double cntd = mean_fluxes<S>(a, target, s0, S, red, mean);
+	if (cntd == 0.0) { if (tid == 0) finish_all_nan(fa, target); return; }
 	const int npix = mplans[target].n_tiles * 16;
 	const double* al = alast + (int64_t)target * kMfmaStars * kMfmaPixels;
 	double acc = 0.0;
-	for (int u = tid; u < npix; u += 256) {
+	for (int u = tid; u < npix; u += kFinThreads) {
 		double others = 0.0, at = 0.0;
 #pragma unroll
 		for (int s = 0; s < S; ++s) {
@@ -1268,23 +1270,8 @@ __global__ __launch_bounds__(256) void tp_linpsf_finalize_m_kernel(FinArgs fa, c
 		}
 		acc += others * at;
 	}
-#pragma unroll
-	for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
-	if ((tid & 63) == 0) red[tid >> 6] = acc;
-	__syncthreads();
-	if (tid == 0) {
-		const double tot = ((red[0] + red[1]) + red[2]) + red[3];
-		double mt = 0.0;
-#pragma unroll
-		for (int u = 0; u < S; ++u) if (u == ti) mt = mean[u];
-		const double cont = tot / mt;
-		fa.contamination[target] = cont;
-		fa.status[target] = (cont > 0.1) ? TP_STATUS_WARNING : TP_STATUS_OK; // :214-219
-		if (fa.fluxes_mean) {
-#pragma unroll
-			for (int u = 0; u < S; ++u) fa.fluxes_mean[s0 + u] = mean[u];
-		}
-	}
+	wave_partials(acc, red);
+	if (tid == 0) finish_target<S>(fa, target, sum4(red), ti, s0, S, mean);
 }
 
 //--------------------------------------------------------------------------------------------------
@@ -1295,6 +1282,14 @@ __global__ __launch_bounds__(256) void tp_linpsf_finalize_m_kernel(FinArgs fa, c
 // Same arithmetic (direct 13x13 contraction, cyclic Jacobi pseudo-inverse with numpy's cut-off), only slower.
 //--------------------------------------------------------------------------------------------------
 constexpr int kMaxManyStars = 64;
+constexpr int kManyThreads = 256;
+
+// a thread's scratch for targets of up to S stars, in doubles: where each array starts, and their sum (the host sizes the scratch by it)
+struct ManyLayout {
+	int G, V, g, x, av, row, col, mx, my, ax0, by0, doubles;
+	__host__ __device__ explicit ManyLayout(int S)
+		: G(0), V(S * S), g(2 * S * S), x(g + S), av(x + S), row(av + S), col(row + S), mx(col + S), my(mx + 4 * S), ax0(my + 4 * S), by0(ax0 + S), doubles(by0 + S) {}
+};
 
 struct ManyScratch {
 	double* base; int64_t n_threads; int64_t gt;
@@ -1304,7 +1299,7 @@ struct ManyScratch {
 // GENERAL: any knot vectors and any cut-off radius (prf_pixel_general: the FITPACK box integral itself); `big_targets` may be
 // null (= every target, first_target + blockIdx.x) and the table stays in HBM when it does not fit the LDS (table_in_lds = 0).
 template <bool GENERAL>
-__global__ __launch_bounds__(256) void tp_linpsf_fit_many_kernel(FitArgs a, const int32_t* __restrict__ big_targets, int first_target, int smax, double* __restrict__ scratch,
+__global__ __launch_bounds__(kManyThreads) void tp_linpsf_fit_many_kernel(FitArgs a, const int32_t* __restrict__ big_targets, int first_target, int smax, double* __restrict__ scratch,
 	int table_in_lds)
 {
 	extern __shared__ __align__(16) double lds[]; // [n*ny] coefficient table (if it fits) + [n+4] + [ny+4] knots
@@ -1326,121 +1321,114 @@ __global__ __launch_bounds__(256) void tp_linpsf_fit_many_kernel(FitArgs a, cons
 	const int ns = (int)(a.star_offsets[target + 1] - s0);
 	const int H = a.height, W = a.width;
 	const double h = kn[5] - kn[4], hy = kny[5] - kny[4], h2 = h * hy;
-	// layout of a thread's scratch: G[S*S] V[S*S] g[S] x[S] av[S] srow[S] scol[S] mx[4S] my[4S] ax0[S] by0[S]
-	const int S = smax, SS = S * S;
+	const int S = smax;
+	const ManyLayout o(S);
 	ManyScratch m{scratch, (int64_t)gridDim.x * gridDim.y * blockDim.x, ((int64_t)blockIdx.x * gridDim.y + blockIdx.y) * blockDim.x + tid};
-	const int oG = 0, oV = SS, og = 2 * SS, ox = og + S, oav = ox + S, orow = oav + S, ocol = orow + S, omx = ocol + S, omy = omx + 4 * S,
-		oax = omy + 4 * S, oby = oax + S;
 	for (int s = 0; s < ns; ++s) {
 		const double r = a.pos_row[(s0 + s) * a.pos_pitch + k], c = a.pos_col[(s0 + s) * a.pos_pitch + k];
-		m.at(orow + s) = r; m.at(ocol + s) = c;
+		m.at(o.row + s) = r; m.at(o.col + s) = c;
 		if (!GENERAL) {
 			double wx[4], wy[4];
 			int ax0, by0;
 			axis_weights(kn, n, c, h, wx, ax0);
 			axis_weights(kny, n, r, hy, wy, by0);
-			for (int q = 0; q < 4; ++q) { m.at(omx + 4 * s + q) = wx[q]; m.at(omy + 4 * s + q) = wy[q]; }
-			m.at(oax + s) = (double)ax0; m.at(oby + s) = (double)by0;
+			for (int q = 0; q < 4; ++q) { m.at(o.mx + 4 * s + q) = wx[q]; m.at(o.my + 4 * s + q) = wy[q]; }
+			m.at(o.ax0 + s) = (double)ax0; m.at(o.by0 + s) = (double)by0;
 		}
-		m.at(og + s) = 0.0;
-		for (int u = 0; u < ns; ++u) m.at(oG + s * S + u) = 0.0;
+		m.at(o.g + s) = 0.0;
+		for (int u = 0; u < ns; ++u) m.at(o.G + s * S + u) = 0.0;
 	}
 	const float* img = a.images + (int64_t)target * H * W * a.t_pitch + k;
 	const float sub = a.subtract ? a.subtract[(int64_t)target * a.subtract_pitch + k] : 0.f;
 	for (int i = 0; i < H; ++i) {
 		for (int j = 0; j < W; ++j) {
-			float bf = img[(int64_t)(i * W + j) * a.t_pitch];
-			if (a.subtract) bf = bf - sub;
-			if (!(fabsf(bf) <= 3.402823466e+38f)) continue;
+			float bf;
+			if (!fetch_pixel(a, img, i * W + j, sub, bf)) continue;
 			const double b = (double)bf;
 			bool any = false;
 			for (int s = 0; s < ns; ++s) {
 				double v = 0.0;
-				const double dc = (double)j - m.at(ocol + s), dr = (double)i - m.at(orow + s);
-				if (sqrt(dc * dc + dr * dr) < a.cutoff) {
+				const double dc = (double)j - m.at(o.col + s), dr = (double)i - m.at(o.row + s);
+				if (inside_cutoff(dc, dr, a.cutoff)) {
 					if (GENERAL) {
-						// psf.py:146  integral(column_cen - 0.5, column_cen + 0.5, row_cen - 0.5, row_cen + 0.5)
-						v = prf_pixel_general(C, n, ny, kn, kny, dc - 0.5, dc + 0.5, dr - 0.5, dr + 0.5);
+						v = star_pixel_general(C, n, ny, kn, kny, dc, dr);
 					} else {
 						double wx[4], wy[4];
-						for (int q = 0; q < 4; ++q) { wx[q] = m.at(omx + 4 * s + q); wy[q] = m.at(omy + 4 * s + q); }
-						int ax = (int)m.at(oax + s) + 9 * j, by = (int)m.at(oby + s) + 9 * i;
-						ax = ax < 0 ? 0 : (ax > n - 13 ? n - 13 : ax);
-						by = by < 0 ? 0 : (by > n - 13 ? n - 13 : by);
-						v = h2 * prf_pixel(C, n, ax, by, wx, wy);
+						for (int q = 0; q < 4; ++q) { wx[q] = m.at(o.mx + 4 * s + q); wy[q] = m.at(o.my + 4 * s + q); }
+						v = star_pixel_uniform(C, n, (int)m.at(o.ax0 + s), (int)m.at(o.by0 + s), i, j, h2, wx, wy);
 					}
 					any = true;
 				}
-				m.at(oav + s) = v;
+				m.at(o.av + s) = v;
 			}
 			if (!any) continue; // a pixel outside every cut-off disc adds nothing to A^T A or A^T b
 			for (int s = 0; s < ns; ++s) {
-				const double as = m.at(oav + s);
+				const double as = m.at(o.av + s);
 				if (as == 0.0) continue;
-				m.at(og + s) += as * b;
-				for (int u = s; u < ns; ++u) m.at(oG + s * S + u) += as * m.at(oav + u);
+				m.at(o.g + s) += as * b;
+				for (int u = s; u < ns; ++u) m.at(o.G + s * S + u) += as * m.at(o.av + u);
 			}
 		}
 	}
 	for (int s = 0; s < ns; ++s) {
-		for (int u = 0; u < s; ++u) m.at(oG + s * S + u) = m.at(oG + u * S + s);
-		for (int u = 0; u < ns; ++u) m.at(oV + s * S + u) = (s == u) ? 1.0 : 0.0;
+		for (int u = 0; u < s; ++u) m.at(o.G + s * S + u) = m.at(o.G + u * S + s);
+		for (int u = 0; u < ns; ++u) m.at(o.V + s * S + u) = (s == u) ? 1.0 : 0.0;
 	}
 	// cyclic Jacobi (same sweep order and stopping rule as pinv_solve)
 	for (int sweep = 0; sweep < 30; ++sweep) {
 		double off = 0.0, d2 = 0.0;
 		for (int p = 0; p < ns; ++p) {
-			const double d = m.at(oG + p * S + p);
+			const double d = m.at(o.G + p * S + p);
 			d2 += d * d;
-			for (int q = p + 1; q < ns; ++q) { const double o = m.at(oG + p * S + q); off += o * o; }
+			for (int q = p + 1; q < ns; ++q) { const double od = m.at(o.G + p * S + q); off += od * od; }
 		}
 		if (!(off > 1e-34 * d2)) break;
 		for (int p = 0; p < ns; ++p) {
 			for (int q = p + 1; q < ns; ++q) {
-				const double apq = m.at(oG + p * S + q);
+				const double apq = m.at(o.G + p * S + q);
 				if (apq == 0.0) continue;
-				const double theta = (m.at(oG + q * S + q) - m.at(oG + p * S + p)) / (2.0 * apq);
+				const double theta = (m.at(o.G + q * S + q) - m.at(o.G + p * S + p)) / (2.0 * apq);
 				const double t = ((theta >= 0.0) ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
 				const double c = 1.0 / sqrt(t * t + 1.0), sn = t * c;
 				for (int e = 0; e < ns; ++e) {
-					const double gp = m.at(oG + e * S + p), gq = m.at(oG + e * S + q);
-					m.at(oG + e * S + p) = c * gp - sn * gq;
-					m.at(oG + e * S + q) = sn * gp + c * gq;
+					const double gp = m.at(o.G + e * S + p), gq = m.at(o.G + e * S + q);
+					m.at(o.G + e * S + p) = c * gp - sn * gq;
+					m.at(o.G + e * S + q) = sn * gp + c * gq;
 				}
 				for (int e = 0; e < ns; ++e) {
-					const double gp = m.at(oG + p * S + e), gq = m.at(oG + q * S + e);
-					m.at(oG + p * S + e) = c * gp - sn * gq;
-					m.at(oG + q * S + e) = sn * gp + c * gq;
+					const double gp = m.at(o.G + p * S + e), gq = m.at(o.G + q * S + e);
+					m.at(o.G + p * S + e) = c * gp - sn * gq;
+					m.at(o.G + q * S + e) = sn * gp + c * gq;
 				}
 				for (int e = 0; e < ns; ++e) {
-					const double vp = m.at(oV + e * S + p), vq = m.at(oV + e * S + q);
-					m.at(oV + e * S + p) = c * vp - sn * vq;
-					m.at(oV + e * S + q) = sn * vp + c * vq;
+					const double vp = m.at(o.V + e * S + p), vq = m.at(o.V + e * S + q);
+					m.at(o.V + e * S + p) = c * vp - sn * vq;
+					m.at(o.V + e * S + q) = sn * vp + c * vq;
 				}
 			}
 		}
 	}
 	double smx = 0.0;
-	for (int i = 0; i < ns; ++i) { const double v = fabs(m.at(oG + i * S + i)); if (v > smx || v != v) smx = v; }
+	for (int i = 0; i < ns; ++i) { const double v = fabs(m.at(o.G + i * S + i)); if (v > smx || v != v) smx = v; }
 	const double cut = 1e-15 * smx;
-	for (int i = 0; i < ns; ++i) m.at(ox + i) = 0.0;
+	for (int i = 0; i < ns; ++i) m.at(o.x + i) = 0.0;
 	for (int e = 0; e < ns; ++e) {
-		const double lam = m.at(oG + e * S + e);
+		const double lam = m.at(o.G + e * S + e);
 		double proj = 0.0;
-		for (int i = 0; i < ns; ++i) proj += m.at(oV + i * S + e) * m.at(og + i);
+		for (int i = 0; i < ns; ++i) proj += m.at(o.V + i * S + e) * m.at(o.g + i);
 		const double inv = (fabs(lam) > cut) ? (1.0 / lam) : ((lam != lam) ? lam : 0.0);
 		const double coef = proj * inv;
-		for (int i = 0; i < ns; ++i) m.at(ox + i) += m.at(oV + i * S + e) * coef;
+		for (int i = 0; i < ns; ++i) m.at(o.x + i) += m.at(o.V + i * S + e) * coef;
 	}
 	const int ti = a.target_index[target];
-	for (int s = 0; s < ns; ++s) a.fluxes_all[(s0 + s) * a.out_pitch + k] = m.at(ox + s);
-	a.flux[(int64_t)target * a.out_pitch + k] = (ti >= 0 && ti < ns) ? m.at(ox + ti) : __builtin_nan("");
+	for (int s = 0; s < ns; ++s) a.fluxes_all[(s0 + s) * a.out_pitch + k] = m.at(o.x + s);
+	a.flux[(int64_t)target * a.out_pitch + k] = (ti >= 0 && ti < ns) ? m.at(o.x + ti) : __builtin_nan("");
 	a.flux_err[(int64_t)target * a.out_pitch + k] = __builtin_nan("");
 }
 
-// finalise for the targets of the kernel above (same rules as tp_linpsf_finalize_kernel, star loops at run time)
+// Finalise for the targets of the kernel above: the same rules, the star loops at run time, every sum serial over the 256 slots of `red`
 template <bool GENERAL>
-__global__ __launch_bounds__(256) void tp_linpsf_finalize_many_kernel(FinArgs fa, const int32_t* __restrict__ big_targets, int first_target)
+__global__ __launch_bounds__(kFinThreads) void tp_linpsf_finalize_many_kernel(FinArgs fa, const int32_t* __restrict__ big_targets, int first_target)
 {
 	extern __shared__ __align__(16) double lds[];
 	const FitArgs& a = fa.f;
@@ -1476,10 +1464,7 @@ __global__ __launch_bounds__(256) void tp_linpsf_finalize_many_kernel(FinArgs fa
 		else if (tid == 0) mean[s] = tot / cntd;
 	}
 	__syncthreads();
-	if (cntd == 0.0) {
-		if (tid == 0) { fa.status[target] = TP_STATUS_ERROR; fa.contamination[target] = __builtin_nan(""); }
-		return;
-	}
+	if (cntd == 0.0) { if (tid == 0) finish_all_nan(fa, target); return; }
 	const int k = a.n_cad - 1;
 	const int H = a.height, W = a.width;
 	const double h = kn[5] - kn[4], hy = kny[5] - kny[4], h2 = h * hy;
@@ -1488,26 +1473,22 @@ __global__ __launch_bounds__(256) void tp_linpsf_finalize_many_kernel(FinArgs fa
 	double acc = 0.0;
 	for (int p = tid; p < H * W; p += blockDim.x) {
 		const int i = p / W, j = p - i * W;
-		float bf = img[(int64_t)p * a.t_pitch];
-		if (a.subtract) bf = bf - sub;
-		if (!(fabsf(bf) <= 3.402823466e+38f)) continue;
+		float bf;
+		if (!fetch_pixel(a, img, p, sub, bf)) continue;
 		double others = 0.0, at = 0.0;
 		for (int s = 0; s < ns; ++s) {
 			const double srow = a.pos_row[(s0 + s) * a.pos_pitch + k], scol = a.pos_col[(s0 + s) * a.pos_pitch + k];
 			const double dc = (double)j - scol, dr = (double)i - srow;
 			double v = 0.0;
-			if (sqrt(dc * dc + dr * dr) < a.cutoff) {
+			if (inside_cutoff(dc, dr, a.cutoff)) {
 				if (GENERAL) {
-					v = prf_pixel_general(C, n, ny, kn, kny, dc - 0.5, dc + 0.5, dr - 0.5, dr + 0.5);
+					v = star_pixel_general(C, n, ny, kn, kny, dc, dr);
 				} else {
 					double wx[4], wy[4];
 					int ax0, by0;
 					axis_weights(kn, n, scol, h, wx, ax0);
 					axis_weights(kny, n, srow, hy, wy, by0);
-					int ax = ax0 + 9 * j, by = by0 + 9 * i;
-					ax = ax < 0 ? 0 : (ax > n - 13 ? n - 13 : ax);
-					by = by < 0 ? 0 : (by > n - 13 ? n - 13 : by);
-					v = h2 * prf_pixel(C, n, ax, by, wx, wy);
+					v = star_pixel_uniform(C, n, ax0, by0, i, j, h2, wx, wy);
 				}
 			}
 			if (s == ti) at = v; else others += v * mean[s];
@@ -1519,10 +1500,7 @@ __global__ __launch_bounds__(256) void tp_linpsf_finalize_many_kernel(FinArgs fa
 	if (tid == 0) {
 		double tot = 0.0;
 		for (int l = 0; l < (int)blockDim.x; ++l) tot += red[l];
-		const double cont = tot / mean[ti];
-		fa.contamination[target] = cont;
-		fa.status[target] = (cont > 0.1) ? TP_STATUS_WARNING : TP_STATUS_OK;
-		if (fa.fluxes_mean) for (int u = 0; u < ns; ++u) fa.fluxes_mean[s0 + u] = mean[u];
+		finish_target<0>(fa, target, tot, ti, s0, ns, mean);
 	}
 }
 
@@ -1562,9 +1540,245 @@ extern "C" int tp_linpsf_last_counts(tp_ctx* ctx, int64_t* counts, int32_t n)
 	return TP_OK;
 }
 
-static int linpsf_fit_impl(tp_ctx* ctx, const tp_cube_desc* desc, const float* d_images,
+namespace {
+
+#define TP_TRY(call) do { const int _rc = (call); if (_rc != TP_OK) return _rc; } while (0)
+
+inline size_t align256(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
+
+// What the plan kernel leaves for the kernels after it: the head of the context's scratch, every array on a 256-byte boundary.
+// The many-star kernels' list and scratch lie behind it (`bytes` from the start).  The scratch may MOVE when it grows, and d_todo
+// and d_total live in this head: so it is grown a second time only where nothing in flight or still to come reads the head -- for
+// the any-grid kernels after the totals' synchronise, for the targets of more than 8 stars after a synchronise of their own.
+struct PlanScratch {
+	int32_t* todo; StarPlan* plans; unsigned long long* total; int32_t* order; MPlan* mplans; uint16_t* ulist; uint8_t* usig;
+	int32_t* lists; SegPlan* segs; int32_t* seglists; double* alast;
+	size_t todo_bytes, bytes;
+};
+constexpr size_t kTotalWords = 32;
+static_assert(kTotCount <= kTotalWords, "the counters fit their block");
+
+// the arrays of the head from the address `base` on (0: only their sizes are wanted)
+void carve_plan_scratch(uintptr_t base, size_t n_targets, size_t n_cad, bool with_alast, PlanScratch& h)
+{
+	size_t off = 0;
+	auto take = [&](auto*& p, size_t count) { p = reinterpret_cast<std::remove_reference_t<decltype(p)>>(base + off); off += align256(count * sizeof(*p)); };
+	take(h.todo, n_targets); h.todo_bytes = off;
+	take(h.plans, n_targets * kMaxStars);
+	take(h.total, kTotalWords);
+	take(h.order, n_targets * n_cad);
+	take(h.mplans, n_targets);
+	take(h.ulist, n_targets * kMfmaPixels);
+	take(h.usig, n_targets * kMfmaPixels);
+	take(h.lists, n_targets * kMfmaClasses);
+	take(h.segs, n_targets * kMfmaSegs);
+	take(h.seglists, n_targets * kMfmaSegs * kMfmaClasses);
+	take(h.alast, with_alast ? n_targets * kMfmaStars * kMfmaPixels : 0);
+	h.bytes = off;
+}
+
+// dynamic LDS: the knot vectors; the coefficient table before them; red[256] behind them (finalise kernels)
+inline size_t knots_lds(const FitArgs& a) { return ((size_t)(a.n + 4) + (size_t)(a.ny + 4)) * sizeof(double); }
+inline size_t table_lds(const FitArgs& a) { return (size_t)a.n * a.ny * sizeof(double) + knots_lds(a); }
+inline size_t fin_lds(const FitArgs& a) { return knots_lds(a) + 256 * sizeof(double); }
+
+// the star offsets on the host (the copy synchronises the stream); no target may bring more stars than the many-star kernels take
+int download_star_offsets(tp_ctx* ctx, const FitArgs& a, int n_targets, std::vector<int64_t>& off)
+{
+	off.resize((size_t)n_targets + 1);
+	TP_HIP(ctx, hipMemcpyAsync(off.data(), a.star_offsets, off.size() * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+	TP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	for (int t = 0; t < n_targets; ++t) {
+		const int64_t ns = off[t + 1] - off[t];
+		TP_REQUIRE(ctx, ns >= 0 && ns <= kMaxManyStars, "tp_linpsf_fit: a target has more than 64 fitted stars");
+	}
+	return TP_OK;
+}
+
+// the many-star kernels: one thread per cadence in workgroups of kManyThreads, a ManyLayout of doubles per thread
+inline int many_blocks(const FitArgs& a) { return (a.n_cad + kManyThreads - 1) / kManyThreads; }
+inline size_t many_scratch_per_target(const FitArgs& a, int smax) { return (size_t)ManyLayout(smax).doubles * sizeof(double) * many_blocks(a) * kManyThreads; }
+
+// fit and finalise `count` targets of up to smax stars out of d_scr: those of d_list, or first .. first + count - 1 (d_list == nullptr)
+template <bool GENERAL>
+int launch_many(tp_ctx* ctx, const FitArgs& a, const FinArgs& fa, const int32_t* d_list, int first, int count, int smax, double* d_scr)
+{
+	// (only the any-grid tables can outgrow the LDS)
+	const int table_in_lds = (!GENERAL || table_lds(a) <= (size_t)160 * 1024) ? 1 : 0;
+	const size_t lds = table_in_lds ? table_lds(a) : knots_lds(a);
+	TP_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(tp_linpsf_fit_many_kernel<GENERAL>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+	TP_LAUNCH(ctx, TPK_LINPSF_FIT_DIRECT, tp_linpsf_fit_many_kernel<GENERAL>, dim3((unsigned)count, (unsigned)many_blocks(a)), dim3(kManyThreads), lds, a, d_list, first, smax, d_scr, table_in_lds);
+	TP_LAUNCH_CHECK(ctx, GENERAL ? "tp_linpsf_fit_many_kernel (general)" : "tp_linpsf_fit_many_kernel");
+	TP_LAUNCH(ctx, TPK_LINPSF_FIN, tp_linpsf_finalize_many_kernel<GENERAL>, dim3((unsigned)count), dim3(kFinThreads), fin_lds(a) + kMaxManyStars * sizeof(double), fa, d_list, first);
+	TP_LAUNCH_CHECK(ctx, GENERAL ? "tp_linpsf_finalize_many_kernel (general)" : "tp_linpsf_finalize_many_kernel");
+	return TP_OK;
+}
+
+// any grid, any cut-off: every target through the run-time sized kernels with the FITPACK box integral, a few GiB of scratch at a time
+int fit_any_grid(tp_ctx* ctx, const FitArgs& a, const FinArgs& fa, int n_targets, const PlanScratch& h)
+{
+	std::vector<int64_t> off;
+	TP_TRY(download_star_offsets(ctx, a, n_targets, off));
+	int smax = 1;
+	for (int t = 0; t < n_targets; ++t) if ((int)(off[t + 1] - off[t]) > smax) smax = (int)(off[t + 1] - off[t]);
+	const size_t per_target = many_scratch_per_target(a, smax);
+	int64_t chunk = (int64_t)(((size_t)4 << 30) / per_target);
+	if (chunk < 1) chunk = 1;
+	if (chunk > n_targets) chunk = n_targets;
+	TP_REQUIRE(ctx, tp_ctx_scratch(ctx, h.bytes + per_target * (size_t)chunk + 256) != nullptr, "tp_linpsf_fit: out of device memory for the scratch of the general kernels");
+	double* d_scr = reinterpret_cast<double*>(static_cast<char*>(ctx->scratch) + h.bytes);
+	for (int64_t first = 0; first < n_targets; first += chunk) {
+		const int64_t cnt = (n_targets - first < chunk) ? (n_targets - first) : chunk;
+		TP_TRY(launch_many<true>(ctx, a, fa, nullptr, (int)first, (int)cnt, smax, d_scr));
+	}
+	ctx->linpsf_counts[13] = n_targets;
+	return TP_OK;
+}
+
+// targets with more than 8 fitted stars (rare: crowded fields): listed on the host from the star offsets
+int fit_many_star_targets(tp_ctx* ctx, const FitArgs& a, const FinArgs& fa, int n_targets, const PlanScratch& h)
+{
+	std::vector<int64_t> off;
+	TP_TRY(download_star_offsets(ctx, a, n_targets, off));
+	std::vector<int32_t> big;
+	int smax = 0;
+	for (int t = 0; t < n_targets; ++t) {
+		const int ns = (int)(off[t + 1] - off[t]);
+		if (ns > kMaxStars) { big.push_back(t); if (ns > smax) smax = ns; }
+	}
+	ctx->linpsf_counts[4] = (int64_t)big.size();
+	if (big.empty()) return TP_OK;
+	const size_t list_bytes = align256(big.size() * sizeof(int32_t));
+	const size_t need = h.bytes + list_bytes + many_scratch_per_target(a, smax) * big.size() + 256;
+	TP_HIP(ctx, hipStreamSynchronize(ctx->stream));   // the class kernels are done with the head (see PlanScratch)
+	TP_REQUIRE(ctx, tp_ctx_scratch(ctx, need) != nullptr, "tp_linpsf_fit: out of device memory for the many-star scratch");
+	char* base = static_cast<char*>(ctx->scratch) + h.bytes;
+	int32_t* d_big = reinterpret_cast<int32_t*>(base);
+	TP_HIP(ctx, hipMemcpyAsync(d_big, big.data(), big.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+	TP_TRY(launch_many<false>(ctx, a, fa, d_big, 0, (int)big.size(), smax, reinterpret_cast<double*>(base + list_bytes)));
+	TP_HIP(ctx, hipStreamSynchronize(ctx->stream)); // `big` (host) must outlive the copy
+	return TP_OK;
+}
+
+// The launches of the class kernels, one instantiation per star count (the normal equations and the registers of a 1-star target are
+// not those of a 4-star one); a workgroup whose target belongs to another class exits at once.  They use linpsf_fit_impl's names.
+#define TP_LINPSF_FINM(S) do { if (totals[kTotClass0 + (S) - 1] > 0) { \
+	TP_LAUNCH(ctx, TPK_LINPSF_FIN, (tp_linpsf_finalize_m_kernel<S>), dim3((unsigned)totals[kTotClass0 + (S) - 1]), dim3(kFinThreads), 0, fa, \
+		(const int32_t*)(h.lists + (size_t)((S) - 1) * n_targets), (const MPlan*)h.mplans, (const double*)h.alast); \
+	TP_LAUNCH_CHECK(ctx, "tp_linpsf_finalize_m_kernel"); } } while (0)
+#define TP_LINPSF_FIT2(S, SLO) do { \
+	TP_LAUNCH(ctx, TPK_LINPSF_FIT, (tp_linpsf_fit2_kernel<S, SLO>), grid2, block2, 0, a, (const StarPlan*)h.plans, (const int32_t*)h.todo, (const double*)d_store, (const int32_t*)h.order); \
+	TP_LAUNCH_CHECK(ctx, "tp_linpsf_fit2_kernel"); } while (0)
+#define TP_LINPSF_DIRECT(S, SLO) do { \
+	TP_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(tp_linpsf_fit_direct_kernel<S, SLO>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)table_lds(a))); \
+	TP_LAUNCH(ctx, TPK_LINPSF_FIT_DIRECT, (tp_linpsf_fit_direct_kernel<S, SLO>), grid, block, table_lds(a), a, (const int32_t*)h.todo); \
+	TP_LAUNCH_CHECK(ctx, "tp_linpsf_fit_direct_kernel"); \
+	TP_LAUNCH(ctx, TPK_LINPSF_FIN, (tp_linpsf_finalize_kernel<S, SLO>), dim3((unsigned)n_targets), dim3(kFinThreads), fin_lds(a), fa); \
+	TP_LAUNCH_CHECK(ctx, "tp_linpsf_finalize_kernel"); } while (0)
+
+// Polynomial path: plan (boxes, item counts, the order of the cadences, the matrix-core lists) and the totals the host needs to
+// size the store and the launches.  `use_mfma`: the matrix-core fit is on and can take this batch.
+int run_plan(tp_ctx* ctx, const FitArgs& a, int n_targets, const PlanScratch& h, int use_mfma, unsigned long long (&totals)[kTotCount])
+{
+	const int max_origins = 36;   // a star that visits more table origins sends its target to the direct kernel
+	// cadences sorted by origin in LDS (8 bytes per slot, next power of two); beyond 8192 cadences the order stays natural
+	int sort_n = 64;
+	while (sort_n < a.n_cad) sort_n <<= 1;
+	if (sort_n > 8192) sort_n = 0;
+	TP_HIP(ctx, hipMemsetAsync(h.todo, 0, h.todo_bytes, ctx->stream));
+	TP_HIP(ctx, hipMemsetAsync(h.total, 0, kTotalWords * sizeof(unsigned long long), ctx->stream));
+	// The uniform-grid kernels (all but the any-grid ones) need the SPOC layout of the PRF grid: 9 samples per pixel, the table
+	// resident in LDS, the cut-off inside the evenly spaced part of the knots.  Whether that holds is decided where the knots are.
+	// (a table with axes of different lengths is never the SPOC layout: the general kernels, the only ones that read a.ny)
+	const int force = (a.n != a.ny || a.n < 32 || a.n > 140 || !(a.cutoff <= 5.25)) ? 1 : 0;
+	hipLaunchKernelGGL(tp_linpsf_grid_kernel, dim3(1), dim3(64), 0, ctx->stream, a.knots_x, a.knots_y, a.n, a.cutoff, force, h.total);
+	TP_LAUNCH_CHECK(ctx, "tp_linpsf_grid_kernel");
+	if (sort_n > 4096) TP_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(tp_linpsf_plan_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sort_n * sizeof(unsigned long long))));
+	TP_LAUNCH(ctx, TPK_LINPSF_PLAN, tp_linpsf_plan_kernel, dim3((unsigned)n_targets), dim3(256), (size_t)sort_n * sizeof(unsigned long long), a, h.plans, h.todo, h.total, max_origins, h.order, sort_n,
+		h.mplans, h.ulist, h.usig, use_mfma, h.lists, n_targets, h.segs, h.seglists);
+	TP_LAUNCH_CHECK(ctx, "tp_linpsf_plan_kernel");
+	// one round trip in the middle of the call (measured: the plan kernel's 0.2 ms and the launch of the coefficient kernel hide
+	// it -- the step's wall time equals the sum of its kernels to 0.05 ms)
+	TP_HIP(ctx, hipMemcpyAsync(totals, h.total, sizeof(totals), hipMemcpyDeviceToHost, ctx->stream));
+	TP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	int64_t* c = ctx->linpsf_counts;   // tp_linpsf_last_counts
+	for (int i = 0; i < 16; ++i) c[i] = 0;
+	for (int k = 0; k < kMfmaClasses; ++k) {
+		c[0] += (int64_t)totals[kTotClass0 + k]; c[1] += (int64_t)totals[kTotSeg0 + k];
+		c[5 + k] = (int64_t)totals[kTotClass0 + k]; c[9 + k] = (int64_t)totals[kTotSeg0 + k];
+	}
+	c[2] = (int64_t)totals[kTotPolyTargets]; c[3] = (int64_t)totals[kTotDirectTargets];
+	return TP_OK;
+}
+
+int linpsf_fit_impl(tp_ctx* ctx, const FitArgs& a, FinArgs fa, int n_targets, int max_stars)
+{
+	PlanScratch h;
+	carve_plan_scratch(0, (size_t)n_targets, (size_t)a.n_cad, ctx->linpsf_path == 1, h);
+	TP_REQUIRE(ctx, tp_ctx_scratch(ctx, h.bytes) != nullptr, "tp_linpsf_fit: out of device memory for the plan");
+	carve_plan_scratch(reinterpret_cast<uintptr_t>(ctx->scratch), (size_t)n_targets, (size_t)a.n_cad, ctx->linpsf_path == 1, h);
+	// the matrix-core path needs the table in LDS (beside the 2 KB job list of its coefficient kernel), and 32-bit element offsets
+	// into a target's cube
+	const int use_mfma = (ctx->linpsf_path == 1 && a.n == a.ny && (size_t)a.n * a.n * sizeof(double) + 2048 <= 160 * 1024
+		&& (int64_t)a.height * a.width * a.t_pitch < (1ll << 30)) ? 1 : 0;
+	fa.todo = use_mfma ? h.todo : nullptr;
+	unsigned long long totals[kTotCount] = {};
+	TP_TRY(run_plan(ctx, a, n_targets, h, use_mfma, totals));
+	if (totals[kTotGeneral] != 0) return fit_any_grid(ctx, a, fa, n_targets, h);
+
+	// the coefficient store (polynomial items, the matrix-core images behind them), grown to what the plan counted
+	const size_t poly_doubles = ((size_t)totals[kTotPolyItems] * 25 + 32 + 63) & ~(size_t)63;
+	const size_t store_need = (poly_doubles + (size_t)totals[kTotKDoubles] + 64) * sizeof(double);
+	if (ctx->store_bytes < store_need) {
+		if (ctx->store) (void)hipFree(ctx->store);
+		ctx->store = nullptr; ctx->store_bytes = 0;
+		TP_HIP(ctx, tp_device_alloc(ctx, &ctx->store, store_need));
+		ctx->store_bytes = store_need;
+	}
+	double* d_store = static_cast<double*>(ctx->store);
+	double* d_kstore = d_store + poly_doubles;
+	const size_t coef_lds = (size_t)a.n * a.n * sizeof(double);
+	TP_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(tp_linpsf_coef_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)coef_lds));
+	TP_LAUNCH(ctx, TPK_LINPSF_COEF, tp_linpsf_coef_kernel, dim3((unsigned)n_targets), dim3(kCoefThreads), coef_lds, a, (const StarPlan*)h.plans, (const int32_t*)h.todo, d_store,
+		(const MPlan*)h.mplans, (const uint16_t*)h.ulist, (const uint8_t*)h.usig, d_kstore, (const SegPlan*)h.segs);
+	TP_LAUNCH_CHECK(ctx, "tp_linpsf_coef_kernel");
+	// the matrix-core fit of the targets marked for it (up to 4 stars, up to 256 reachable pixels)
+	if (use_mfma) {
+		TP_TRY(fit_mfma_launch(ctx, a, n_targets, totals + kTotSeg0, h.segs, h.seglists, h.mplans, h.ulist, h.usig, d_kstore, h.alast));
+		TP_LINPSF_FINM(1); TP_LINPSF_FINM(2); TP_LINPSF_FINM(3); TP_LINPSF_FINM(4);
+	}
+	if (totals[kTotPolyTargets] > 0) {   // none when the matrix-core fit has taken every target
+		const int nblk = (a.n_cad + 255) / 256;
+		const dim3 grid2((unsigned)n_targets, (unsigned)nblk), block2((unsigned)((((a.n_cad + nblk - 1) / nblk) + 63) / 64 * 64));
+		TP_LINPSF_FIT2(1, 0);
+		if (max_stars > 1) TP_LINPSF_FIT2(2, 2);
+		if (max_stars > 2) TP_LINPSF_FIT2(3, 3);
+		if (max_stars > 3) TP_LINPSF_FIT2(4, 4);
+		if (max_stars > 4) TP_LINPSF_FIT2(8, 5);
+	}
+	// the direct kernel (targets the plan flagged for it) and the finalisation of every vector-ALU target, by coarser classes
+	if (totals[kTotPolyTargets] + totals[kTotDirectTargets] > 0) {
+		const int nblk = (a.n_cad + 511) / 512;
+		const dim3 grid((unsigned)n_targets, (unsigned)nblk), block((unsigned)((((a.n_cad + nblk - 1) / nblk) + 63) / 64 * 64));
+		TP_LINPSF_DIRECT(2, 0);
+		if (max_stars > 2) TP_LINPSF_DIRECT(4, 3);
+		if (max_stars > 4) TP_LINPSF_DIRECT(8, 5);
+	}
+	if (max_stars > kMaxStars) TP_TRY(fit_many_star_targets(ctx, a, fa, n_targets, h));
+	return TP_OK;
+}
+#undef TP_LINPSF_FINM
+#undef TP_LINPSF_FIT2
+#undef TP_LINPSF_DIRECT
+#undef TP_TRY
+
+} // namespace
+
+// d_coef [n_targets][n_coef_axis_x * n_coef_axis_y], d_knots_x [n_coef_axis_x + 4], d_knots_y [n_coef_axis_y + 4]: psf.py:119 takes any
+// RectBivariateSpline; a PRF spline that is not on the SPOC grid (axes of different lengths among them) is fitted by the any-grid kernels
+extern "C" int tp_linpsf_fit_xy(tp_ctx* ctx, const tp_cube_desc* desc, const float* d_images,
 	const float* d_subtract, int64_t subtract_pitch,
-	const double* d_coef, const double* d_knots_x, const double* d_knots_y, int32_t n_coef_axis, int32_t n_coef_axis_y, int32_t max_stars,
+	const double* d_coef, const double* d_knots_x, const double* d_knots_y, int32_t n_coef_axis_x, int32_t n_coef_axis_y, int32_t max_stars,
 	const int64_t* d_star_offsets, const int32_t* d_target_index,
 	const double* d_pos_row, const double* d_pos_col, int64_t pos_pitch, double cutoff_radius,
 	double* d_flux, double* d_flux_err, double* d_fluxes_all, int64_t out_pitch,
@@ -1577,7 +1791,7 @@ static int linpsf_fit_impl(tp_ctx* ctx, const tp_cube_desc* desc, const float* d
 	TP_REQUIRE(ctx, d_flux && d_flux_err && d_fluxes_all && d_contamination && d_status, "tp_linpsf_fit: null output pointer");
 	TP_REQUIRE(ctx, pos_pitch >= desc->n_cad && out_pitch >= desc->n_cad, "tp_linpsf_fit: pitch < n_cad");
 	TP_REQUIRE(ctx, d_subtract == nullptr || subtract_pitch >= desc->n_cad, "tp_linpsf_fit: bad subtract pitch");
-	TP_REQUIRE(ctx, n_coef_axis >= 4 && n_coef_axis <= 2048 && n_coef_axis_y >= 4 && n_coef_axis_y <= 2048, "tp_linpsf_fit: coefficient table must be 4..2048 per axis");
+	TP_REQUIRE(ctx, n_coef_axis_x >= 4 && n_coef_axis_x <= 2048 && n_coef_axis_y >= 4 && n_coef_axis_y <= 2048, "tp_linpsf_fit: coefficient table must be 4..2048 per axis");
 	TP_REQUIRE(ctx, max_stars >= 1 && max_stars <= kMaxManyStars, "tp_linpsf_fit: at most 64 stars fitted per target");
 	TP_REQUIRE(ctx, cutoff_radius > 0, "tp_linpsf_fit: cutoff_radius must be positive (infinity = no cut-off, psf.py:142 `cutoff_radius is None`)");
 	if (desc->n_targets == 0 || desc->n_cad == 0) return TP_OK;
@@ -1585,216 +1799,16 @@ static int linpsf_fit_impl(tp_ctx* ctx, const tp_cube_desc* desc, const float* d
 	FitArgs a;
 	a.images = d_images; a.subtract = d_subtract; a.subtract_pitch = subtract_pitch;
 	a.n_cad = desc->n_cad; a.height = desc->height; a.width = desc->width; a.t_pitch = desc->t_pitch;
-	a.coef = d_coef; a.knots_x = d_knots_x; a.knots_y = d_knots_y; a.n = n_coef_axis; a.ny = n_coef_axis_y;
+	a.coef = d_coef; a.knots_x = d_knots_x; a.knots_y = d_knots_y; a.n = n_coef_axis_x; a.ny = n_coef_axis_y;
 	a.star_offsets = d_star_offsets; a.target_index = d_target_index;
 	a.pos_row = d_pos_row; a.pos_col = d_pos_col; a.pos_pitch = pos_pitch; a.cutoff = cutoff_radius;
 	a.flux = d_flux; a.flux_err = d_flux_err; a.fluxes_all = d_fluxes_all; a.out_pitch = out_pitch;
-
-	const size_t shmem = ((size_t)n_coef_axis * n_coef_axis_y + (n_coef_axis + 4) + (n_coef_axis_y + 4)) * sizeof(double);
-	const int nblk = (desc->n_cad + 511) / 512;
-	int threads = (((desc->n_cad + nblk - 1) / nblk) + 63) / 64 * 64;
-	dim3 grid((unsigned)desc->n_targets, (unsigned)nblk), block((unsigned)threads);
-	const size_t shmem_fin = (((size_t)n_coef_axis + 4) + ((size_t)n_coef_axis_y + 4) + 256) * sizeof(double);
 	FinArgs fa; fa.f = a; fa.contamination = d_contamination; fa.status = d_status; fa.fluxes_mean = d_fluxes_mean; fa.todo = nullptr;
-	// polynomial path: plan (boxes, item counts) -> coefficient store -> fit; targets whose stars visit more table origins than
-	// max_origins are flagged and redone by the general kernel
-	const int max_origins = 36;
-	const size_t todo_bytes = ((size_t)desc->n_targets * sizeof(int32_t) + 255) & ~(size_t)255;
-	const size_t plan_bytes = ((size_t)desc->n_targets * kMaxStars * sizeof(StarPlan) + 255) & ~(size_t)255;
-	const size_t order_bytes = ((size_t)desc->n_targets * desc->n_cad * sizeof(int32_t) + 255) & ~(size_t)255;
-	const size_t mplan_bytes = ((size_t)desc->n_targets * sizeof(MPlan) + 255) & ~(size_t)255;
-	const size_t ulist_bytes = ((size_t)desc->n_targets * kMfmaPixels * sizeof(uint16_t) + 255) & ~(size_t)255;
-	const size_t usig_bytes = ((size_t)desc->n_targets * kMfmaPixels * sizeof(uint8_t) + 255) & ~(size_t)255;
-	const size_t lists_bytes = ((size_t)desc->n_targets * kMfmaClasses * sizeof(int32_t) + 255) & ~(size_t)255;
-	const size_t segs_bytes = ((size_t)desc->n_targets * kMfmaSegs * sizeof(SegPlan) + 255) & ~(size_t)255;
-	const size_t seglists_bytes = ((size_t)desc->n_targets * kMfmaSegs * kMfmaClasses * sizeof(int32_t) + 255) & ~(size_t)255;
-	const size_t alast_bytes = (ctx->linpsf_path == 1) ? (((size_t)desc->n_targets * kMfmaStars * kMfmaPixels * sizeof(double) + 255) & ~(size_t)255) : 0;
-	const size_t head_bytes = todo_bytes + plan_bytes + 256 + order_bytes + mplan_bytes + ulist_bytes + usig_bytes + lists_bytes + segs_bytes + seglists_bytes + alast_bytes;
-	static_assert(kTotCount * sizeof(unsigned long long) <= 256, "the counters fit their block");
-	TP_REQUIRE(ctx, tp_ctx_scratch(ctx, head_bytes) != nullptr, "tp_linpsf_fit: out of device memory for the plan");
-	char* sbase = static_cast<char*>(ctx->scratch);
-	int32_t* d_todo = reinterpret_cast<int32_t*>(sbase);
-	StarPlan* d_plans = reinterpret_cast<StarPlan*>(sbase + todo_bytes);
-	unsigned long long* d_total = reinterpret_cast<unsigned long long*>(sbase + todo_bytes + plan_bytes);
-	int32_t* d_order = reinterpret_cast<int32_t*>(sbase + todo_bytes + plan_bytes + 256);
-	MPlan* d_mplans = reinterpret_cast<MPlan*>(sbase + todo_bytes + plan_bytes + 256 + order_bytes);
-	uint16_t* d_ulist = reinterpret_cast<uint16_t*>(sbase + todo_bytes + plan_bytes + 256 + order_bytes + mplan_bytes);
-	uint8_t* d_usig = reinterpret_cast<uint8_t*>(sbase + todo_bytes + plan_bytes + 256 + order_bytes + mplan_bytes + ulist_bytes);
-	int32_t* d_lists = reinterpret_cast<int32_t*>(sbase + todo_bytes + plan_bytes + 256 + order_bytes + mplan_bytes + ulist_bytes + usig_bytes);
-	SegPlan* d_segs = reinterpret_cast<SegPlan*>(sbase + todo_bytes + plan_bytes + 256 + order_bytes + mplan_bytes + ulist_bytes + usig_bytes + lists_bytes);
-	int32_t* d_seglists = reinterpret_cast<int32_t*>(sbase + todo_bytes + plan_bytes + 256 + order_bytes + mplan_bytes + ulist_bytes + usig_bytes + lists_bytes + segs_bytes);
-	double* d_alast = reinterpret_cast<double*>(sbase + todo_bytes + plan_bytes + 256 + order_bytes + mplan_bytes + ulist_bytes + usig_bytes + lists_bytes + segs_bytes + seglists_bytes);
-	// cadences sorted by origin in LDS (8 bytes per slot, next power of two); beyond 8192 cadences the order stays natural
-	int sort_n = 64;
-	while (sort_n < desc->n_cad) sort_n <<= 1;
-	if (sort_n > 8192) sort_n = 0;
-	// the matrix-core path needs the table in LDS (beside the job list of its coefficient kernel), and 32-bit element offsets
-	// into a target's cube
-	const int use_mfma = (ctx->linpsf_path == 1 && n_coef_axis == n_coef_axis_y && (size_t)n_coef_axis * n_coef_axis * sizeof(double) + 2048 <= 160 * 1024   // (2 KB: the kernel's job table)
-		&& (int64_t)desc->height * desc->width * desc->t_pitch < (1ll << 30)) ? 1 : 0;
-	fa.todo = use_mfma ? d_todo : nullptr;
-	TP_HIP(ctx, hipMemsetAsync(d_todo, 0, todo_bytes, ctx->stream));
-	TP_HIP(ctx, hipMemsetAsync(d_total, 0, 256, ctx->stream));
-	// the uniform-grid kernels (everything below up to the many-star kernel) need the SPOC layout of the PRF grid: 9 samples per
-	// pixel, the table resident in LDS, the cut-off inside the evenly spaced part of the knots.  Whether that holds is decided
-	// where the knots are; anything else is fitted by the general kernels with the FITPACK box integral itself
-	{
-		// (a table with axes of different lengths is never the SPOC layout: the general kernels, the only ones that read a.ny)
-		const int force = (n_coef_axis != n_coef_axis_y || n_coef_axis < 32 || n_coef_axis > 140 || !(cutoff_radius <= 5.25)) ? 1 : 0;
-		hipLaunchKernelGGL(tp_linpsf_grid_kernel, dim3(1), dim3(64), 0, ctx->stream, d_knots_x, d_knots_y, (int)n_coef_axis, cutoff_radius, force, d_total);
-		TP_LAUNCH_CHECK(ctx, "tp_linpsf_grid_kernel");
-	}
-	if (sort_n > 4096) TP_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(tp_linpsf_plan_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sort_n * sizeof(unsigned long long))));
-	TP_LAUNCH(ctx, TPK_LINPSF_PLAN, tp_linpsf_plan_kernel, dim3((unsigned)desc->n_targets), dim3(256), (size_t)sort_n * sizeof(unsigned long long), a, d_plans, d_todo, d_total, max_origins, d_order, sort_n,
-		d_mplans, d_ulist, d_usig, use_mfma, d_lists, (int)desc->n_targets, d_segs, d_seglists);
-	TP_LAUNCH_CHECK(ctx, "tp_linpsf_plan_kernel");
-	// items of the polynomial store, doubles of the matrix-core store behind it, targets and segments per class.  The host needs
-	// them to size the store and the launches: one round trip in the middle of the call (measured: the plan kernel's 0.2 ms and
-	// the launch of the coefficient kernel hide it -- the step's wall time equals the sum of its kernels to 0.05 ms)
-	unsigned long long totals[kTotCount] = {};
-	TP_HIP(ctx, hipMemcpyAsync(totals, d_total, sizeof(totals), hipMemcpyDeviceToHost, ctx->stream));
-	TP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	{
-		int64_t* c = ctx->linpsf_counts;
-		for (int i = 0; i < 16; ++i) c[i] = 0;
-		for (int k = 0; k < kMfmaClasses; ++k) {
-			c[0] += (int64_t)totals[kTotClass0 + k]; c[1] += (int64_t)totals[kTotSeg0 + k];
-			c[5 + k] = (int64_t)totals[kTotClass0 + k]; c[9 + k] = (int64_t)totals[kTotSeg0 + k];
-		}
-		c[2] = (int64_t)totals[kTotPolyTargets]; c[3] = (int64_t)totals[kTotDirectTargets];
-	}
-	if (totals[kTotGeneral] != 0) {
-		// ---- any grid, any cut-off: every target through the run-time sized kernel (normal equations in an HBM scratch) with the
-		// FITPACK box integral, a few GiB of scratch at a time
-		std::vector<int64_t> off((size_t)desc->n_targets + 1);
-		TP_HIP(ctx, hipMemcpyAsync(off.data(), d_star_offsets, off.size() * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
-		TP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-		int smax = 1;
-		for (int t = 0; t < desc->n_targets; ++t) {
-			const int ns = (int)(off[t + 1] - off[t]);
-			TP_REQUIRE(ctx, ns >= 0 && ns <= kMaxManyStars, "tp_linpsf_fit: a target has more than 64 fitted stars");
-			if (ns > smax) smax = ns;
-		}
-		const int table_in_lds = (shmem <= (size_t)160 * 1024) ? 1 : 0;
-		const size_t shmem_g = table_in_lds ? shmem : ((size_t)(n_coef_axis + 4) + (size_t)(n_coef_axis_y + 4)) * sizeof(double);
-		const int threads_m = 256, nblk_m = (desc->n_cad + threads_m - 1) / threads_m;
-		const size_t per_target = (size_t)(2 * smax * smax + 15 * smax) * sizeof(double) * nblk_m * threads_m;
-		int64_t chunk = (int64_t)(((size_t)4 << 30) / per_target);
-		if (chunk < 1) chunk = 1;
-		if (chunk > desc->n_targets) chunk = desc->n_targets;
-		TP_REQUIRE(ctx, tp_ctx_scratch(ctx, head_bytes + per_target * (size_t)chunk + 256) != nullptr, "tp_linpsf_fit: out of device memory for the scratch of the general kernels");
-		double* d_scr = reinterpret_cast<double*>(static_cast<char*>(ctx->scratch) + head_bytes);
-		TP_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(tp_linpsf_fit_many_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem_g));
-		const size_t shmem_fin_m = shmem_fin + kMaxManyStars * sizeof(double);
-		for (int64_t first = 0; first < desc->n_targets; first += chunk) {
-			const int64_t cnt = (desc->n_targets - first < chunk) ? (desc->n_targets - first) : chunk;
-			TP_LAUNCH(ctx, TPK_LINPSF_FIT_DIRECT, tp_linpsf_fit_many_kernel<true>, dim3((unsigned)cnt, (unsigned)nblk_m), dim3(threads_m), shmem_g, a, (const int32_t*)nullptr, (int)first, smax, d_scr, table_in_lds);
-			TP_LAUNCH_CHECK(ctx, "tp_linpsf_fit_many_kernel (general)");
-			TP_LAUNCH(ctx, TPK_LINPSF_FIN, tp_linpsf_finalize_many_kernel<true>, dim3((unsigned)cnt), dim3(256), shmem_fin_m, fa, (const int32_t*)nullptr, (int)first);
-			TP_LAUNCH_CHECK(ctx, "tp_linpsf_finalize_many_kernel (general)");
-		}
-		ctx->linpsf_counts[13] = desc->n_targets;
-		return TP_OK;
-	}
-	const size_t poly_doubles = ((size_t)totals[kTotPolyItems] * 25 + 32 + 63) & ~(size_t)63;
-	const size_t store_need = (poly_doubles + (size_t)totals[kTotKDoubles] + 64) * sizeof(double);
-	if (ctx->store_bytes < store_need) {
-		if (ctx->store) (void)hipFree(ctx->store);
-		ctx->store = nullptr; ctx->store_bytes = 0;
-		TP_HIP(ctx, tp_device_alloc(ctx, &ctx->store, store_need));
-		ctx->store_bytes = store_need;
-	}
-	double* d_store = static_cast<double*>(ctx->store);
-	double* d_kstore = d_store + poly_doubles;
-	const size_t coef_lds = (size_t)n_coef_axis * n_coef_axis * sizeof(double);
-	TP_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(tp_linpsf_coef_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)coef_lds));
-	TP_LAUNCH(ctx, TPK_LINPSF_COEF, tp_linpsf_coef_kernel, dim3((unsigned)desc->n_targets), dim3(kCoefThreads), coef_lds, a, (const StarPlan*)d_plans, (const int32_t*)d_todo, d_store,
-		(const MPlan*)d_mplans, (const uint16_t*)d_ulist, (const uint8_t*)d_usig, d_kstore, (const SegPlan*)d_segs);
-	TP_LAUNCH_CHECK(ctx, "tp_linpsf_coef_kernel");
-	// the matrix-core fit of the targets marked for it (up to 4 stars, up to 256 reachable pixels)
-	if (use_mfma) {
-		const int rc = fit_mfma_launch(ctx, a, desc->n_targets, totals + kTotSeg0, totals + kTotClass0, d_segs, d_seglists, d_mplans, d_ulist, d_usig, d_kstore, d_alast);
-		if (rc != TP_OK) return rc;
-#define TP_LINPSF_FINM(CLS, SS) do { \
-			if (totals[kTotClass0 + CLS] > 0) { \
-				TP_LAUNCH(ctx, TPK_LINPSF_FIN, (tp_linpsf_finalize_m_kernel<SS>), dim3((unsigned)totals[kTotClass0 + CLS]), dim3(256), 0, fa, (const int32_t*)(d_lists + (size_t)(CLS) * desc->n_targets), \
-					(const MPlan*)d_mplans, (const double*)d_alast); \
-				TP_LAUNCH_CHECK(ctx, "tp_linpsf_finalize_m_kernel"); \
-			} \
-		} while (0)
-		TP_LINPSF_FINM(0, 1); TP_LINPSF_FINM(1, 2); TP_LINPSF_FINM(2, 3); TP_LINPSF_FINM(3, 4);
-#undef TP_LINPSF_FINM
-	}
-	const int nblk2 = (desc->n_cad + 255) / 256;
-	const int threads2 = (((desc->n_cad + nblk2 - 1) / nblk2) + 63) / 64 * 64;
-#define TP_LINPSF_FIT2(SS, SL) do { \
-		TP_LAUNCH(ctx, TPK_LINPSF_FIT, (tp_linpsf_fit2_kernel<SS, SL>), dim3((unsigned)desc->n_targets, (unsigned)nblk2), dim3((unsigned)threads2), 0, a, (const StarPlan*)d_plans, (const int32_t*)d_todo, (const double*)d_store, (const int32_t*)d_order); \
-		TP_LAUNCH_CHECK(ctx, "tp_linpsf_fit2_kernel"); \
-	} while (0)
-#define TP_LINPSF_LAUNCH(SS, SL) do { \
-		TP_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(tp_linpsf_fit_direct_kernel<SS, SL>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem)); \
-		TP_LAUNCH(ctx, TPK_LINPSF_FIT_DIRECT, (tp_linpsf_fit_direct_kernel<SS, SL>), grid, block, shmem, a, (const int32_t*)d_todo); \
-		TP_LAUNCH_CHECK(ctx, "tp_linpsf_fit_direct_kernel"); \
-		TP_LAUNCH(ctx, TPK_LINPSF_FIN, (tp_linpsf_finalize_kernel<SS, SL>), dim3((unsigned)desc->n_targets), dim3(256), shmem_fin, fa); \
-		TP_LAUNCH_CHECK(ctx, "tp_linpsf_finalize_kernel"); \
-	} while (0)
-	// one instantiation per star count (the normal equations and the registers of a 1-star target are not those of a 4-star
-	// one); a workgroup whose target belongs to another class exits at once
-	if (totals[kTotPolyTargets] > 0) {   // none when the matrix-core fit has taken every target
-		TP_LINPSF_FIT2(1, 0);
-		if (max_stars > 1) TP_LINPSF_FIT2(2, 2);
-		if (max_stars > 2) TP_LINPSF_FIT2(3, 3);
-		if (max_stars > 3) TP_LINPSF_FIT2(4, 4);
-		if (max_stars > 4) TP_LINPSF_FIT2(8, 5);
-	}
-	// the general kernel (flagged targets) and the finalisation, by coarser classes
-	if (totals[kTotPolyTargets] + totals[kTotDirectTargets] > 0) {
-		TP_LINPSF_LAUNCH(2, 0);
-		if (max_stars > 2) TP_LINPSF_LAUNCH(4, 3);
-		if (max_stars > 4) TP_LINPSF_LAUNCH(8, 5);
-	}
-#undef TP_LINPSF_FIT2
-#undef TP_LINPSF_LAUNCH
-	if (max_stars > kMaxStars) {
-		// targets with more than 8 fitted stars (rare: crowded fields): listed on the host from the star offsets, fitted by
-		// the run-time sized kernel out of an HBM scratch
-		std::vector<int64_t> off((size_t)desc->n_targets + 1);
-		TP_HIP(ctx, hipMemcpyAsync(off.data(), d_star_offsets, off.size() * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
-		TP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-		std::vector<int32_t> big;
-		int smax = 0;
-		for (int t = 0; t < desc->n_targets; ++t) {
-			const int ns = (int)(off[t + 1] - off[t]);
-			TP_REQUIRE(ctx, ns <= kMaxManyStars, "tp_linpsf_fit: a target has more than 64 fitted stars");
-			if (ns > kMaxStars) { big.push_back(t); if (ns > smax) smax = ns; }
-		}
-		ctx->linpsf_counts[4] = (int64_t)big.size();
-		if (!big.empty()) {
-			const int threads = 256, nblk_m = (desc->n_cad + threads - 1) / threads;
-			const size_t per_thread = (size_t)(2 * smax * smax + 15 * smax) * sizeof(double);
-			const size_t list_bytes = (big.size() * sizeof(int32_t) + 255) & ~(size_t)255;
-			const size_t head = head_bytes;
-			const size_t need = head + list_bytes + per_thread * big.size() * nblk_m * threads + 256;
-			// the scratch also holds d_todo at its start: grow it BEFORE the class kernels' flags could be lost -- they are done
-			TP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-			TP_REQUIRE(ctx, tp_ctx_scratch(ctx, need) != nullptr, "tp_linpsf_fit: out of device memory for the many-star scratch");
-			char* base = static_cast<char*>(ctx->scratch) + head;
-			int32_t* d_big = reinterpret_cast<int32_t*>(base);
-			double* d_scr = reinterpret_cast<double*>(base + list_bytes);
-			TP_HIP(ctx, hipMemcpyAsync(d_big, big.data(), big.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-			TP_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(tp_linpsf_fit_many_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-			TP_LAUNCH(ctx, TPK_LINPSF_FIT_DIRECT, tp_linpsf_fit_many_kernel<false>, dim3((unsigned)big.size(), (unsigned)nblk_m), dim3(threads), shmem, a, (const int32_t*)d_big, 0, smax, d_scr, 1);
-			TP_LAUNCH_CHECK(ctx, "tp_linpsf_fit_many_kernel");
-			const size_t shmem_fin_m = shmem_fin + kMaxManyStars * sizeof(double);
-			TP_LAUNCH(ctx, TPK_LINPSF_FIN, tp_linpsf_finalize_many_kernel<false>, dim3((unsigned)big.size()), dim3(256), shmem_fin_m, fa, (const int32_t*)d_big, 0);
-			TP_LAUNCH_CHECK(ctx, "tp_linpsf_finalize_many_kernel");
-			TP_HIP(ctx, hipStreamSynchronize(ctx->stream)); // `big` (host) must outlive the copy
-		}
-	}
-	return TP_OK;
+	return linpsf_fit_impl(ctx, a, fa, (int)desc->n_targets, (int)max_stars);
 	TP_API_END(ctx)
 }
 
+// the same for a square table (the SPOC PRF: 117 coefficients per axis)
 extern "C" int tp_linpsf_fit(tp_ctx* ctx, const tp_cube_desc* desc, const float* d_images,
 	const float* d_subtract, int64_t subtract_pitch,
 	const double* d_coef, const double* d_knots_x, const double* d_knots_y, int32_t n_coef_axis, int32_t max_stars,
@@ -1803,22 +1817,7 @@ extern "C" int tp_linpsf_fit(tp_ctx* ctx, const tp_cube_desc* desc, const float*
 	double* d_flux, double* d_flux_err, double* d_fluxes_all, int64_t out_pitch,
 	double* d_contamination, int32_t* d_status, double* d_fluxes_mean)
 {
-	return linpsf_fit_impl(ctx, desc, d_images, d_subtract, subtract_pitch, d_coef, d_knots_x, d_knots_y, n_coef_axis, n_coef_axis, max_stars,
-		d_star_offsets, d_target_index, d_pos_row, d_pos_col, pos_pitch, cutoff_radius, d_flux, d_flux_err, d_fluxes_all, out_pitch,
-		d_contamination, d_status, d_fluxes_mean);
-}
-
-// the same for a PRF spline whose two axes have different numbers of samples (psf.py:119 takes any RectBivariateSpline): d_coef
-// [n_targets][n_coef_axis_x * n_coef_axis_y], d_knots_x [n_coef_axis_x + 4], d_knots_y [n_coef_axis_y + 4]; fitted by the any-grid kernels
-extern "C" int tp_linpsf_fit_xy(tp_ctx* ctx, const tp_cube_desc* desc, const float* d_images,
-	const float* d_subtract, int64_t subtract_pitch,
-	const double* d_coef, const double* d_knots_x, const double* d_knots_y, int32_t n_coef_axis_x, int32_t n_coef_axis_y, int32_t max_stars,
-	const int64_t* d_star_offsets, const int32_t* d_target_index,
-	const double* d_pos_row, const double* d_pos_col, int64_t pos_pitch, double cutoff_radius,
-	double* d_flux, double* d_flux_err, double* d_fluxes_all, int64_t out_pitch,
-	double* d_contamination, int32_t* d_status, double* d_fluxes_mean)
-{
-	return linpsf_fit_impl(ctx, desc, d_images, d_subtract, subtract_pitch, d_coef, d_knots_x, d_knots_y, n_coef_axis_x, n_coef_axis_y, max_stars,
+	return tp_linpsf_fit_xy(ctx, desc, d_images, d_subtract, subtract_pitch, d_coef, d_knots_x, d_knots_y, n_coef_axis, n_coef_axis, max_stars,
 		d_star_offsets, d_target_index, d_pos_row, d_pos_col, pos_pitch, cutoff_radius, d_flux, d_flux_err, d_fluxes_all, out_pitch,
 		d_contamination, d_status, d_fluxes_mean);
 }

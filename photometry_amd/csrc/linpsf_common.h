@@ -166,7 +166,7 @@ struct MPlan {
 // The series of a target is cut into SEGMENTS of consecutive 16-cadence tiles inside which every fitted star visits at most
 // kMfmaSpan knot intervals per axis: a star that drifts across the pixel during the series (pointing drift, velocity aberration:
 // half a pixel is 4.5 knot intervals) stays on the matrix cores, each stretch of the series with the spline of the intervals it
-// visits THEN (round 3 sent such a target to the vector-ALU kernels).  Without drift the jitter gives one segment.
+// visits THEN.  Without drift the jitter gives one segment.
 // Per (target, segment): the coefficients of ONE tensor-product quartic spline per star over its na x nb intervals
 // (linpsf_mfma.hip), laid out as the A operands of the matrix instruction: [star][rank of the tile among its tiles][step][64
 // lanes] doubles, the whole segment contiguous from `koff` (that image is copied to LDS as it is), star s from
@@ -201,7 +201,7 @@ enum { kTotPolyItems = 0, kTotKDoubles = 1, kTotPolyTargets = 2, kTotDirectTarge
 enum { kPathPoly = 0, kPathDirect = 1, kPathMfma = 2 };
 
 // linpsf_mfma.hip
-int fit_mfma_launch(tp_ctx* ctx, const FitArgs& a, int n_targets, const unsigned long long* seg_counts, const unsigned long long* class_counts, const SegPlan* d_segs,
+int fit_mfma_launch(tp_ctx* ctx, const FitArgs& a, int n_targets, const unsigned long long* seg_counts, const SegPlan* d_segs,
 	const int32_t* d_seg_lists, const MPlan* d_mplans, const uint16_t* d_ulist, const uint8_t* d_usig, const double* d_kstore, double* d_alast);
 
 } // namespace tp_linpsf

@@ -387,7 +387,7 @@ static int fit_waves(int n_cad, int most, int group_cadences)
 }
 
 // launches the matrix-core fit, one launch per star count over the segments the plan kernel has listed for it
-int fit_mfma_launch(tp_ctx* ctx, const FitArgs& a, int n_targets, const unsigned long long* seg_counts, const unsigned long long* class_counts, const SegPlan* d_segs,
+int fit_mfma_launch(tp_ctx* ctx, const FitArgs& a, int n_targets, const unsigned long long* seg_counts, const SegPlan* d_segs,
 	const int32_t* d_seg_lists, const MPlan* d_mplans, const uint16_t* d_ulist, const uint8_t* d_usig, const double* d_kstore, double* d_alast)
 {
 	// The launches are independent (one per star count): the first runs on the context's stream, the others on two side streams
@@ -406,7 +406,6 @@ int fit_mfma_launch(tp_ctx* ctx, const FitArgs& a, int n_targets, const unsigned
 	// (the workgroup is sized for the whole series also where the class has several segments per target: sizing it for the mean
 	// segment -- fewer wavefronts, a fuller last round -- measured slower, 7.5 against 6.9 ms on the drift scene: the classes with
 	// two and more stars hold one workgroup per CU, and its wavefronts are the CU's occupancy)
-	(void)class_counts;
 #define TP_FITM(CLS, SS, TT, WW, LDS) do { \
 		if (seg_counts[CLS] > 0 && err == hipSuccess && streams[used % 3] != nullptr) { \
 			const int si = used++ % 3; \
