@@ -106,8 +106,11 @@ __global__ __launch_bounds__(NTHR, MINW) void tp_linpsf_fitm_kernel(FitArgs a, c
 	int na[S], nb[S], nk[S], kbase[S], axmin[S], bymin[S];
 #pragma unroll
 	for (int s = 0; s < S; ++s) {
-		tl[s] = mp.tiles[s]; etl[s] = mp.edge_tiles[s];
 		na[s] = sg.na[s]; nb[s] = sg.nb[s];
+		// a star without a valid position in the whole segment (na == 0) has NO blocks in the segment's image (plan kernel: ksub[s]
+		// is where the next star's begin, or the end of the image): it reaches no tile here, its columns stay zero.  Its basis
+		// products are zero too, but 0 times whatever lies in LDS behind the image is not.
+		tl[s] = (na[s] > 0) ? mp.tiles[s] : 0u; etl[s] = (na[s] > 0) ? mp.edge_tiles[s] : 0u;
 		nk[s] = mfma_steps(na[s], nb[s]);
 		kbase[s] = (int)sg.ksub[s] * 64;
 		axmin[s] = sg.axmin[s]; bymin[s] = sg.bymin[s];

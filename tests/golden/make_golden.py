@@ -6,7 +6,11 @@ Generate the golden vectors in this directory by EXECUTING THE REFERENCE'S OWN C
 inputs.  Runs only in the dev container; the ``.npz`` files it writes are data
 (inputs + the reference's outputs) and are committed.  Usage::
 
-    python tests/golden/make_golden.py
+    python tests/golden/make_golden.py [--out DIR] [NAME ...]
+
+writes every fixture (or the named ones) into DIR, by default this directory.  ``tests/test_golden_regenerates.py`` runs
+it into a temporary directory and holds what it writes to the committed files: in the default order, in reverse and one
+fixture at a time.
 
 Fixtures:
 
@@ -49,6 +53,7 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
+OUT = HERE # where the fixtures are written: ``--out DIR``, default this directory
 sys.path.insert(0, HERE)
 sys.path.insert(0, ROOT)
 
@@ -83,6 +88,10 @@ from photometry import STATUS # noqa: E402
 ap_module = sys.modules['photometry.AperturePhotometry.photometry'] # noqa: E402
 k2p2v2 = sys.modules['photometry.AperturePhotometry.k2p2v2'] # noqa: E402
 AperturePhotometry = ap_module.AperturePhotometry # noqa: E402
+# ``ap_module.k2p2`` IS the k2p2v2 module: golden_aperture / golden_diagnostics replace its k2p2FixFromSum by prescribed masks,
+# so the reference's own function is taken once, here, and put back from this name when they are done.
+assert ap_module.k2p2 is k2p2v2
+_real_k2p2 = k2p2v2.k2p2FixFromSum
 from photometry.linpsf_photometry import LinPSFPhotometry, lsfit # noqa: E402
 from photometry.psf import PSF # noqa: E402
 from photometry.BasePhotometry import BasePhotometry # noqa: E402
@@ -90,6 +99,11 @@ from photometry import quality as refquality, utilities as refutil # noqa: E402
 from scipy.interpolate import RectBivariateSpline # noqa: E402
 
 from photometry_amd import simulate # noqa: E402
+
+
+def _out(name):
+	"""Path of the fixture ``name`` under the output directory."""
+	return os.path.join(OUT, name)
 
 
 def _settings():
@@ -163,7 +177,7 @@ def golden_misc():
 	out['mmc_out'] = refutil.move_median_central(x_1d, 3)
 	X, Y = np.meshgrid(np.arange(-1, 2), np.arange(-1, 2))
 	out['ig_out'] = refutil.integratedGaussian(X, Y, 10, 0, 0)
-	np.savez_compressed(os.path.join(HERE, 'golden_misc.npz'), **out)
+	np.savez_compressed(_out('golden_misc.npz'), **out)
 	print('golden_misc', {k: np.shape(v) for k, v in out.items()})
 
 
@@ -193,7 +207,7 @@ def golden_sumimage():
 		f.Ntimes = scene.n_cad
 		f.lightcurve = {'quality': q}
 		outs.append(np.array(f.sumimage))
-	np.savez_compressed(os.path.join(HERE, 'golden_sumimage.npz'), images=scene.images, quality=q, sumimage=np.array(outs))
+	np.savez_compressed(_out('golden_sumimage.npz'), images=scene.images, quality=q, sumimage=np.array(outs))
 	print('golden_sumimage', np.array(outs).shape, 'nan count', np.isnan(outs).sum())
 
 
@@ -259,42 +273,43 @@ def golden_aperture():
 		out['cat_' + k] = v
 	out['n_cases'] = len(cases)
 
-	for n, (i, kind, mm) in enumerate(cases):
-		f = make_fake(AperturePhotometry, scene, i, S[i])
-		if kind == 'masks_shifted_catalog':
-			cat = scene.catalog_of(i)
-			cat = {k: v.copy() for k, v in cat.items()}
-			cat['row'] = cat['row'] + 4
-			cat['column'] = cat['column'] - 3
-			f._catalog = _refstub.FakeCatalog(**cat)
-			out[f'case{n}_cat_row'] = cat['row']
-			out[f'case{n}_cat_column'] = cat['column']
+	try:
+		for n, (i, kind, mm) in enumerate(cases):
+			f = make_fake(AperturePhotometry, scene, i, S[i])
+			if kind == 'masks_shifted_catalog':
+				cat = scene.catalog_of(i)
+				cat = {k: v.copy() for k, v in cat.items()}
+				cat['row'] = cat['row'] + 4
+				cat['column'] = cat['column'] - 3
+				f._catalog = _refstub.FakeCatalog(**cat)
+				out[f'case{n}_cat_row'] = cat['row']
+				out[f'case{n}_cat_column'] = cat['column']
 
-		def fake_k2p2(SumImage, _kind=kind, _mm=mm, **kwargs):
-			if _kind == 'nostars':
-				raise k2p2v2.K2P2NoStars("No flux above threshold")
-			return (None if _mm is None else np.array(_mm, dtype='float64')), 1.0
-		ap_module.k2p2.k2p2FixFromSum = fake_k2p2
-		with warnings.catch_warnings():
-			warnings.simplefilter('ignore')
-			status = AperturePhotometry.do_photometry(f)
-		out[f'case{n}_target'] = i
-		out[f'case{n}_kind'] = kind
-		out[f'case{n}_masks'] = np.zeros((0, H, W)) if mm is None else np.asarray(mm, dtype='float64')
-		out[f'case{n}_status'] = status.value
-		out[f'case{n}_flux'] = np.asarray(f.lightcurve['flux'])
-		out[f'case{n}_flux_err'] = np.asarray(f.lightcurve['flux_err'])
-		out[f'case{n}_flux_background'] = np.asarray(f.lightcurve['flux_background'])
-		out[f'case{n}_pos_centroid'] = np.asarray(f.lightcurve['pos_centroid'])
-		out[f'case{n}_final_mask'] = np.zeros((H, W), dtype=bool) if f.final_phot_mask is None else np.asarray(f.final_phot_mask, dtype=bool)
-		out[f'case{n}_has_mask'] = f.final_phot_mask is not None
-		cont = f.additional_headers.get('AP_CONT', (np.nan,))[0]
-		out[f'case{n}_contamination'] = np.float64(cont)
-		out[f'case{n}_skip_targets'] = np.asarray(f._details.get('skip_targets', []), dtype='int64')
-		print('aperture case', n, kind, 'target', i, status, 'cont', cont, 'skip', f._details.get('skip_targets'))
-	# restore
-	ap_module.k2p2.k2p2FixFromSum = k2p2v2.k2p2FixFromSum
-	np.savez_compressed(os.path.join(HERE, 'golden_aperture.npz'), **out)
+			def fake_k2p2(SumImage, _kind=kind, _mm=mm, **kwargs):
+				if _kind == 'nostars':
+					raise k2p2v2.K2P2NoStars("No flux above threshold")
+				return (None if _mm is None else np.array(_mm, dtype='float64')), 1.0
+			k2p2v2.k2p2FixFromSum = fake_k2p2
+			with warnings.catch_warnings():
+				warnings.simplefilter('ignore')
+				status = AperturePhotometry.do_photometry(f)
+			out[f'case{n}_target'] = i
+			out[f'case{n}_kind'] = kind
+			out[f'case{n}_masks'] = np.zeros((0, H, W)) if mm is None else np.asarray(mm, dtype='float64')
+			out[f'case{n}_status'] = status.value
+			out[f'case{n}_flux'] = np.asarray(f.lightcurve['flux'])
+			out[f'case{n}_flux_err'] = np.asarray(f.lightcurve['flux_err'])
+			out[f'case{n}_flux_background'] = np.asarray(f.lightcurve['flux_background'])
+			out[f'case{n}_pos_centroid'] = np.asarray(f.lightcurve['pos_centroid'])
+			out[f'case{n}_final_mask'] = np.zeros((H, W), dtype=bool) if f.final_phot_mask is None else np.asarray(f.final_phot_mask, dtype=bool)
+			out[f'case{n}_has_mask'] = f.final_phot_mask is not None
+			cont = f.additional_headers.get('AP_CONT', (np.nan,))[0]
+			out[f'case{n}_contamination'] = np.float64(cont)
+			out[f'case{n}_skip_targets'] = np.asarray(f._details.get('skip_targets', []), dtype='int64')
+			print('aperture case', n, kind, 'target', i, status, 'cont', cont, 'skip', f._details.get('skip_targets'))
+	finally:
+		k2p2v2.k2p2FixFromSum = _real_k2p2
+	np.savez_compressed(_out('golden_aperture.npz'), **out)
 
 
 #--------------------------------------------------------------------------------------------------
@@ -334,7 +349,7 @@ def golden_cutout():
 		f.Ntimes = T
 		f.hdf = FakeHDF({'images': frames})
 		cubes.append(BasePhotometry._load_cube(f, tpf_field='FLUX', hdf_group='images'))
-	np.savez_compressed(os.path.join(HERE, 'golden_cutout.npz'), frames=frames, stamps=stamps, offsets=np.array(offs), cubes=np.array(cubes))
+	np.savez_compressed(_out('golden_cutout.npz'), frames=frames, stamps=stamps, offsets=np.array(offs), cubes=np.array(cubes))
 	print('golden_cutout', np.array(cubes).shape)
 
 
@@ -367,46 +382,58 @@ def golden_diagnostics():
 	from oracle import sumimage as osum
 	S = osum.sumimage_batch(scene.images, scene.quality)
 	out = {'time': scene.time, 'quality': scene.quality, 'sumimage': S, 'n_cases': scene.n_targets}
-	for i in range(scene.n_targets):
-		cat = scene.catalog_of(i)
-		c = np.column_stack((cat['column_stamp'], cat['row_stamp'], cat['tmag']))
-		mm, _ = ok2p2.k2p2FixFromSum(S[i], catalog=c, thresh=0.8, min_no_pixels_in_mask=4, min_for_cluster=4,
-			cluster_radius=np.sqrt(2) + np.finfo(np.float64).eps, segmentation=True, ws_blur=0.5, ws_thres=0,
-			ws_footprint=3, extend_overflow=True)
-		if i == 5: # a mask that touches the stamp edge: edge_flux != 0
-			mm = np.zeros((1, H, W)); mm[0, 0:7, 2:9] = 1
-		if i == 6: # NaN fluxes in some cadences (a NaN pixel inside the mask)
-			main = np.asarray(mm, dtype=bool)[0]
-			rr, cc = np.argwhere(main)[0]
-			scene.images[i, rr, cc, [3, 20, 21, 50]] = np.nan
-		f = make_fake(AperturePhotometry, scene, i, S[i])
-		f.lightcurve = FakeLC(f.lightcurve)
-		f._status = STATUS.UNKNOWN
+	try:
+		for i in range(scene.n_targets):
+			cat = scene.catalog_of(i)
+			c = np.column_stack((cat['column_stamp'], cat['row_stamp'], cat['tmag']))
+			mm, _ = ok2p2.k2p2FixFromSum(S[i], catalog=c, thresh=0.8, min_no_pixels_in_mask=4, min_for_cluster=4,
+				cluster_radius=np.sqrt(2) + np.finfo(np.float64).eps, segmentation=True, ws_blur=0.5, ws_thres=0,
+				ws_footprint=3, extend_overflow=True)
+			if i == 5: # a mask that touches the stamp edge: edge_flux != 0
+				mm = np.zeros((1, H, W)); mm[0, 0:7, 2:9] = 1
+			if i == 6: # NaN fluxes in some cadences (a NaN pixel inside the mask)
+				main = np.asarray(mm, dtype=bool)[0]
+				rr, cc = np.argwhere(main)[0]
+				scene.images[i, rr, cc, [3, 20, 21, 50]] = np.nan
+			f = make_fake(AperturePhotometry, scene, i, S[i])
+			f.lightcurve = FakeLC(f.lightcurve)
+			f._status = STATUS.UNKNOWN
 
-		def fake_k2p2(SumImage, _mm=mm, **kwargs):
-			return np.array(_mm, dtype='float64'), 1.0
-		ap_module.k2p2.k2p2FixFromSum = fake_k2p2
-		with warnings.catch_warnings():
-			warnings.simplefilter('ignore')
-			BasePhotometry.photometry(f)
-		d = f._details
-		lc = f.lightcurve
-		out[f'case{i}_status'] = f._status.value
-		out[f'case{i}_flux'] = np.asarray(lc['flux'])
-		out[f'case{i}_flux_err'] = np.asarray(lc['flux_err'])
-		out[f'case{i}_pos_centroid'] = np.asarray(lc['pos_centroid'])
-		out[f'case{i}_mask'] = np.asarray(f.final_phot_mask, dtype=bool)
-		for key in ('mean_flux', 'variance', 'rms_hour', 'ptp', 'variability', 'mask_size', 'edge_flux'):
-			out[f'case{i}_{key}'] = np.float64(d[key])
-		out[f'case{i}_det_pos_centroid'] = np.asarray(d['pos_centroid'], dtype='float64')
-		print('diagnostics case', i, f._status, {k: d[k] for k in ('mean_flux', 'variance', 'rms_hour', 'ptp', 'variability', 'mask_size', 'edge_flux')})
-	ap_module.k2p2.k2p2FixFromSum = k2p2v2.k2p2FixFromSum
-	np.savez_compressed(os.path.join(HERE, 'golden_diagnostics.npz'), **out)
+			def fake_k2p2(SumImage, _mm=mm, **kwargs):
+				return np.array(_mm, dtype='float64'), 1.0
+			k2p2v2.k2p2FixFromSum = fake_k2p2
+			with warnings.catch_warnings():
+				warnings.simplefilter('ignore')
+				BasePhotometry.photometry(f)
+			d = f._details
+			lc = f.lightcurve
+			out[f'case{i}_status'] = f._status.value
+			out[f'case{i}_flux'] = np.asarray(lc['flux'])
+			out[f'case{i}_flux_err'] = np.asarray(lc['flux_err'])
+			out[f'case{i}_pos_centroid'] = np.asarray(lc['pos_centroid'])
+			out[f'case{i}_mask'] = np.asarray(f.final_phot_mask, dtype=bool)
+			for key in ('mean_flux', 'variance', 'rms_hour', 'ptp', 'variability', 'mask_size', 'edge_flux'):
+				out[f'case{i}_{key}'] = np.float64(d[key])
+			out[f'case{i}_det_pos_centroid'] = np.asarray(d['pos_centroid'], dtype='float64')
+			print('diagnostics case', i, f._status, {k: d[k] for k in ('mean_flux', 'variance', 'rms_hour', 'ptp', 'variability', 'mask_size', 'edge_flux')})
+	finally:
+		k2p2v2.k2p2FixFromSum = _real_k2p2
+	np.savez_compressed(_out('golden_diagnostics.npz'), **out)
 
 
 #--------------------------------------------------------------------------------------------------
+def _assert_reference_k2p2():
+	"""A generator that is not running the reference's own ``k2p2FixFromSum`` must stop, not write."""
+	fn = k2p2v2.k2p2FixFromSum
+	assert fn is _real_k2p2, f"k2p2v2.k2p2FixFromSum is {fn!r}: a prescribed-mask patch of another generator is still in place"
+	code_file = os.path.realpath(fn.__code__.co_filename)
+	ref_root = os.path.realpath(_refstub.REFERENCE_PATH)
+	assert os.path.commonpath([code_file, ref_root]) == ref_root, f"k2p2FixFromSum comes from {code_file}, not from the reference checkout {ref_root}"
+
+
 def golden_k2p2():
 	"""Reference k2p2FixFromSum control flow with stand-ins (partial oracle)."""
+	_assert_reference_k2p2()
 	out = {}
 	n = 0
 	settings = dict(thresh=0.8, min_no_pixels_in_mask=4, min_for_cluster=4,
@@ -449,7 +476,7 @@ def golden_k2p2():
 			print('k2p2 case', n, (H, W), 'nmasks', 0 if masks is None else len(masks), err)
 			n += 1
 	out['n_cases'] = n
-	np.savez_compressed(os.path.join(HERE, 'golden_k2p2.npz'), **out)
+	np.savez_compressed(_out('golden_k2p2.npz'), **out)
 
 
 #--------------------------------------------------------------------------------------------------
@@ -483,7 +510,7 @@ def golden_psf():
 		print('psf case', n, shape, res.sum())
 		n += 1
 	out['n_cases'] = n
-	np.savez_compressed(os.path.join(HERE, 'golden_psf.npz'), **out)
+	np.savez_compressed(_out('golden_psf.npz'), **out)
 
 
 def golden_linpsf():
@@ -555,7 +582,7 @@ def golden_linpsf():
 	out['cat_offsets'] = scene.cat_offsets
 	for k, v in scene.catalog.items():
 		out['cat_' + k] = v
-	np.savez_compressed(os.path.join(HERE, 'golden_linpsf.npz'), **out)
+	np.savez_compressed(_out('golden_linpsf.npz'), **out)
 
 #--------------------------------------------------------------------------------------------------
 class _Group(dict):
@@ -631,7 +658,7 @@ def golden_background():
 		out[f'b3_images_backapp{int(backapp)}'] = np.stack(imgs)
 		out[f'b3_errors_backapp{int(backapp)}'] = np.stack(errs)
 	out['b3_raw'], out['b3_raw_err'], out['b3_flags'] = raw, err, flags
-	np.savez_compressed(os.path.join(HERE, 'golden_background.npz'), **out)
+	np.savez_compressed(_out('golden_background.npz'), **out)
 
 def golden_shenanigans():
 	"""
@@ -666,7 +693,7 @@ def golden_shenanigans():
 		out[f's{case}_indicator'] = np.moveaxis(ind, 2, 0)
 		out[f's{case}_mean'] = ns['mean_shenanigans']
 	out['n_cases'] = np.array(4)
-	np.savez_compressed(os.path.join(HERE, 'golden_shenanigans.npz'), **out)
+	np.savez_compressed(_out('golden_shenanigans.npz'), **out)
 	print('golden_shenanigans', 4, 'cases')
 
 
@@ -725,7 +752,7 @@ def golden_pixelflags():
 		assert np.array_equal(cols, np.arange(shape[1]) >= first), "exclusions are a column suffix"
 		for k, v in zip(out.keys(), (camera, ccd, -1 if ffi is None else ffi, t0, t1, is_tess, zero, first)):
 			out[k].append(v)
-	np.savez_compressed(os.path.join(HERE, 'golden_pixelflags.npz'), **{k: np.asarray(v) for k, v in out.items()})
+	np.savez_compressed(_out('golden_pixelflags.npz'), **{k: np.asarray(v) for k, v in out.items()})
 	print('golden_pixelflags', len(cases), 'cases, first excluded columns', out['first_excluded_column'])
 
 
@@ -763,7 +790,7 @@ def golden_psfphot():
 		out[key] = getattr(scene, key)
 	for k, v in scene.catalog.items():
 		out['cat_' + k] = v
-	np.savez_compressed(os.path.join(HERE, 'golden_psfphot.npz'), **out)
+	np.savez_compressed(_out('golden_psfphot.npz'), **out)
 
 
 #--------------------------------------------------------------------------------------------------
@@ -828,7 +855,7 @@ def golden_skiptargets():
 		out[f's{c}_status_out'] = np.array([final[int(p)] for p in priority], dtype='int32')
 		out[f's{c}_ran'] = np.array(ran, dtype='int64')
 	out['n_cases'] = n_cases
-	np.savez_compressed(os.path.join(HERE, 'golden_skiptargets.npz'), **out)
+	np.savez_compressed(_out('golden_skiptargets.npz'), **out)
 	print('skiptargets:', n_cases, 'todo-lists')
 
 
@@ -929,6 +956,18 @@ class _RecTime(object):
 		return f'MJD-OF({self.jd1!r},{self.jd2!r},{self.scale})'
 
 
+class _RecDatetime(object):
+	"""Stand-in for the ``datetime`` module as BasePhotometry sees it: ``save_lightcurve`` asks it for the wall clock once
+	(``datetime.datetime.now()``, BasePhotometry.py:1459) to write the DATE card; a fixed instant makes the fixture reproducible."""
+	import datetime as _dt
+	NOW = _dt.datetime(2026, 10, 3, 12, 0, 0)
+
+	class datetime(_dt.datetime):
+		@classmethod
+		def now(cls, tz=None):
+			return _RecDatetime.NOW
+
+
 class _RecWCS(object):
 	"""The WCS object only has to be sliced and turned into a header (BasePhotometry.py:1659-1661)."""
 	def __init__(self, sl=None):
@@ -961,6 +1000,9 @@ def golden_fitsfile():
 	import json
 	import tempfile
 	bp = sys.modules['photometry.BasePhotometry']
+	# the class attributes that are replaced per case by properties handing out the test data (``wcs`` is an instance attribute
+	# upstream: None here): put back after every case, or a generator that runs after this one (golden_sumimage) meets them
+	own_attributes = {k: bp.BasePhotometry.__dict__.get(k) for k in ('pixelflags', 'aperture', 'sumimage', 'wcs')}
 	rng = np.random.default_rng(5)
 	cases = []
 	arrays = {}
@@ -1008,12 +1050,17 @@ def golden_fitsfile():
 			f.output_folder_base = os.path.join(tmp, 'output')
 			f.output_folder = os.path.join(f.output_folder_base, 'sub')
 			_RecFits.written.clear()
-			old = bp.fits, bp.Time
-			bp.fits, bp.Time = _RecFits, _RecTime
+			old = bp.fits, bp.Time, bp.datetime
+			bp.fits, bp.Time, bp.datetime = _RecFits, _RecTime, _RecDatetime
 			try:
 				path = bp.BasePhotometry.save_lightcurve(f)
 			finally:
-				bp.fits, bp.Time = old
+				bp.fits, bp.Time, bp.datetime = old
+				for k, v in own_attributes.items():
+					if v is None:
+						delattr(bp.BasePhotometry, k)
+					else:
+						setattr(bp.BasePhotometry, k, v)
 		w = _RecFits.written[0]
 		assert w['checksum'] is True
 
@@ -1043,13 +1090,25 @@ def golden_fitsfile():
 				'header': f.header, 'additional_headers': {k: list(v) for k, v in f.additional_headers.items()}, 'stamp': list(f._stamp)}})
 		for k, v in inputs.items():
 			arrays[f'c{c}_in_{k}'] = v
-	with open(os.path.join(HERE, 'golden_fitsfile.json'), 'w') as fh:
+	with open(_out('golden_fitsfile.json'), 'w') as fh:
 		json.dump({'cases': cases}, fh, indent=1)
-	np.savez_compressed(os.path.join(HERE, 'golden_fitsfile.npz'), **arrays)
+	np.savez_compressed(_out('golden_fitsfile.npz'), **arrays)
 	print('fitsfile:', len(cases), 'files;', [len(h['cards']) for h in cases[0]['hdus']], 'cards per HDU')
 
 
+DEFAULT = ['misc', 'sumimage', 'aperture', 'k2p2', 'psf', 'linpsf', 'diagnostics', 'cutout', 'background', 'psfphot', 'pixelflags', 'shenanigans', 'skiptargets', 'fitsfile']
+
+
 if __name__ == '__main__':
-	which = sys.argv[1:] or ['misc', 'sumimage', 'aperture', 'k2p2', 'psf', 'linpsf', 'diagnostics', 'cutout', 'background', 'psfphot', 'pixelflags', 'shenanigans', 'skiptargets', 'fitsfile']
-	for w in which:
+	import argparse
+	parser = argparse.ArgumentParser(description="Write the golden fixtures by executing the reference.")
+	parser.add_argument('--out', default=HERE, metavar='DIR', help="directory the fixtures are written to (default: this directory)")
+	parser.add_argument('fixtures', nargs='*', metavar='NAME', help="fixtures to write (default: all, in the order " + ' '.join(DEFAULT) + ")")
+	args = parser.parse_intermixed_args()
+	unknown = [w for w in args.fixtures if w not in DEFAULT]
+	if unknown:
+		parser.error(f"unknown fixture(s) {unknown}; known: {DEFAULT}")
+	OUT = os.path.abspath(args.out)
+	os.makedirs(OUT, exist_ok=True)
+	for w in args.fixtures or DEFAULT:
 		globals()['golden_' + w]()

@@ -9,7 +9,8 @@ The series hold NaN kernels (one of them at index 0, whose NaN is the interpolat
 inside, on and outside the range, for the three numeric warp modes.  ``tests/test_motion_golden.py`` holds
 ``photometry_amd.motion.MovementKernel`` to these values bit for bit.
 
-Run once on a machine with the reference checkout (``python tests/golden/make_golden_motion.py``); the result is committed.
+Run on a machine with the reference checkout (``python tests/golden/make_golden_motion.py [--out DIR]``, by default into this
+directory); the result is committed, and ``tests/test_golden_regenerates.py`` holds a fresh run to it.
 """
 
 import os
@@ -41,7 +42,7 @@ def series(mode, rng, T=40):
 	return times, kernels
 
 
-def main():
+def main(out_dir=HERE):
 	rng = np.random.default_rng(20261015)
 	out = {}
 	xy = np.array([[10.5, 20.25], [1000.0, 1500.0], [2047.0, 0.0], [431.7, 1777.3]])
@@ -69,8 +70,13 @@ def main():
 		imk.load_series(np.arange(5.0), np.zeros((5, 3)))
 	except ValueError as e:
 		out['wrong_shape_message'] = np.array(str(e))
-	np.savez_compressed(os.path.join(HERE, 'golden_motion.npz'), **out)
+	np.savez_compressed(os.path.join(out_dir, 'golden_motion.npz'), **out)
 
 
 if __name__ == '__main__':
-	main()
+	import argparse
+	parser = argparse.ArgumentParser(description="Write golden_motion.npz by executing the reference.")
+	parser.add_argument('--out', default=HERE, metavar='DIR', help="directory the fixture is written to (default: this directory)")
+	args = parser.parse_args()
+	os.makedirs(args.out, exist_ok=True)
+	main(os.path.abspath(args.out))

@@ -53,7 +53,7 @@ def aperture_loop(n=6, T=1300):
 		assert status.value == r['status']
 		np.testing.assert_array_equal(np.asarray(f.lightcurve['flux']), r['flux'])
 		done += 1
-	mg.ap_module.k2p2.k2p2FixFromSum = mg.k2p2v2.k2p2FixFromSum
+	mg.k2p2v2.k2p2FixFromSum = mg._real_k2p2
 	print(f'aperture loop (mask given), {done} targets x {T} cadences x 15x15: reference {t_ref / done:.4f} s/target = {done / t_ref:.1f} targets/s/core;'
 		f' oracle {t_ora / done:.4f} s/target = {done / t_ora:.1f} targets/s/core; oracle / reference time = {t_ora / t_ref:.2f}')
 

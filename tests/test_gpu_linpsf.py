@@ -118,6 +118,7 @@ def test_linpsf_golden(ctx, golden_dir, path):
 	for i in range(int(g['n_linpsf'])):
 		ref = g[f'lp{i}_flux']
 		np.testing.assert_allclose(res['flux'][i], ref, rtol=1e-8, atol=1e-9*np.abs(ref).max())
+		np.testing.assert_array_equal(res['flux_err'][i], g[f'lp{i}_flux_err'])   # NaN upstream (linpsf_photometry.py:169)
 		assert int(res['status'][i]) == int(g[f'lp{i}_status'])
 		np.testing.assert_allclose(res['contamination'][i], float(g[f'lp{i}_contamination']), rtol=1e-7, atol=1e-11)
 

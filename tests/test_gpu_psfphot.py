@@ -74,6 +74,7 @@ def test_psf_photometry_golden(ctx, golden_dir):
 		np.testing.assert_allclose(res['flux'][i], ref, rtol=FLUX_RTOL)
 		np.testing.assert_allclose(np.column_stack((res['centroid_row'][i], res['centroid_col'][i])), g[f'pp{n}_pos_centroid'], atol=POS_ATOL)
 		assert np.all(np.isnan(res['flux_err'][i])) and int(res['status'][i]) == int(g[f'pp{n}_status'])
+		np.testing.assert_array_equal(res['flux_err'][i], g[f'pp{n}_flux_err'])   # NaN upstream (psf_photometry.py:175)
 
 
 def test_psf_photometry_matches_oracle(ctx):

@@ -61,6 +61,9 @@ def test_transforms_against_astropy(ctx, g):
 		fp = w.calc_footprint(axes=(2136, 2078))
 		assert wc.ra_diff(fp[:, 0], g[f'hdr_{i}_footprint'][:, 0]).max() < 1e-10, name
 		assert np.abs(fp[:, 1] - g[f'hdr_{i}_footprint'][:, 1]).max() < 1e-10, name
+		fp22 = w.calc_footprint(axes=(2, 2))
+		assert wc.ra_diff(fp22[:, 0], g[f'hdr_{i}_footprint22'][:, 0]).max() < 1e-10, name
+		assert np.abs(fp22[:, 1] - g[f'hdr_{i}_footprint22'][:, 1]).max() < 1e-10, name
 		for bt in (0, 1):
 			world = g[f'hdr_{i}_world{bt}']
 			np.testing.assert_allclose(w.wcs_world2pix(world, 0), g[f'hdr_{i}_wcs_world2pix{bt}'], rtol=0, atol=1e-8, err_msg=name)

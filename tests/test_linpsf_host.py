@@ -125,6 +125,10 @@ def test_design_facts():
 		assert cl['cls'] == 'matrix' and cl['segments'] == [(0, 1), (1, 2), (2, 3)]
 		nb = (case['scene'].specs[i]['place'] + 1) % cl['stars']
 		assert [sh[nb] for sh in cl['shapes']] == [(1, 1), (0, 0), (1, 1)] and all(sh[case['scene'].specs[i]['place']] == (1, 1) for sh in cl['shapes'])
+	# a star with na == 0 has no blocks in its segment's coefficient image: in target 1 it is the LAST fitted star, whose blocks would
+	# begin where the image ends -- the fit must not read there (whatever lies in LDS behind the image, times zero, may be NaN)
+	last = [(case['scene'].specs[i]['place'] + 1) % case['scene'].specs[i]['S'] == case['scene'].specs[i]['S'] - 1 for i in (0, 1, 2)]
+	assert last == [False, True, False]
 
 
 def so_slice(case, i):

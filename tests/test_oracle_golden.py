@@ -140,6 +140,7 @@ def test_linpsf(golden_dir):
 		assert res['status'] == int(g[f'lp{n}_status'])
 		np.testing.assert_allclose(res['flux'], g[f'lp{n}_flux'], rtol=1e-9)
 		assert np.all(np.isnan(res['flux_err']))
+		np.testing.assert_array_equal(res['flux_err'], g[f'lp{n}_flux_err'])   # what the reference itself left there: NaN (:169)
 		np.testing.assert_allclose(res['contamination'], float(g[f'lp{n}_contamination']), rtol=1e-8, atol=1e-12)
 
 
@@ -189,6 +190,7 @@ def test_psf_photometry_golden(golden_dir):
 			np.testing.assert_allclose(res['flux'], g[f'pp{n}_flux'], rtol=2e-5)
 			np.testing.assert_allclose(res['pos_centroid'], g[f'pp{n}_pos_centroid'], atol=2e-4)
 			assert np.all(np.isnan(res['flux_err']))
+			np.testing.assert_array_equal(res['flux_err'], g[f'pp{n}_flux_err'])   # the reference's own column: NaN (:175)
 
 
 def test_pixel_manual_exclude_golden(golden_dir):
@@ -253,6 +255,7 @@ def test_psf_distribution_fixture_belongs_to_the_seeded_scene(golden_dir):
 	import make_psf_distribution as mk
 	g = np.load(os.path.join(golden_dir, 'golden_psf_distribution.npz'))
 	assert tuple(int(v) for v in g['shape']) == (mk.NT, mk.T, mk.H, mk.W)
+	assert [int(v) for v in g['seeds']] == [mk.SCENE_SEED, mk.PRF_SEED] and float(g['nan_fraction'][0]) == mk.NAN_FRACTION
 	s, _prf = mk.build_scene()
 	assert float(np.nansum(s.images.astype('float64'))) == float(g['images_checksum'][0])
 	assert g['flux'].shape == (mk.NT, mk.T) and g['nit'].max() == 1500 and 0.4 < np.isfinite(g['flux']).mean() < 0.9   # two- and three-star fits mostly run into maxiter: NaN by the reference's rule

@@ -95,6 +95,10 @@ def test_restatement_against_astropy(g):
 		assert np.abs(r.pix2foc(pts, 0) - g[f'hdr_{i}_pix2foc']).max() < 1e-10, name
 		fp = r.all_pix2world(np.array([[0.0, 0.0], [0.0, 2077.0], [2135.0, 2077.0], [2135.0, 0.0]]), 0)
 		assert wc.ra_diff(fp[:, 0], g[f'hdr_{i}_footprint'][:, 0]).max() < 1e-10, name
+		# calc_footprint(axes=(2, 2)): the corners load_series' check sends back through all_world2pix (image_motion.py:300-309)
+		fp22 = r.all_pix2world(np.array([[0.0, 0.0], [0.0, 1.0], [1.0, 1.0], [1.0, 0.0]]), 0)
+		assert wc.ra_diff(fp22[:, 0], g[f'hdr_{i}_footprint22'][:, 0]).max() < 1e-10, name
+		assert np.abs(fp22[:, 1] - g[f'hdr_{i}_footprint22'][:, 1]).max() < 1e-10, name
 		for b in (0, 1):
 			world = g[f'hdr_{i}_world{b}']
 			np.testing.assert_allclose(r.wcs_world2pix(world, 0), g[f'hdr_{i}_wcs_world2pix{b}'], rtol=0, atol=1e-8, err_msg=name)
