@@ -516,6 +516,35 @@ int tp_linpsf_fit(tp_ctx* ctx, const tp_cube_desc* desc, const float* d_images,
 	const double* d_pos_row, const double* d_pos_col, int64_t pos_pitch, double cutoff_radius,
 	double* d_flux, double* d_flux_err, double* d_fluxes_all, int64_t out_pitch,
 	double* d_contamination, int32_t* d_status, double* d_fluxes_mean);
+/* tp_linpsf_flux_err: the uncertainty of the LinPSF target flux, propagated from the pixel errors.  The reference has none --
+ * linpsf_photometry.py:169 writes flux_err[k] = NaN ("FIXME: Add errors!"), BasePhotometry.photometry() then refuses the light curve
+ * (BasePhotometry.py:1348-1349) -- and tp_linpsf_fit keeps doing exactly that; this is a separate pass beside it, defined here.
+ * For one target and one cadence k, in float64:
+ *   good     = the pixels the fit uses: finite d_images value (linpsf_photometry.py:123); d_images is read for nothing else;
+ *   A        = the design matrix of the fit (npx x S, linpsf_photometry.py:126-133): column s is the pixel-integrated unit PRF of
+ *              fitted star s at its position of cadence k, zero outside cutoff_radius;
+ *   G        = A^T A;  p = pinv(G)[t, :] with t = d_target_index and numpy's rcond = 1e-15;  m = A p (the target's flux is m . b);
+ *   flux_err = sqrt(sum over good pixels of (m_px * err_px)^2), err the float32 d_images_err value widened.
+ * The sum is a plain sum, as the aperture's sqrt(sum(err^2)) is (photometry.py:211): a non-finite err at a good pixel makes the
+ * cadence's error NaN, also where m_px is 0.  A cadence without a good pixel gives 0 (the fit gives flux 0 there).  A target whose
+ * d_target_index is not one of its fitted stars gives NaN.  A background series subtracted in the fit does not enter.
+ * (Computed in one pass as W = A^T diag(err^2) A, var = p^T W p: the same number to rounding.)
+ * Conventions of tp_linpsf_fit: the layouts of desc (t_pitch honoured), d_images_err laid out like d_images, d_coef / d_knots_* /
+ * max_stars / d_star_offsets / d_pos_* as there, pos_pitch and out_pitch >= n_cad, d_flux_err float64 [n_targets][out_pitch] with the
+ * values beyond n_cad left untouched, cutoff_radius +infinity = none.  The SPOC grid with cutoff_radius <= 5.25 runs one lane per
+ * cadence out of registers (up to 8 fitted stars; 9 .. 64 out of an HBM workspace); any other grid, any radius and axes of
+ * different lengths (_xy) evaluate the FITPACK box integral out of that workspace, far slower.  No atomics: two calls give the same
+ * bits, and a target alone the bits it gives inside a batch. */
+int tp_linpsf_flux_err_xy(tp_ctx* ctx, const tp_cube_desc* desc, const float* d_images, const float* d_images_err,
+	const double* d_coef, const double* d_knots_x, const double* d_knots_y, int32_t n_coef_axis_x, int32_t n_coef_axis_y, int32_t max_stars,
+	const int64_t* d_star_offsets, const int32_t* d_target_index,
+	const double* d_pos_row, const double* d_pos_col, int64_t pos_pitch, double cutoff_radius,
+	double* d_flux_err, int64_t out_pitch);
+int tp_linpsf_flux_err(tp_ctx* ctx, const tp_cube_desc* desc, const float* d_images, const float* d_images_err,
+	const double* d_coef, const double* d_knots_x, const double* d_knots_y, int32_t n_coef_axis, int32_t max_stars,
+	const int64_t* d_star_offsets, const int32_t* d_target_index,
+	const double* d_pos_row, const double* d_pos_col, int64_t pos_pitch, double cutoff_radius,
+	double* d_flux_err, int64_t out_pitch);
 
 /* ---- non-linear PSF photometry ------------------------------------------------
  * replaces PSFPhotometry.do_photometry (photometry/psf_photometry.py:111-196) with its likelihood (:52-90, statistic

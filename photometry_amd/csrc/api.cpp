@@ -68,6 +68,7 @@ static const char* const kKernelNames[TPK_COUNT] = {
 	"tp_wcs_positions_kernel",
 	"tp_motion_interp_kernel",
 	"tp_motion_positions_kernel",
+	"tp_linpsf_err_kernel",
 };
 
 extern "C" {

@@ -66,6 +66,7 @@ enum tp_kernel_id {
 	TPK_WCS_POSITIONS,
 	TPK_MOTION_INTERP,
 	TPK_MOTION_POSITIONS,
+	TPK_LINPSF_FLUX_ERR,
 	TPK_COUNT
 };
 

@@ -85,55 +85,8 @@ __global__ __launch_bounds__(256) void tp_linpsf_prf_fixed_kernel(const double* 
 	}
 }
 
-// ---- What the direct, the many-star and the finalise kernels share, each rule stated once.  (The build sets -ffp-contract=off:
-// an expression gives the same bits in a helper as written out in a kernel.)
-// pixel p of a cadence's frame (img: its pixel 0) as the fit sees it, lowered by `sub` where a.subtract is set; false unless it is
-// finite: good_pixels = isfinite(img) (linpsf_photometry.py:123)
-__device__ __forceinline__ bool fetch_pixel(const FitArgs& a, const float* img, int p, float sub, float& bf)
-{
-	bf = img[(int64_t)p * a.t_pitch];
-	if (a.subtract) bf = bf - sub;
-	return fabsf(bf) <= 3.402823466e+38f;
-}
-
-// psf.py:142  sqrt((j-col)^2 + (i-row)^2) < cutoff_radius  (a NaN position is never inside: zero column)
-__device__ __forceinline__ bool inside_cutoff(double dc, double dr, double cutoff) { return sqrt(dc * dc + dr * dr) < cutoff; }
-
-// the pixel-integrated PRF of a star at pixel (i, j) on the uniform grid: the table origin moved by 9 knots per pixel, clamped to the table
-__device__ __forceinline__ double star_pixel_uniform(const double* __restrict__ C, int n, int ax0, int by0, int i, int j, double h2,
-	const double (&mx)[4], const double (&my)[4])
-{
-	int ax = ax0 + 9 * j, by = by0 + 9 * i;
-	ax = ax < 0 ? 0 : (ax > n - 13 ? n - 13 : ax);
-	by = by < 0 ? 0 : (by > n - 13 ? n - 13 : by);
-	return h2 * prf_pixel(C, n, ax, by, mx, my);
-}
-
-// the same on any grid, (dc, dr) the pixel centre: psf.py:146  integral(column_cen - 0.5, column_cen + 0.5, row_cen - 0.5, row_cen + 0.5)
-__device__ __forceinline__ double star_pixel_general(const double* __restrict__ C, int n, int ny, const double* __restrict__ kn, const double* __restrict__ kny, double dc, double dr)
-{ return prf_pixel_general(C, n, ny, kn, kny, dc - 0.5, dc + 0.5, dr - 0.5, dr + 0.5); }
-
-// per register-resident star at one cadence: position, edge weights (the same for every pixel) and table origin of pixel 0
-template <int S> struct StarEdges { double mx[S][4], my[S][4], srow[S], scol[S]; int ax0[S], by0[S]; };
-
-template <int S>
-__device__ __forceinline__ void star_edges(const FitArgs& a, const double* kn, const double* kny, int n, double h, double hy, int64_t s0, int ns, int k, StarEdges<S>& e)
-{
-#pragma unroll
-	for (int s = 0; s < S; ++s) {
-		if (s < ns) {
-			e.srow[s] = a.pos_row[(s0 + s) * a.pos_pitch + k];
-			e.scol[s] = a.pos_col[(s0 + s) * a.pos_pitch + k];
-			// x <-> column (first spline axis), y <-> row  (psf.py:146)
-			axis_weights(kn, n, e.scol[s], h, e.mx[s], e.ax0[s]);
-			axis_weights(kny, n, e.srow[s], hy, e.my[s], e.by0[s]);
-		} else {
-			e.srow[s] = e.scol[s] = 0.0; e.ax0[s] = e.by0[s] = 4;
-#pragma unroll
-			for (int q = 0; q < 4; ++q) { e.mx[s][q] = 0.0; e.my[s][q] = 0.0; }
-		}
-	}
-}
+// (fetch_pixel, inside_cutoff, star_pixel_uniform / _general, StarEdges and star_edges live in linpsf_common.h: the flux-error pass of
+// linpsf_err.hip forms the same design matrix)
 
 // General path: direct evaluation of the 13x13 contraction per star, pixel and cadence.  Runs only for the
 // targets that the polynomial path could not take (`todo` flag set, or todo == nullptr).

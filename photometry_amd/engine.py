@@ -359,6 +359,29 @@ def linpsf_fit(ctx, images, coef, knots_x, knots_y, star_offsets, target_index, 
 	return out
 
 
+def linpsf_flux_err(ctx, images, images_err, coef, knots_x, knots_y, star_offsets, target_index, pos_row, pos_col, max_stars,
+	cutoff_radius=5.0, out=None):
+	"""
+	The uncertainty of the LinPSF target flux, propagated from the pixel errors (``tp_linpsf_flux_err_xy``; the reference has none,
+	linpsf_photometry.py:169): per cadence ``sqrt(sum_good (m_px * err_px)^2)`` with ``m`` the row of ``pinv(A^T A) A^T`` that gives
+	the target's flux and ``A`` the design matrix of :func:`linpsf_fit` -- a separate pass beside the fit, which it leaves untouched.
+	``images_err``: a :class:`DeviceCube` laid out like ``images``; the other arguments as for :func:`linpsf_fit`.
+	Returns a float64 ``(Nt, T)`` device array (``out``: a caller-owned one of at least ``T`` columns, written up to ``T``).
+	"""
+	n, ny = knots_x.shape[0] - 4, knots_y.shape[0] - 4
+	if cutoff_radius is None:
+		cutoff_radius = float('inf')
+	if out is None:
+		out = ctx.zeros((images.n_targets, images.n_cad), 'float64')
+	assert pos_row.shape[1] >= images.n_cad and pos_col.shape == pos_row.shape
+	assert images_err.t_pitch == images.t_pitch and images_err.data.shape == images.data.shape
+	assert out.shape[0] >= images.n_targets and out.shape[1] >= images.n_cad
+	desc = images.desc
+	ctx._check(ctx.lib.tp_linpsf_flux_err_xy(ctx.handle, ctypes.byref(desc), images.ptr, images_err.ptr, coef.ptr, knots_x.ptr, knots_y.ptr, n, ny,
+		int(max_stars), star_offsets.ptr, target_index.ptr, pos_row.ptr, pos_col.ptr, pos_row.shape[1], float(cutoff_radius), out.ptr, out.shape[1]))
+	return out
+
+
 
 def psf_fit(ctx, images, backgrounds, coef, knots_x, knots_y, star_offsets, params0, mini_aperture, variance_floor=9.0,
 	cutoff_radius=5.0, maxiter_first=1500, maxiter=500):

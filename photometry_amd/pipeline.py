@@ -903,7 +903,7 @@ def _jitter32(jitter, T):
 	return j[:, 0].astype('float32'), j[:, 1].astype('float32')
 
 
-def linpsf_frames(ctx, stack, targets, catalog, time, quality, prf_model, jitter=None, cutoff_radius=5, movement=None, timecorr=None):
+def linpsf_frames(ctx, stack, targets, catalog, time, quality, prf_model, jitter=None, cutoff_radius=5, movement=None, timecorr=None, flux_errors=False):
 	"""
 	``LinPSFPhotometry.do_photometry`` (linpsf_photometry.py:79-219) for every target of a CCD region held in a
 	:class:`FrameStack`: default stamps grouped by size and cut on the device, the stars fitted beside each target selected as
@@ -915,6 +915,8 @@ def linpsf_frames(ctx, stack, targets, catalog, time, quality, prf_model, jitter
 	Under a ``'euclidian'`` or ``'affine'`` kernel every star moves by its own shift (``'unchanged'``: by none): ``catalog_attime``'s
 	``interpolate`` over each stamp's catalogue, formed on the device in its float32 arithmetic (``tp_motion_star_positions``).
 	A ``'wcs'`` kernel does the same through the headers, each stamp's catalogue one batch (``tp_wcs_star_positions``).
+	``flux_errors``: also cut the ``images_err`` stack and fill ``flux_err`` with the pixel errors propagated through the fit
+	(``tp_linpsf_flux_err``, with the positions the fit used); by default it is NaN as the reference leaves it (linpsf_photometry.py:169).
 	Returns a :class:`PSFFramesResult`.
 	"""
 	from . import psf as hpsf
@@ -975,10 +977,15 @@ def linpsf_frames(ctx, stack, targets, catalog, time, quality, prf_model, jitter
 			pos_col, pos_row, _ = wcs.star_positions(ctx, movement._d_series, len(movement.series_kernels), movement.wcs_ref, cat_offsets,
 				np.column_stack((cat['column'], cat['row'])), cat['column_stamp'], cat['row_stamp'], out_index, len(rows), *wcs_pairs)
 		cube = engine.cut_stamps(ctx, stack.dev['images'], ctx.array(cur[idx].astype('int32')), H, W, stack.row0, stack.col0)
+		err_cube = None
 		try:
 			coef = engine.linpsf_prf(ctx, base_coef, ctx.array(prf_model.weights(cur[idx])))
-			fit = engine.linpsf_fit(ctx, cube, coef, tx, ty, ctx.array(star_offsets), ctx.array(target_index), pos_row, pos_col,
-				max(int(np.diff(star_offsets).max()), 1), cutoff_radius=cutoff_radius)
+			d_offsets, d_index, max_stars = ctx.array(star_offsets), ctx.array(target_index), max(int(np.diff(star_offsets).max()), 1)
+			fit = engine.linpsf_fit(ctx, cube, coef, tx, ty, d_offsets, d_index, pos_row, pos_col, max_stars, cutoff_radius=cutoff_radius)
+			if flux_errors:
+				err_cube = engine.cut_stamps(ctx, stack.dev['images_err'], ctx.array(cur[idx].astype('int32')), H, W, stack.row0, stack.col0)
+				engine.linpsf_flux_err(ctx, cube, err_cube, coef, tx, ty, d_offsets, d_index, pos_row, pos_col, max_stars, cutoff_radius=cutoff_radius,
+					out=fit.flux_err)
 			res = fit.to_host(('contamination', 'status'))
 			if len(idx) == n and np.array_equal(idx, np.arange(n)) and fit.flux.shape == out.flux.shape:
 				# one group holds every target in order (the usual case: default stamps of one size): straight into the result arrays
@@ -991,6 +998,8 @@ def linpsf_frames(ctx, stack, targets, catalog, time, quality, prf_model, jitter
 		finally:
 			ctx.sync()
 			cube.free()
+			if err_cube is not None:
+				err_cube.free()
 		out.contamination[idx] = res['contamination']
 		# linpsf_photometry.py:198-200, 214-219: ERROR when every flux is NaN, WARNING above 10 % contamination (NaN compares false)
 		failed = res['status'] == 2

@@ -28,8 +28,10 @@ from . import engine, pipeline, stamps
 # input adapter's job here -- see the warning in BasePhotometry.__init__ -- and a switch that switches nothing would mislead)
 # [halo] enabled is this engine's own switch (not in the reference's file): Halo photometry here is a TV-min implementation of its own
 # (photometry_amd.halo, DESIGN.md "Halo"), not halophot, so it runs only when a settings file asks for it
+# [linpsf] flux_errors is this engine's own switch as well: the reference's LinPSF plugin has no flux errors (linpsf_photometry.py:169)
+# and ends in an error for it; the propagated pixel errors are a definition of this engine, on only when asked for
 DEFAULT_SETTINGS = {'todolist': {'faint_limit': '15.0'}, 'haloswitch': {'tmag_limit': '6.0', 'flux_limit': '0.01'},
-	'halo': {'enabled': 'false'}}
+	'halo': {'enabled': 'false'}, 'linpsf': {'flux_errors': 'false'}}
 
 TESS_DEFAULT_BITMASK = engine.TESS_DEFAULT_BITMASK
 #: PixelQualityFlags.BackgroundShenanigans / CorrectorQualityFlags.BackgroundShenanigans (photometry/quality.py:163, :85)
@@ -819,6 +821,14 @@ class LinPSFPhotometry(BasePhotometry):
 		super().__init__(*args, **kwargs)
 		self.cutoff_radius = 5
 
+	@staticmethod
+	def flux_errors(settings=None):
+		"""Whether the flux errors are propagated from the pixel errors: the ``[linpsf] flux_errors`` switch of the settings
+		(``TESSPHOT_SETTINGS``), off by default -- the reference has none (linpsf_photometry.py:169)."""
+		if settings is None:
+			settings = load_settings()
+		return settings.getboolean('linpsf', 'flux_errors', fallback=False)
+
 	def do_photometry(self):
 		from . import psf as hpsf
 		from .device import DeviceCube
@@ -839,8 +849,18 @@ class LinPSFPhotometry(BasePhotometry):
 			pos_col[:, k] = ck['column_stamp'][sel]
 		coef = engine.linpsf_prf(ctx, ctx.array(model.base_coef), ctx.array(model.weights(np.asarray([self._stamp]))))
 		cube = DeviceCube.from_host(ctx, self.images_cube)
-		res = engine.linpsf_fit(ctx, cube, coef, ctx.array(model.tx), ctx.array(model.ty), ctx.array(star_offsets), ctx.array(target_index),
-			ctx.array(pos_row), ctx.array(pos_col), max(nfit, 1), cutoff_radius=self.cutoff_radius).to_host()
+		with_errors = self.flux_errors(self.settings)
+		if with_errors:
+			# the same device arrays for the fit and the error pass after it
+			tx, ty, d_offsets, d_index = ctx.array(model.tx), ctx.array(model.ty), ctx.array(star_offsets), ctx.array(target_index)
+			d_row, d_col = ctx.array(pos_row), ctx.array(pos_col)
+			res = engine.linpsf_fit(ctx, cube, coef, tx, ty, d_offsets, d_index, d_row, d_col, max(nfit, 1), cutoff_radius=self.cutoff_radius).to_host()
+			res['flux_err'] = engine.linpsf_flux_err(ctx, cube, DeviceCube.from_host(ctx, self.images_err_cube), coef, tx, ty, d_offsets, d_index,
+				d_row, d_col, max(nfit, 1), cutoff_radius=self.cutoff_radius).to_host()
+			self.additional_headers['PSF_FERR'] = (True, 'flux errors propagated from pixel errors')
+		else:
+			res = engine.linpsf_fit(ctx, cube, coef, ctx.array(model.tx), ctx.array(model.ty), ctx.array(star_offsets), ctx.array(target_index),
+				ctx.array(pos_row), ctx.array(pos_col), max(nfit, 1), cutoff_radius=self.cutoff_radius).to_host()
 		self.lightcurve['flux'] = res['flux'][0]
 		self.lightcurve['flux_err'] = res['flux_err'][0]
 		status = int(res['status'][0])
