@@ -584,11 +584,16 @@ int tp_psf_fit(tp_ctx* ctx, const tp_cube_desc* desc, const float* d_images, con
  *   d_sumimage / d_mask (both or neither): for mask_size and edge_flux (:1394-1403);
  *   timescale_days: bin width of rms_hour (the reference uses 3600/86400);
  *   d_diag: float64 [n_targets][10] = mean_flux, variance, rms_hour, ptp, pos_centroid column, row,
- *            variability, mask_size, edge_flux, flags.  flags (as a float64 integer): 1 all fluxes NaN, 2 all
- *            errors NaN (both ValueError upstream, :1346-1349), 4 invalid time vector (ValueError in
- *            rms_timescale), 8 no detrending ("Could not detrend ..." warning: detrend = 0), 16 more
- *            time bins than cadences (rms_hour = NaN).  Light curves up to ~3 900 cadences are reduced out of
- *            LDS, longer ones (2-minute data) out of a context-owned HBM scratch with the same code.    */
+ *            variability, mask_size, edge_flux, flags.  flags (as a float64 integer), a sum of the bits
+ *              1  ALLNAN_FLUX    all fluxes NaN      } both ValueError upstream (:1346-1349); every light-curve
+ *              2  ALLNAN_ERR     all errors NaN      } column of the row is NaN
+ *              4  BAD_TIME       invalid time vector, or samples but none finite: ValueError in rms_timescale; rms_hour = NaN
+ *              8  NO_DETREND     "Could not detrend ..." warning: detrend = 0 (no fitted cadence, or a rank-deficient cubic;
+ *                                one fitted cadence, where the reference's polyfit fails with LinAlgError, is reported so too)
+ *             16  TOO_MANY_BINS  device only: more time bins than max(n_cad, 256) on a series that is not in time order (or more
+ *                                than 2e9 bins); rms_hour = NaN where the reference returns a number
+ *            Light curves up to ~6 650 cadences are reduced out of LDS, longer ones (2-minute data) out of a context-owned
+ *            HBM scratch with the same code.                                                                             */
 int tp_lightcurve_diagnostics(tp_ctx* ctx, int32_t n_targets, int32_t n_cad,
 	const double* d_flux, const double* d_flux_err, const double* d_centroid_col, const double* d_centroid_row, int64_t lc_pitch,
 	const double* d_time, const int32_t* d_quality, int64_t quality_target_stride, uint32_t bitmask,

@@ -22,14 +22,17 @@ FLAG_ALLNAN_FLUX = 1      # "Final lightcurve fluxes are all NaNs"   (BasePhotom
 FLAG_ALLNAN_ERR = 2       # "Final lightcurve errors are all NaNs"   (:1348-1349)
 FLAG_BAD_TIME = 4         # rms_timescale: invalid time vector        (utilities.py:248-254) -> ValueError upstream
 FLAG_NO_DETREND = 8       # "Could not detrend lightcurve for variability calculation." (:1386-1391): detrend = 0
+FLAG_TOO_MANY_BINS = 16   # device only: more time bins than the kernel's bin array holds, on a series that is not time-ordered (rms_hour = NaN)
 
 
-def diagnostics(time, quality, flux, flux_err, pos_centroid, sumimage=None, mask=None, bitmask=TESS_DEFAULT_BITMASK):
+def diagnostics(time, quality, flux, flux_err, pos_centroid, sumimage=None, mask=None, bitmask=TESS_DEFAULT_BITMASK,
+	timescale=3600/86400):
 	"""
 	BasePhotometry.py:1343-1401 for one target with status OK / WARNING.
 
 	Returns a dict with the keys of :data:`COLUMNS` (``flags`` as int).  Where the reference raises
-	``ValueError`` the corresponding flag is set and the remaining values are NaN.
+	``ValueError`` the corresponding flag is set and the remaining values are NaN.  ``timescale``: the bin width of ``rms_hour``
+	in days (the reference always passes one hour, :1365).
 	"""
 	out = {k: np.nan for k in COLUMNS}
 	out['flags'] = 0
@@ -60,7 +63,7 @@ def diagnostics(time, quality, flux, flux_err, pos_centroid, sumimage=None, mask
 		rel_err = np.abs(1/mean_flux) * gerr # :1361
 		out['variance'] = np.nanvar(rel, ddof=1) # :1364
 		try:
-			out['rms_hour'] = rms_timescale(gtime, rel, timescale=3600/86400) # :1365
+			out['rms_hour'] = rms_timescale(gtime, rel, timescale=timescale) # :1365
 		except ValueError:
 			out['flags'] |= FLAG_BAD_TIME
 		out['ptp'] = np.nanmedian(np.abs(np.diff(rel))) if len(rel) > 1 else np.nan # :1366
@@ -76,6 +79,11 @@ def diagnostics(time, quality, flux, flux_err, pos_centroid, sumimage=None, mask
 					p = np.polyfit(gtime[indx] - mintime, rel[indx], 3, w=1/rel_err[indx]) # :1382
 					detrend = np.polyval(p, gtime - mintime)
 				except np.exceptions.RankWarning:
+					out['flags'] |= FLAG_NO_DETREND
+				except np.linalg.LinAlgError:
+					# one fitted cadence: polyfit divides the Vandermonde columns by their norms, three of which are zero, and
+					# the SVD of the NaNs "did not converge".  The reference itself fails there (BasePhotometry.py:1381 catches
+					# only RankWarning); the engine reports the flag instead, with detrend = 0 as for a rank-deficient fit.
 					out['flags'] |= FLAG_NO_DETREND
 		else:
 			out['flags'] |= FLAG_NO_DETREND

@@ -304,17 +304,21 @@ __global__ __launch_bounds__(kThreads) void tp_diagnostics_kernel(DiagArgs a)
 	// ---- rms on the one-hour time scale (utilities.py:227-264)
 	double rms_hour = nan;
 	{
-		int cf = 0, ct = 0;
+		int cf = 0, cfin = 0, ct = 0;
 		double tmn = __builtin_inf(), tmx = -__builtin_inf();
 		for (int g = tid; g < Ng; g += kThreads) {
 			cf += !is_nan(gflux[g]);
+			cfin += is_finite(gflux[g]);
 			const double t = gtime_at(g);
 			if (!is_nan(t)) { ct++; if (t < tmn) tmn = t; if (t > tmx) tmx = t; }
 		}
-		const double nfl = block_sum((double)cf, red), nt = block_sum((double)ct, red);
+		const double nfl = block_sum((double)cf, red), nfin = block_sum((double)cfin, red), nt = block_sum((double)ct, red);
 		const double tmin = block_min(tmn, red), tmax = block_max(tmx, red);
 		if (Ng > 0 && nfl > 0.0) {
 			if (nt == 0.0 || !is_finite(tmin) || !is_finite(tmax) || !(tmax - tmin > 0.0)) flags |= F_BAD_TIME;
+			// samples that are not NaN but none finite (a median flux of exactly 0: rel = +-inf): binned_statistic gets an empty
+			// selection and raises the same ValueError as an invalid time vector (:261)
+			else if (nfin == 0.0) flags |= F_BAD_TIME;
 			else {
 				const double ts = a.timescale;
 				const double nbd = ceil((tmax - tmin) / ts); // len(np.arange(tmin, tmax, ts))
@@ -453,7 +457,11 @@ __global__ __launch_bounds__(kThreads) void tp_diagnostics_kernel(DiagArgs a)
 		double s = 0.0; int cn = 0;
 		for (int g = tid; g < Ng; g += kThreads) {
 			double d = gflux[g];
-			if (have_fit) { const double u = (gtime_at(g) - mid) / half; d -= ((pc[3] * u + pc[2]) * u + pc[1]) * u + pc[0]; }
+			if (have_fit) {
+				// np.polyval starts its Horner scheme from y = 0: at a time that is not finite the detrend is 0 * inf = NaN, not +-inf
+				const double u = (gtime_at(g) - mid) / half;
+				d = is_finite(u) ? d - (((pc[3] * u + pc[2]) * u + pc[1]) * u + pc[0]) : nan;
+			}
 			srt[g] = d;
 			if (!is_nan(d)) { s += d; cn++; }
 		}

@@ -265,6 +265,9 @@ def lightcurve_diagnostics(ctx, lc, time, quality, status=None, sumimage=None, m
 	Light-curve diagnostics of a batch (BasePhotometry.py:1343-1407, utilities.py:227-264).
 	``lc``: :class:`LightCurves`; ``time``: float64 DeviceArray ``(T,)``; ``quality`` as in :func:`sumimage`.
 	Returns float64 DeviceArray ``(Nt, 10)`` with the columns :data:`DIAGNOSTICS_COLUMNS`.
+	``flags`` is a sum of the bits 1 (all fluxes NaN), 2 (all errors NaN), 4 (invalid time vector, or samples but no finite one:
+	``rms_hour`` is NaN), 8 (no detrending: ``detrend = 0`` in ``variability``) and 16 (device only: more ``timescale`` bins than
+	``max(T, 256)`` on a series that is not in time order; ``rms_hour`` is NaN).  2-D ``quality`` ``(Nt, T)``: one row per target.
 	"""
 	Nt, T = lc.n_targets, lc.n_cad
 	if out is None:

@@ -6,14 +6,15 @@ light curves with NaNs, flagged cadences, gaps and degenerate cases.
 
 Tolerances: medians (mean_flux, ptp, centroid), mask_size and edge_flux are selections / integer / the same summation
 order -> exact; variance, rms_hour use tree sums instead of numpy's pairwise sums -> 1e-12 relative; variability goes
-through a differently conditioned least-squares solve -> 1e-9 relative.
+through a differently conditioned least-squares solve -> 1e-9 relative (``check`` of tests/diagnostics_common.py).
 """
 import os
 import numpy as np
 import pytest
 
+from diagnostics_common import run as _run, check as _check # the launch and the comparison, shared with test_gpu_diagnostics_edges.py
+
 pytestmark = pytest.mark.gpu
-EXACT = ('mean_flux', 'ptp', 'pos_centroid_col', 'pos_centroid_row', 'mask_size', 'edge_flux')
 
 
 @pytest.fixture(scope='module')
@@ -22,33 +23,6 @@ def ctx():
 	c = Context(0)
 	yield c
 	c.close()
-
-
-def _run(ctx, time, quality, flux, flux_err, cen, status=None, sumimage=None, mask=None):
-	from photometry_amd import engine
-	Nt, T = flux.shape
-	lc = engine.LightCurves(ctx, Nt, T)
-	block = np.zeros((5, Nt, T))
-	block[0], block[1], block[3], block[4] = flux, flux_err, cen[..., 0], cen[..., 1]
-	ctx._check(ctx.lib.tp_memcpy_h2d(ctx.handle, lc.block.ptr, np.ascontiguousarray(block).ctypes.data, block.nbytes))
-	out = engine.lightcurve_diagnostics(ctx, lc, ctx.array(np.asarray(time, dtype='float64')), ctx.array(np.asarray(quality, dtype='int32')),
-		status=None if status is None else ctx.array(np.asarray(status, dtype='int32')),
-		sumimage=None if sumimage is None else ctx.array(np.asarray(sumimage, dtype='float64')),
-		mask=None if mask is None else ctx.array(np.asarray(mask, dtype='uint8')))
-	ctx.sync()
-	return out.to_host()
-
-
-def _check(got, ref, tag=''):
-	from photometry_amd.engine import DIAGNOSTICS_COLUMNS as COLS
-	for j, key in enumerate(COLS):
-		g, r = got[j], ref[key]
-		if key == 'flags':
-			assert int(g) == int(r), (tag, key, g, r)
-		elif key in EXACT:
-			assert (g == r) or (np.isnan(g) and np.isnan(r)), (tag, key, g, r)
-		else:
-			np.testing.assert_allclose(g, r, rtol=1e-9 if key == 'variability' else 1e-12, equal_nan=True, err_msg=f'{tag} {key}')
 
 
 def test_golden_reference_photometry(ctx, golden_dir):
@@ -67,7 +41,8 @@ def test_golden_reference_photometry(ctx, golden_dir):
 		_check(got[i], ref, tag=f'case{i}')
 
 
-# 6000 and 19500 cadences (2-minute data of a sector): the series arrays no longer fit the LDS and move to HBM scratch
+# 19500 cadences (2-minute data of a sector): the series arrays no longer fit the LDS and move to HBM scratch.  6000 are still
+# reduced out of LDS (148 KB of the 160); the two sizes on either side of the switch are in test_gpu_diagnostics_edges.py
 @pytest.mark.parametrize('T', [7, 300, 1300, 2500, 6000, 19500])
 def test_against_oracle(ctx, T):
 	from oracle import diagnostics as odiag
