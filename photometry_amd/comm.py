@@ -55,6 +55,20 @@ def packed_block_layout(n_targets, n_cad, height, width, psf=False, align=256, n
 	return layout, off
 
 
+def frames_block_fields(n_targets, n_cad, height, width, cat_capacity):
+	"""
+	The fields of the packed block of one group of the native frames engine, in order, as ``(name, shape, dtype, nbytes)``:
+	``packed_block_layout(n_targets, n_cad, height, width, n_cat=cat_capacity, extras=True)`` written out (every field starts at
+	the next multiple of 256 bytes; ``BlockLayout`` of ``csrc/frames_rules.h`` is the same table).  ``pipeline.FramesJob.collect``
+	walks it once per group: through :func:`packed_block_layout` that was 1.0 ms of a 7.7 ms call.
+	"""
+	m, T, H, W, cc = n_targets, n_cad, height, width, cat_capacity
+	P = H * W
+	return (('lc', (5, m, T), 'float64', 40 * m * T), ('contamination', (m,), 'float64', 8 * m), ('status', (m,), 'int32', 4 * m),
+		('flags', (m,), 'int32', 4 * m), ('mask', (m, H, W), 'uint8', m * P), ('cat_in_mask', (cc,), 'uint8', cc),
+		('sumimage', (m, H, W), 'float64', 8 * m * P), ('diagnostics', (m, 10), 'float64', 80 * m))
+
+
 #: the planes of ``lc`` that are float32 sums widened on store (AperturePhotometry/photometry.py:172-201: flux, flux_err,
 #: flux_background) -- a gathered block carries them as float32 and loses nothing; planes 3, 4 (the centroids) are float64
 LC_FLOAT32_PLANES = 3

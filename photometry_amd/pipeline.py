@@ -654,16 +654,13 @@ class FramesJob(object):
 		for g in range(ng.value):
 			m, H, W, cap, ncat, blk, nb = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int64(), ctypes.c_int64(), ctypes.c_void_p(), ctypes.c_uint64()
 			lib.tp_frames_group(h, g, ctypes.byref(m), ctypes.byref(H), ctypes.byref(W), ctypes.byref(cap), ctypes.byref(ncat), ctypes.byref(blk), ctypes.byref(nb))
-			# the fields of the packed block (comm.packed_block_layout with the catalogue flags and the extras), as read-only views of the
-			# page-locked block: offsets written out here -- this loop is the host's share of a batch (it was 1.0 ms of a 7.7 ms call
-			# through packed_block_layout / unpack_block and one ctypes array TYPE per block size)
-			mm, Hh, Ww, cc = m.value, H.value, W.value, cap.value
-			P = Hh * Ww
+			# the fields of the packed block (comm.frames_block_fields: comm.packed_block_layout with the catalogue flags and the extras,
+			# written out), as read-only views of the page-locked block -- this loop is the host's share of a batch (it was 1.0 ms of a
+			# 7.7 ms call through packed_block_layout / unpack_block and one ctypes array TYPE per block size)
+			mm, cc = m.value, cap.value
 			host = _view_bytes(blk.value, nb.value)
 			grp, off = {}, 0
-			for name, shape, dtype, size in (('lc', (5, mm, T), 'float64', 40 * mm * T), ('contamination', (mm,), 'float64', 8 * mm), ('status', (mm,), 'int32', 4 * mm),
-				('flags', (mm,), 'int32', 4 * mm), ('mask', (mm, Hh, Ww), 'uint8', mm * P), ('cat_in_mask', (cc,), 'uint8', cc),
-				('sumimage', (mm, Hh, Ww), 'float64', 8 * mm * P), ('diagnostics', (mm, 10), 'float64', 80 * mm)):
+			for name, shape, dtype, size in tpcomm.frames_block_fields(mm, T, H.value, W.value, cc):
 				grp[name] = host[off:off + size].view(dtype).reshape(shape)
 				off = -(-(off + size) // 256) * 256
 			if off != nb.value:
