@@ -26,10 +26,10 @@
 //
 // Roofline: the FP64 pipe, not HBM: the image cube is read once (P*T*4 bytes per target).  The fit of a target
 // with up to 4 stars runs on the matrix cores (linpsf_mfma.hip: ONE quartic spline per star and pixel over the knot intervals the
-// star visits, cadences in natural order); the kernels of this file plan it (tp_linpsf_plan_kernel), build its coefficients
-// (tp_linpsf_coef_kernel) and finalise it (tp_linpsf_finalize_m_kernel), and fit the targets that do not qualify on the vector
-// ALUs (tp_linpsf_fit2_kernel: a biquartic per pixel and table origin, cadences sorted by origin; tp_linpsf_fit_direct_kernel;
-// tp_linpsf_fit_many_kernel).
+// star visits, cadences in natural order); the kernels of linpsf_plan.hip plan it (tp_linpsf_plan_kernel) and build its coefficients
+// (tp_linpsf_coef_kernel); the kernels of this file finalise it (tp_linpsf_finalize_m_kernel) and fit the targets that do not qualify
+// on the vector ALUs (tp_linpsf_fit2_kernel: a biquartic per pixel and table origin, cadences sorted by origin;
+// tp_linpsf_fit_direct_kernel; tp_linpsf_fit_many_kernel).  The C entry is here.
 #include "linpsf_common.h"
 
 void* tp_ctx_scratch(tp_ctx* ctx, size_t bytes); // aperture.hip
@@ -180,14 +180,12 @@ __global__ __launch_bounds__(512) void tp_linpsf_fit_direct_kernel(FitArgs a, co
 //   B. every cadence evaluates its stars' PRF values by Horner (24 FMAs per star and pixel instead of 169 table reads and
 //      ~230 flops) and accumulates the normal equations.
 // The arithmetic differs from the direct contraction only by rounding (1e-15 relative).  A target whose stars visit more
-// origins than max_origins (pointing excursions) is flagged for the general kernel.
+// origins than kMaxOrigins (pointing excursions) is flagged for the general kernel.
 //--------------------------------------------------------------------------------------------------
 // (kEdgePoly and axis_phase live in linpsf_dev.h: the non-linear PSF kernel uses the same polynomial form)
 
-struct StarBox { int axmin, axmax, bymin, bymax, jmin, jmax, imin, imax; };
-
 //--------------------------------------------------------------------------------------------------
-// Three kernels (a single kernel that kept the 110 KB table in LDS, one 768-thread workgroup per CU, and read the 25
+// Three kernels, plan and coef in linpsf_plan.hip (a single kernel that kept the 110 KB table in LDS, one 768-thread workgroup per CU, and read the 25
 // coefficients of every Horner evaluation from LDS in every lane: 4 SIMDs share one LDS, so the coefficient reads, not the
 // FMAs, set its pace -- 24 ms for the C3 batch):
 //   plan  per target the boxes of its stars over ALL cadences (table origins visited, pixels that can be inside the
@@ -218,681 +216,6 @@ __device__ __forceinline__ double fma_sgpr_addend(double a, double b, double c) 
 	double r;
 	asm("v_fma_f64 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "s"(c));
 	return r;
-}
-
-// inverse of the reflected Gray code n ^ (n >> 1) on 4 bits: the place of a membership pattern in the order 1,3,2,6,7,5,4,12,...
-__device__ __forceinline__ unsigned gray_rank4(unsigned g) { g ^= g >> 2; g ^= g >> 1; return g & 15u; }
-
-// one segment of a target's series: the knot intervals every star visits in it (lo / hi per star and axis; hi < lo: never valid)
-__device__ __forceinline__ void emit_segment(SegPlan& g, int target, int t0, int t1, const int (&lo)[kMfmaStars][2], const int (&hi)[kMfmaStars][2],
-	int ns, const StarPlan* spl)
-{
-	g.target = target; g.tile0 = t0; g.tile1 = t1; g.kdoubles = 0; g.koff = 0;
-	for (int s = 0; s < kMfmaStars; ++s) {
-		const bool any = (s < ns) && (hi[s][0] >= lo[s][0]) && (hi[s][1] >= lo[s][1]) && (spl[s].nc > 0);
-		g.axmin[s] = any ? lo[s][0] : 0; g.bymin[s] = any ? lo[s][1] : 0;
-		g.na[s] = (uint8_t)(any ? (hi[s][0] - lo[s][0] + 1) : 0); g.nb[s] = (uint8_t)(any ? (hi[s][1] - lo[s][1] + 1) : 0);
-		g.ksub[s] = 0;
-	}
-}
-
-// Decides on the device (the knots live there) whether the uniform-grid forms apply: totals[kTotGeneral] = 1 if not.  The plan
-// kernel then does nothing and the host, which reads the totals anyway, sends every target to the general kernels.
-__global__ __launch_bounds__(64) void tp_linpsf_grid_kernel(const double* __restrict__ tx, const double* __restrict__ ty, int n, double cutoff, int force,
-	unsigned long long* __restrict__ totals)
-{
-	if (threadIdx.x != 0 || blockIdx.x != 0) return;
-	const bool ok = !force && (cutoff <= 5.25) && uniform_grid_ok(tx, n, cutoff) && uniform_grid_ok(ty, n, cutoff);
-	if (!ok) totals[kTotGeneral] = 1ull;
-}
-
-// totals: kTotPolyItems items (25 doubles each) of the polynomial store; kTotKDoubles doubles of the matrix-core store (laid behind
-// it); kTotPolyTargets targets left to the vector-ALU fit; kTotClass0 + c targets of class c of the matrix-core fit (class_lists[c][..])
-__global__ __launch_bounds__(256) void tp_linpsf_plan_kernel(FitArgs a, StarPlan* __restrict__ plans, int32_t* __restrict__ todo,
-	unsigned long long* __restrict__ totals, int max_origins, int32_t* __restrict__ order, int sort_n,
-	MPlan* __restrict__ mplans, uint16_t* __restrict__ ulist, uint8_t* __restrict__ usig, int use_mfma, int32_t* __restrict__ class_lists, int n_targets,
-	SegPlan* __restrict__ segs, int32_t* __restrict__ seg_lists)
-{
-	extern __shared__ unsigned long long skeys[];   // [sort_n] (key of the cadence's origins) * 8192 + cadence, or nothing
-	// matrix-core path: the knot intervals every star visits per 16-cadence tile (x lowest / highest, y lowest / highest; the
-	// sentinel 32767 / -32768: no valid position in the tile), and the segments the series is cut into
-	__shared__ __align__(8) short s_tr[kMfmaStars][kMfmaCadTiles][4];
-	__shared__ SegPlan s_seg[kMfmaSegs];
-	__shared__ int s_nseg, s_walk, s_too_many;
-	__shared__ StarBox sbox[kMaxStars];
-	__shared__ StarPlan spl[kMaxStars];
-	__shared__ double spos[4][kMfmaStars][4];      // per wavefront and star: min / max of the row and column position
-	__shared__ double srange[kMfmaStars][4];
-	__shared__ unsigned pkeys[kMfmaPixels];
-	__shared__ unsigned s_tiles[kMfmaStars], s_etiles[kMfmaStars];
-	__shared__ int s_ok, s_nkeys, s_path;
-	__shared__ double kn[160], kny[160];
-	const int target = blockIdx.x, tid = threadIdx.x;
-	const int n = a.n;
-	const int64_t s0 = a.star_offsets[target];
-	const int ns = (int)(a.star_offsets[target + 1] - s0);
-	int32_t* ord = order + (int64_t)target * a.n_cad;
-	if (totals[kTotGeneral] != 0) return;   // tp_linpsf_grid_kernel found a grid / cut-off the uniform forms cannot take: the general kernels fit every target
-	if (ns > kMaxStars) return;   // the many-star kernel's targets
-	if (tid == 0) { s_ok = 0; s_nkeys = 0; s_path = kPathPoly; s_nseg = 0; }
-	const bool want_segments = use_mfma && ns >= 1 && ns <= kMfmaStars;
-	for (int i = tid; i < n + 4; i += 256) { kn[i] = a.knots_x[i]; kny[i] = a.knots_y[i]; }
-	if (tid < kMaxStars) {
-		sbox[tid].axmin = sbox[tid].bymin = sbox[tid].jmin = sbox[tid].imin = 0x7fffffff;
-		sbox[tid].axmax = sbox[tid].bymax = sbox[tid].jmax = sbox[tid].imax = -0x7fffffff;
-	}
-	if (tid < kMfmaStars) { s_tiles[tid] = 0u; s_etiles[tid] = 0u; }
-	__syncthreads();
-	const double h = kn[5] - kn[4], hy = kny[5] - kny[4];
-	const double cutoff = a.cutoff;
-	for (int s = 0; s < ns; ++s) {
-		const int big = 0x7fffffff;
-		int lo[4] = {big, big, big, big}, hi[4] = {-big, -big, -big, -big};
-		double pr[4] = {1e300, -1e300, 1e300, -1e300};   // row min, row max, column min, column max over the valid cadences
-		// (whole rounds of 256 cadences, so that the 16 lanes of a tile of cadences reduce together)
-		for (int k = tid; k < ((a.n_cad + 255) & ~255); k += 256) {
-			const bool in_series = k < a.n_cad;
-			const double srow = in_series ? a.pos_row[(s0 + s) * a.pos_pitch + k] : __builtin_nan(""), scol = in_series ? a.pos_col[(s0 + s) * a.pos_pitch + k] : __builtin_nan("");
-			double phx, phy; int ax0, by0;
-			const bool vx = axis_phase(kn, n, scol, h, phx, ax0);
-			const bool vy = axis_phase(kny, n, srow, hy, phy, by0);
-			if (want_segments && s < kMfmaStars) {
-				// consecutive lanes hold consecutive cadences: 16 of them are one tile
-				int t0 = (vx && vy) ? ax0 : 32767, t1 = (vx && vy) ? ax0 : -32768, t2 = (vx && vy) ? by0 : 32767, t3 = (vx && vy) ? by0 : -32768;
-#pragma unroll
-				for (int off = 1; off < 16; off <<= 1) {
-					const int o0 = __shfl_xor(t0, off, 64), o1 = __shfl_xor(t1, off, 64), o2 = __shfl_xor(t2, off, 64), o3 = __shfl_xor(t3, off, 64);
-					t0 = (o0 < t0) ? o0 : t0; t1 = (o1 > t1) ? o1 : t1; t2 = (o2 < t2) ? o2 : t2; t3 = (o3 > t3) ? o3 : t3;
-				}
-				if ((tid & 15) == 0 && in_series && (k >> 4) < kMfmaCadTiles) {
-					// (an interval index beyond 16 bits -- a position thousands of pixels off -- can only come with others that are
-					// not: the span test below then refuses the target; clamping keeps the order)
-					auto cl = [](int v) { return (short)((v < -32767) ? -32767 : ((v > 32766) ? 32766 : v)); };
-					const bool any = t1 >= t0;
-					s_tr[s][k >> 4][0] = any ? cl(t0) : (short)32767; s_tr[s][k >> 4][1] = any ? cl(t1) : (short)-32768;
-					s_tr[s][k >> 4][2] = any ? cl(t2) : (short)32767; s_tr[s][k >> 4][3] = any ? cl(t3) : (short)-32768;
-				}
-			}
-			if (vx && vy) {
-				const int v0[4] = {ax0, by0, (int)floor(scol - cutoff), (int)floor(srow - cutoff)};
-				const int v1[4] = {ax0, by0, (int)ceil(scol + cutoff), (int)ceil(srow + cutoff)};
-#pragma unroll
-				for (int e = 0; e < 4; ++e) { lo[e] = (v0[e] < lo[e]) ? v0[e] : lo[e]; hi[e] = (v1[e] > hi[e]) ? v1[e] : hi[e]; }
-				pr[0] = fmin(pr[0], srow); pr[1] = fmax(pr[1], srow); pr[2] = fmin(pr[2], scol); pr[3] = fmax(pr[3], scol);
-			}
-		}
-#pragma unroll
-		for (int off = 32; off > 0; off >>= 1) {
-#pragma unroll
-			for (int e = 0; e < 4; ++e) {
-				const int l2 = __shfl_xor(lo[e], off, 64), h2 = __shfl_xor(hi[e], off, 64);
-				lo[e] = (l2 < lo[e]) ? l2 : lo[e];
-				hi[e] = (h2 > hi[e]) ? h2 : hi[e];
-			}
-			pr[0] = fmin(pr[0], __shfl_xor(pr[0], off, 64)); pr[1] = fmax(pr[1], __shfl_xor(pr[1], off, 64));
-			pr[2] = fmin(pr[2], __shfl_xor(pr[2], off, 64)); pr[3] = fmax(pr[3], __shfl_xor(pr[3], off, 64));
-		}
-		if ((tid & 63) == 0) {
-			if (hi[0] >= lo[0]) {
-				atomicMin(&sbox[s].axmin, lo[0]); atomicMax(&sbox[s].axmax, hi[0]);
-				atomicMin(&sbox[s].bymin, lo[1]); atomicMax(&sbox[s].bymax, hi[1]);
-				atomicMin(&sbox[s].jmin, lo[2]); atomicMax(&sbox[s].jmax, hi[2]);
-				atomicMin(&sbox[s].imin, lo[3]); atomicMax(&sbox[s].imax, hi[3]);
-			}
-			if (s < kMfmaStars) {
-#pragma unroll
-				for (int e = 0; e < 4; ++e) spos[tid >> 6][s][e] = pr[e];
-			}
-		}
-	}
-	__syncthreads();
-	if (tid == 0) {
-		bool too_many = false;
-		for (int s = 0; s < ns; ++s) {
-			StarBox b = sbox[s];
-			StarPlan& q = spl[s];
-			q.axmin = q.bymin = 0; q.nby = 1; q.nc = 0; q.jmin = q.imin = 0; q.jmax = q.imax = -1; q.item_off = 0;
-			if (b.axmax < b.axmin) continue;   // never a valid position: an all-zero column
-			if (b.jmin < 0) b.jmin = 0;
-			if (b.jmax > a.width - 1) b.jmax = a.width - 1;
-			if (b.imin < 0) b.imin = 0;
-			if (b.imax > a.height - 1) b.imax = a.height - 1;
-			if (b.jmax < b.jmin || b.imax < b.imin) continue;   // never on the stamp
-			q.axmin = b.axmin; q.bymin = b.bymin; q.nby = b.bymax - b.bymin + 1; q.nc = (b.axmax - b.axmin + 1) * q.nby;
-			q.jmin = b.jmin; q.jmax = b.jmax; q.imin = b.imin; q.imax = b.imax;
-			if (q.nc > max_origins) too_many = true;
-		}
-		for (int s = 0; s < ns && s < kMfmaStars; ++s) {
-			srange[s][0] = fmin(fmin(spos[0][s][0], spos[1][s][0]), fmin(spos[2][s][0], spos[3][s][0]));
-			srange[s][1] = fmax(fmax(spos[0][s][1], spos[1][s][1]), fmax(spos[2][s][1], spos[3][s][1]));
-			srange[s][2] = fmin(fmin(spos[0][s][2], spos[1][s][2]), fmin(spos[2][s][2], spos[3][s][2]));
-			srange[s][3] = fmax(fmax(spos[0][s][3], spos[1][s][3]), fmax(spos[2][s][3], spos[3][s][3]));
-		}
-		// The matrix-core path: the series cut into segments of 16-cadence tiles inside which no star visits more than kMfmaSpan knot
-		// intervals per axis (greedy: a segment ends before the tile that would take a star beyond that).  A star that does so inside
-		// ONE tile (jitter of a third of a pixel within 16 cadences), more than kMfmaSegs segments, or a series beyond
-		// 16 * kMfmaCadTiles cadences leave the target to the vector-ALU kernels.
-		// (a target without a fitted star -- its own catalogue entry dropped for a NaN magnitude or position -- has no class list:
-		// the polynomial path finalises it as 'All target flux values are NaN')
-		bool seg_ok = want_segments && a.height * a.width <= 65535 && a.n_cad <= 16 * kMfmaCadTiles;
-		int nseg = 0;
-		s_walk = 0;
-		if (seg_ok) {
-			// the common case needs no walk: no star leaves its three intervals during the whole series (no drift) -- one segment with
-			// the boxes found above
-			int lo[kMfmaStars][2], hi[kMfmaStars][2];
-			for (int s = 0; s < kMfmaStars; ++s) { lo[s][0] = lo[s][1] = 32767; hi[s][0] = hi[s][1] = -32768; }
-			bool whole = true;
-			for (int s = 0; s < ns; ++s) {
-				const StarBox b = sbox[s];
-				if (b.axmax < b.axmin) continue;
-				if (b.axmax - b.axmin + 1 > kMfmaSpan || b.bymax - b.bymin + 1 > kMfmaSpan || b.axmin < -32000 || b.axmax > 32000 || b.bymin < -32000 || b.bymax > 32000) whole = false;
-				lo[s][0] = b.axmin; hi[s][0] = b.axmax; lo[s][1] = b.bymin; hi[s][1] = b.bymax;
-			}
-			if (whole) { emit_segment(s_seg[0], target, 0, (a.n_cad + 15) >> 4, lo, hi, ns, spl); nseg = 1; }
-			else s_walk = 1;   // the first wavefront walks the tiles (below)
-		}
-		s_nseg = seg_ok ? nseg : 0;
-		s_too_many = too_many ? 1 : 0;
-	}
-	__syncthreads();
-	if (s_walk && tid < 64) {
-		// Greedy segmentation by one wavefront, a window of 64 tiles at a time: lane j holds the knot intervals of tile pos + j,
-		// an inclusive min / max scan gives every lane the range of [segment start, its tile], the first lane whose range goes
-		// beyond the span ends the segment before its tile.  (One thread walking the tiles through LDS took 40 us per target.)
-		const int ntile = (a.n_cad + 15) >> 4;
-		const int lane = tid;
-		int nseg = 0, seg_start = 0, pos = 0;
-		bool ok = true;
-		int clo[kMfmaStars][2], chi[kMfmaStars][2];   // the range of the open segment up to the window (wave-uniform)
-#pragma unroll
-		for (int s = 0; s < kMfmaStars; ++s) { clo[s][0] = clo[s][1] = 32767; chi[s][0] = chi[s][1] = -32768; }
-		while (pos < ntile && ok) {
-			const int t = pos + lane;
-			const bool valid = t < ntile;
-			int pl[kMfmaStars][2], pu[kMfmaStars][2];
-			bool fits = true;
-#pragma unroll
-			for (int s = 0; s < kMfmaStars; ++s) {
-#pragma unroll
-				for (int e = 0; e < 2; ++e) {
-					int l = (valid && s < ns) ? (int)s_tr[s][valid ? t : 0][2 * e] : 32767, u = (valid && s < ns) ? (int)s_tr[s][valid ? t : 0][2 * e + 1] : -32768;
-					if (lane == 0) { l = (clo[s][e] < l) ? clo[s][e] : l; u = (chi[s][e] > u) ? chi[s][e] : u; }
-#pragma unroll
-					for (int off = 1; off < 64; off <<= 1) {
-						const int ol = __shfl_up(l, off, 64), ou = __shfl_up(u, off, 64);
-						if (lane >= off) { l = (ol < l) ? ol : l; u = (ou > u) ? ou : u; }
-					}
-					pl[s][e] = l; pu[s][e] = u;
-					if (u >= l && u - l + 1 > kMfmaSpan) fits = false;
-				}
-			}
-			const unsigned long long bad = __ballot(valid && !fits);
-			if (bad == 0ull) {
-				const int lastl = (ntile - 1 - pos < 63) ? (ntile - 1 - pos) : 63;
-#pragma unroll
-				for (int s = 0; s < kMfmaStars; ++s)
-#pragma unroll
-					for (int e = 0; e < 2; ++e) { clo[s][e] = __shfl(pl[s][e], lastl, 64); chi[s][e] = __shfl(pu[s][e], lastl, 64); }
-				pos += 64;
-				continue;
-			}
-			const int c = __builtin_ctzll(bad);
-			if (c == 0 && pos == seg_start) { ok = false; break; }   // one tile of cadences alone goes beyond the span
-			int lo[kMfmaStars][2], hi[kMfmaStars][2];
-#pragma unroll
-			for (int s = 0; s < kMfmaStars; ++s)
-#pragma unroll
-				for (int e = 0; e < 2; ++e) {
-					const int sl = __shfl(pl[s][e], (c > 0) ? (c - 1) : 0, 64), su = __shfl(pu[s][e], (c > 0) ? (c - 1) : 0, 64);
-					lo[s][e] = (c > 0) ? sl : clo[s][e]; hi[s][e] = (c > 0) ? su : chi[s][e];
-					clo[s][e] = 32767; chi[s][e] = -32768;
-				}
-			if (nseg >= kMfmaSegs) { ok = false; break; }
-			if (lane == 0) emit_segment(s_seg[nseg], target, seg_start, pos + c, lo, hi, ns, spl);
-			++nseg;
-			seg_start = pos = pos + c;
-		}
-		if (ok) {
-			if (nseg >= kMfmaSegs) ok = false;
-			else { if (lane == 0) emit_segment(s_seg[nseg], target, seg_start, ntile, clo, chi, ns, spl); ++nseg; }
-		}
-		if (lane == 0) s_nseg = ok ? nseg : 0;
-	}
-	__syncthreads();
-	if (tid == 0) {
-		if (s_nseg > 0) s_path = kPathMfma;
-		else if (s_too_many) s_path = kPathDirect;   // pointing excursions over many knots: the general kernel
-	}
-	__syncthreads();
-	if (s_path == kPathMfma) {
-		// the pixels some star can reach at some cadence: nearer than the cut-off to the rectangle its position sweeps
-		const int npix = a.height * a.width;
-		const double reach = (cutoff + 1e-6) * (cutoff + 1e-6), always = (cutoff - 1e-6) * (cutoff - 1e-6);
-		for (int p = tid; p < npix; p += 256) {
-			const int i = p / a.width, j = p - i * a.width;
-			unsigned sig = 0u, edge = 0u;
-			for (int s = 0; s < ns; ++s) {
-				if (spl[s].nc <= 0) continue;
-				const double dr = fmax(0.0, fmax(srange[s][0] - (double)i, (double)i - srange[s][1]));
-				const double dc = fmax(0.0, fmax(srange[s][2] - (double)j, (double)j - srange[s][3]));
-				if (dr * dr + dc * dc < reach) {
-					sig |= 1u << s;
-					// an "edge" pixel is inside the cut-off at some positions of the star and outside at others: the farthest
-					// corner of the rectangle the position sweeps is not inside
-					const double fr = fmax(fabs((double)i - srange[s][0]), fabs((double)i - srange[s][1]));
-					const double fc = fmax(fabs((double)j - srange[s][2]), fabs((double)j - srange[s][3]));
-					if (!(fr * fr + fc * fc < always)) edge |= 1u << s;
-				}
-			}
-			if (sig) {
-				const int idx = atomicAdd(&s_nkeys, 1);
-				// order: membership pattern (Gray rank), interior pixels before edge pixels, raster
-				if (idx < kMfmaPixels) pkeys[idx] = (gray_rank4(sig) << 25) | ((edge ? 1u : 0u) << 24) | (edge << 20) | (sig << 16) | (unsigned)p;
-			}
-		}
-		__syncthreads();
-		const int nk = s_nkeys;
-		if (nk > kMfmaPixels) {   // a large stamp: the vector-ALU kernels
-			if (tid == 0) { bool tm = false; for (int s = 0; s < ns; ++s) if (spl[s].nc > max_origins) tm = true; s_path = tm ? kPathDirect : kPathPoly; }
-		}
-		else {
-			uint16_t* ul = ulist + (int64_t)target * kMfmaPixels;
-			uint8_t* us = usig + (int64_t)target * kMfmaPixels;
-			if (tid < nk) {
-				const unsigned key = pkeys[tid];
-				int r = 0;
-				for (int q = 0; q < nk; ++q) r += (pkeys[q] < key) ? 1 : 0;
-				const unsigned sig = (key >> 16) & 15u, edge = (key >> 20) & 15u;
-				ul[r] = (uint16_t)(key & 0xffffu);
-				us[r] = (uint8_t)(sig | (edge << 4));
-				for (int s = 0; s < ns; ++s) {
-					if (sig & (1u << s)) atomicOr(&s_tiles[s], 1u << (r >> 4));
-					if (edge & (1u << s)) atomicOr(&s_etiles[s], 1u << (r >> 4));
-				}
-			} else if (tid < kMfmaPixels) { ul[tid] = (uint16_t)0xffffu; us[tid] = (uint8_t)0; }
-		}
-		__syncthreads();
-	}
-	if (tid == 0) {
-		int path = s_path;
-		if (path == kPathMfma) {
-			// per segment one spline per star over the knot intervals it visits there (at most 3 x 3), the segment's coefficient image
-			// within the LDS of its class; otherwise the vector-ALU kernels take the target
-			MPlan mp;
-			mp.n_pix = s_nkeys; mp.n_tiles = (s_nkeys + 15) >> 4; mp.n_seg = s_nseg;
-			for (int s = 0; s < kMfmaStars; ++s) {
-				mp.tiles[s] = (s < ns) ? s_tiles[s] : 0u;
-				mp.edge_tiles[s] = (s < ns) ? s_etiles[s] : 0u;
-			}
-			bool fits = true;
-			long long total = 0;
-			for (int i = 0; i < s_nseg; ++i) {
-				SegPlan& g = s_seg[i];
-				long long blocks = 0;
-				for (int s = 0; s < kMfmaStars; ++s) {
-					g.ksub[s] = (uint16_t)blocks;
-					if (g.na[s] > 0) blocks += (long long)__popc(mp.tiles[s]) * mfma_steps(g.na[s], g.nb[s]);
-				}
-				if (blocks * 512 > ((ns <= 1) ? kMfmaLdsSmall : kMfmaLdsLarge)) fits = false;
-				g.kdoubles = (int32_t)(blocks * 64);
-				g.koff = total;
-				total += blocks * 64;
-			}
-			if (fits) {
-				const long long base = (long long)atomicAdd(&totals[kTotKDoubles], (unsigned long long)total);
-				mplans[target] = mp;
-				const int cls = ns - 1;   // one launch per star count
-				const unsigned long long sat = atomicAdd(&totals[kTotSeg0 + cls], (unsigned long long)s_nseg);
-				for (int i = 0; i < s_nseg; ++i) {
-					s_seg[i].koff += base;
-					segs[(int64_t)target * kMfmaSegs + i] = s_seg[i];
-					seg_lists[(int64_t)cls * n_targets * kMfmaSegs + (int64_t)sat + i] = target * kMfmaSegs + i;
-				}
-				for (int s = 0; s < ns; ++s) plans[(int64_t)target * kMaxStars + s] = spl[s];
-				todo[target] = kPathMfma;
-				const unsigned long long at = atomicAdd(&totals[kTotClass0 + cls], 1ull);
-				class_lists[(int64_t)cls * n_targets + (int64_t)at] = target;
-			} else {
-				bool too_many = false;
-				for (int s = 0; s < ns; ++s) if (spl[s].nc > max_origins) too_many = true;
-				path = too_many ? kPathDirect : kPathPoly;
-			}
-		}
-		if (path == kPathDirect) { todo[target] = kPathDirect; atomicAdd(&totals[kTotDirectTargets], 1ull); }
-		else if (path == kPathPoly) {
-			long long items = 0;
-			for (int s = 0; s < ns; ++s) {
-				StarPlan& q = spl[s];
-				q.item_off = items;
-				if (q.nc > 0) items += (long long)q.nc * (q.jmax - q.jmin + 1) * (q.imax - q.imin + 1);
-			}
-			const long long base = (long long)atomicAdd(&totals[kTotPolyItems], (unsigned long long)items);
-			atomicAdd(&totals[kTotPolyTargets], 1ull);
-			for (int s = 0; s < ns; ++s) { spl[s].item_off += base; plans[(int64_t)target * kMaxStars + s] = spl[s]; }
-			s_ok = 1;
-		}
-	}
-	__syncthreads();
-	if (!s_ok) return;
-	// the order in which the fit kernel walks the cadences: sorted by the origins of all stars, so that the 64 cadences of a
-	// wavefront share their polynomial coefficients (the jitter straddles a knot boundary in most targets)
-	if (sort_n <= 0) { for (int k = tid; k < a.n_cad; k += 256) ord[k] = k; return; }
-	for (int k = tid; k < sort_n; k += 256) {
-		unsigned long long key = ~0ull;
-		if (k < a.n_cad) {
-			key = 0;
-			for (int s = 0; s < ns; ++s) {
-				const StarPlan q = spl[s];
-				double phx, phy; int ax0, by0;
-				const bool vx = axis_phase(kn, n, a.pos_col[(s0 + s) * a.pos_pitch + k], h, phx, ax0);
-				const bool vy = axis_phase(kny, n, a.pos_row[(s0 + s) * a.pos_pitch + k], hy, phy, by0);
-				const int cc = (vx && vy && q.nc > 0) ? ((ax0 - q.axmin) * q.nby + (by0 - q.bymin)) : 0;
-				key = key * (unsigned long long)(max_origins + 1) + (unsigned long long)cc;
-			}
-			key = key * 8192ull + (unsigned long long)k;
-		}
-		skeys[k] = key;
-	}
-	__syncthreads();
-	for (int size = 2; size <= sort_n; size <<= 1) {
-		for (int stride = size >> 1; stride > 0; stride >>= 1) {
-			for (int t = tid; t < sort_n / 2; t += 256) {
-				const int lo = ((t / stride) * (stride << 1)) + (t % stride), hi = lo + stride;
-				const bool up = ((lo & size) == 0);
-				const unsigned long long x = skeys[lo], y = skeys[hi];
-				if ((x > y) == up) { skeys[lo] = y; skeys[hi] = x; }
-			}
-			__syncthreads();
-		}
-	}
-	for (int k = tid; k < a.n_cad; k += 256) ord[k] = (int)(skeys[k] & 8191ull);
-}
-
-// the 25 coefficients (times h2) of the 13 x 13 table patch at (ax, by): kk[e][b], e = power of phi_x, b = power of phi_y
-__device__ __forceinline__ void patch_coefficients(const double* __restrict__ C, int n, int ax, int by, double h2, double (&kk)[5][5])
-{
-#pragma unroll
-	for (int e = 0; e < 5; ++e)
-#pragma unroll
-		for (int bcol = 0; bcol < 5; ++bcol) kk[e][bcol] = 0.0;
-	const double* c0 = C + (int64_t)ax * n + by;
-#pragma unroll 1
-	for (int pp = 0; pp < 13; ++pp) {
-		const double* r = c0 + pp * n;
-		double rv[13];
-#pragma unroll
-		for (int q = 0; q < 13; ++q) rv[q] = r[q];
-		const double e0 = kEdgePoly[pp][0], e1 = kEdgePoly[pp][1], e2 = kEdgePoly[pp][2], e3 = kEdgePoly[pp][3], e4 = kEdgePoly[pp][4];
-#pragma unroll
-		for (int bcol = 0; bcol < 5; ++bcol) {
-			double t = 0.0;
-#pragma unroll
-			for (int q = 0; q < 13; ++q) t = __builtin_fma(kEdgePoly[q][bcol], rv[q], t);
-			kk[0][bcol] = __builtin_fma(e0, t, kk[0][bcol]);
-			kk[1][bcol] = __builtin_fma(e1, t, kk[1][bcol]);
-			kk[2][bcol] = __builtin_fma(e2, t, kk[2][bcol]);
-			kk[3][bcol] = __builtin_fma(e3, t, kk[3][bcol]);
-			kk[4][bcol] = __builtin_fma(e4, t, kk[4][bcol]);
-		}
-	}
-#pragma unroll
-	for (int e = 0; e < 5; ++e)
-#pragma unroll
-		for (int bcol = 0; bcol < 5; ++bcol) kk[e][bcol] *= h2;
-}
-
-// The same contraction for the `na` consecutive intervals (ax, by), (ax + 1, by) .. along x at once: their 13 x 13 patches are
-// 13 + na - 1 table rows, and the inner sums t = sum_q E[q][b] C[row][by + q] of a row serve every interval that holds the row
-// (2 340 -> 1 560 multiply-adds for two intervals, 3 510 -> 2 100 for three).  Every kk[ca] gets exactly the operations
-// patch_coefficients gives it, in the same order: bit-identical.  Rows ax .. ax + 12 + na - 1 must lie inside the table.
-__device__ __forceinline__ void patch_coefficients_along_x(const double* __restrict__ C, int n, int ax, int by, double h2, int na, double (&kk)[3][5][5])
-{
-#pragma unroll
-	for (int ca = 0; ca < 3; ++ca)
-#pragma unroll
-		for (int e = 0; e < 5; ++e)
-#pragma unroll
-			for (int bcol = 0; bcol < 5; ++bcol) kk[ca][e][bcol] = 0.0;
-	const double* c0 = C + (int64_t)ax * n + by;
-#pragma unroll 1
-	for (int row = 0; row < 12 + na; ++row) {
-		const double* r = c0 + row * n;
-		double rv[13], t[5];
-#pragma unroll
-		for (int q = 0; q < 13; ++q) rv[q] = r[q];
-#pragma unroll
-		for (int bcol = 0; bcol < 5; ++bcol) {
-			double v = 0.0;
-#pragma unroll
-			for (int q = 0; q < 13; ++q) v = __builtin_fma(kEdgePoly[q][bcol], rv[q], v);
-			t[bcol] = v;
-		}
-#pragma unroll
-		for (int ca = 0; ca < 3; ++ca) {
-			const int pp = row - ca;
-			if (ca < na && pp >= 0 && pp < 13) {   // uniform
-				const double e0 = kEdgePoly[pp][0], e1 = kEdgePoly[pp][1], e2 = kEdgePoly[pp][2], e3 = kEdgePoly[pp][3], e4 = kEdgePoly[pp][4];
-#pragma unroll
-				for (int bcol = 0; bcol < 5; ++bcol) {
-					kk[ca][0][bcol] = __builtin_fma(e0, t[bcol], kk[ca][0][bcol]);
-					kk[ca][1][bcol] = __builtin_fma(e1, t[bcol], kk[ca][1][bcol]);
-					kk[ca][2][bcol] = __builtin_fma(e2, t[bcol], kk[ca][2][bcol]);
-					kk[ca][3][bcol] = __builtin_fma(e3, t[bcol], kk[ca][3][bcol]);
-					kk[ca][4][bcol] = __builtin_fma(e4, t[bcol], kk[ca][4][bcol]);
-				}
-			}
-		}
-	}
-#pragma unroll
-	for (int ca = 0; ca < 3; ++ca)
-#pragma unroll
-		for (int e = 0; e < 5; ++e)
-#pragma unroll
-			for (int bcol = 0; bcol < 5; ++bcol) kk[ca][e][bcol] *= h2;
-}
-
-constexpr int kCoefThreads = 512;
-__global__ __launch_bounds__(kCoefThreads) void tp_linpsf_coef_kernel(FitArgs a, const StarPlan* __restrict__ plans, const int32_t* __restrict__ todo,
-	double* __restrict__ store, const MPlan* __restrict__ mplans, const uint16_t* __restrict__ ulist, const uint8_t* __restrict__ usig,
-	double* __restrict__ kstore, const SegPlan* __restrict__ segs)
-{
-	extern __shared__ __align__(16) double ctab[];   // the target's coefficient table [n*n]: every patch is read ~5 times over
-	const int target = blockIdx.x, tid = threadIdx.x;
-	const int path = todo[target];
-	if (path == kPathDirect) return;
-	const int ns = (int)(a.star_offsets[target + 1] - a.star_offsets[target]);
-	if (ns > kMaxStars) return;
-	const int n = a.n;
-	const double h2 = (a.knots_x[5] - a.knots_x[4]) * (a.knots_y[5] - a.knots_y[4]);
-	{
-		// the whole table in flight at once (up to 39 doubles per thread for the largest table admitted), then into LDS: one round
-		// trip to memory instead of one per slice.  (A workgroup per CU that walks the targets with the next table on its way in
-		// registers while this one's patches are contracted: 0.85 against 0.76 ms -- 78 more registers, and the targets' work differs.)
-		const double* cg = a.coef + (int64_t)target * n * n;
-		constexpr int kPer = (140 * 140 + kCoefThreads - 1) / kCoefThreads;
-		double tmp[kPer];
-#pragma unroll
-		for (int u = 0; u < kPer; ++u) { const int i = u * kCoefThreads + tid; tmp[u] = (i < n * n) ? cg[i] : 0.0; }
-#pragma unroll
-		for (int u = 0; u < kPer; ++u) { const int i = u * kCoefThreads + tid; if (i < n * n) ctab[i] = tmp[u]; }
-	}
-	__syncthreads();
-	const double* C = ctab;
-	if (path == kPathMfma) {
-		// matrix-core layout (linpsf_mfma.hip): per (star, tile of the star) the A operands of the MFMA steps, lane = (group g,
-		// pixel u of the tile).  The coefficients are those of the tensor-product quartic spline over the na x nb knot intervals
-		// the star visits, in the basis {1, X, X^2, X^3, X^4, (X-1)+^4, (X-2)+^4} x {the same in Y}: ce[e][d] (e, d <= 4) is the
-		// biquartic of interval (0, 0); a quartic spline changes only its leading coefficient at a knot, so the coefficient of
-		// (X-a)+^4 Y^d is K(a,0)[4][d] - K(a-1,0)[4][d], of X^e (Y-b)+^4 it is K(0,b)[e][4] - K(0,b-1)[e][4], and of (X-a)+^4 (Y-b)+^4
-		// the second difference of K[4][4] -- every interval's 13 x 13 patch is contracted as for the vector-ALU path.
-		// Pixels of the tile the star never reaches get zeros.
-		const MPlan mp = mplans[target];
-		const uint16_t* ul = ulist + (int64_t)target * kMfmaPixels;
-		const uint8_t* us = usig + (int64_t)target * kMfmaPixels;
-		// One thread per (pixel of a tile, knot interval): the 13 x 13 patch of that interval is contracted into its 25
-		// coefficients; the interval (0, 0) writes the steps that hold C[e][d], e <= 4, d < 4, at once, every interval leaves its
-		// K[4][0..4] and K[0..3][4] in LDS, and one thread per pixel then forms the differences and writes the remaining steps.
-		// Jobs: one per (segment, star that is on the stamp in it).  A LANE takes one pixel of the star's tiles and one interval
-		// along y, and all na intervals along x (patch_coefficients_along_x); the nb lanes of a pixel are neighbours, so the
-		// differences across y come from the lane below by one shuffle and those across x are the lane's own -- nothing goes
-		// through LDS, and after the table is staged no wavefront waits for another: each takes every (waves)-th unit of 64 / nb
-		// pixels of the job list.  (One thread per (pixel, interval) with the differences formed through LDS between two barriers
-		// per round of 512 threads, a round per star and segment: 1.09 ms per 10 000 targets, 4.4 ms on the drift scene.)
-		struct Job { int na, nb, nt, axmin, bymin, s; unsigned tiles; long long dst; };
-		__shared__ Job s_job[kMfmaSegs * kMfmaStars];
-		__shared__ int s_njobs;
-		if (tid == 0) {
-			int nj = 0;
-			for (int sgi = 0; sgi < mp.n_seg; ++sgi) {
-				const SegPlan sg = segs[(int64_t)target * kMfmaSegs + sgi];
-				for (int s = 0; s < ns; ++s) {
-					if (sg.na[s] == 0) continue;
-					Job j;
-					j.na = sg.na[s]; j.nb = sg.nb[s]; j.nt = __popc(mp.tiles[s]); j.axmin = sg.axmin[s]; j.bymin = sg.bymin[s]; j.s = s;
-					j.tiles = mp.tiles[s]; j.dst = sg.koff + (long long)sg.ksub[s] * 64;
-					s_job[nj++] = j;
-				}
-			}
-			s_njobs = nj;
-		}
-		__syncthreads();
-		const int njobs = s_njobs;
-		const int lane = tid & 63, wave = tid >> 6, nwaves = (int)blockDim.x >> 6;
-		int unit = 0;                              // units of the job list passed so far (uniform)
-		for (int jb = 0; jb < njobs; ++jb) {
-			const Job jq = s_job[jb];
-			const int na = jq.na, nb = jq.nb, nk = mfma_steps(na, nb);
-			const int per = 64 / nb, nitems = jq.nt * 16;
-			const int nunits = (nitems + per - 1) / per;
-			for (int c = 0; c < nunits; ++c, ++unit) {
-				if (unit % nwaves != wave) continue;
-				const int li = lane / nb, cb = lane - li * nb;
-				const int item = c * per + li;
-				const bool mine = li < per && item < nitems;
-				double kk[3][5][5];
-				int r = 0, u = 0;
-				bool reach = false;
-				int ax = 0, by = 0;
-				if (mine) {
-					r = item >> 4; u = item & 15;
-					unsigned m = jq.tiles;
-					for (int q = 0; q < r; ++q) m &= m - 1;          // drop the r lowest set bits
-					const int slot = (__ffs(m) - 1) * 16 + u;
-					const unsigned pix = ul[slot];
-					if (pix != 0xffffu && ((us[slot] >> jq.s) & 1)) {
-						const int i = (int)pix / a.width, j = (int)pix - i * a.width;
-						ax = jq.axmin + 9 * j; by = (jq.bymin + cb) + 9 * i;
-						by = by < 0 ? 0 : (by > n - 13 ? n - 13 : by);
-						reach = true;
-					}
-				}
-				if (reach && ax >= 0 && ax + na - 1 <= n - 13) {
-					patch_coefficients_along_x(C, n, ax, by, h2, na, kk);
-				} else {
-#pragma unroll
-					for (int ca = 0; ca < 3; ++ca) {
-						if (reach && ca < na) {                  // an interval beyond the table's edge: clamped one by one
-							int axc = ax + ca;
-							axc = axc < 0 ? 0 : (axc > n - 13 ? n - 13 : axc);
-							patch_coefficients(C, n, axc, by, h2, kk[ca]);
-						} else {
-#pragma unroll
-							for (int e = 0; e < 5; ++e)
-#pragma unroll
-								for (int d = 0; d < 5; ++d) kk[ca][e][d] = 0.0;
-						}
-					}
-				}
-				// what the lane below (same pixel, interval cb - 1) holds of K[0][0..3][4] and K[ca][4][4]; zero below interval 0
-				double lo_e4[4], lo_44[3];
-#pragma unroll
-				for (int e = 0; e < 4; ++e) { const double v = __shfl_up(kk[0][e][4], 1, 64); lo_e4[e] = (cb > 0) ? v : 0.0; }
-#pragma unroll
-				for (int ca = 0; ca < 3; ++ca) { const double v = __shfl_up(kk[ca][4][4], 1, 64); lo_44[ca] = (cb > 0) ? v : 0.0; }
-				if (!mine) continue;
-				double* dst = kstore + jq.dst + (int64_t)r * nk * 64 + u;
-				// ce[4 + a][d] (d < 4), ce[e][4 + b] (e < 4), ce[4 + a][4 + b]: first differences along the axis that leaves interval 0,
-				// the second difference of K[4][4] off both axes (operations and their order as in the LDS version)
-				auto corner = [&](int ca) -> double {
-					const double here = kk[ca][4][4], left = (ca > 0) ? kk[ca > 0 ? ca - 1 : 0][4][4] : 0.0;
-					const double below = lo_44[ca], diag = (ca > 0) ? lo_44[ca > 0 ? ca - 1 : 0] : 0.0;
-					return ((here - left) - below) + diag;
-				};
-				if (cb == 0) {
-#pragma unroll
-					for (int e = 0; e < 5; ++e)
-#pragma unroll
-						for (int g = 0; g < 4; ++g) dst[e * 64 + g * 16] = kk[0][e][g];
-				}
-				if (mfma_is22(na, nb)) {
-					// 9 steps: y basis 4 with x basis 0..3; {x basis 4, 5 with y basis 4, x basis 0, 1 with y basis 5}; x basis 5 with y
-					// basis 0..3; x basis 2..5 with y basis 5
-					if (cb == 0) {
-#pragma unroll
-						for (int g = 0; g < 4; ++g) {
-							dst[5 * 64 + g * 16] = kk[0][g][4] - 0.0;
-							dst[7 * 64 + g * 16] = kk[1][4][g] - kk[0][4][g];
-						}
-						dst[6 * 64 + 0 * 16] = corner(0);
-						dst[6 * 64 + 1 * 16] = corner(1);
-					} else {
-						dst[6 * 64 + 2 * 16] = kk[0][0][4] - lo_e4[0];
-						dst[6 * 64 + 3 * 16] = kk[0][1][4] - lo_e4[1];
-						dst[8 * 64 + 0 * 16] = kk[0][2][4] - lo_e4[2];
-						dst[8 * 64 + 1 * 16] = kk[0][3][4] - lo_e4[3];
-						dst[8 * 64 + 2 * 16] = corner(0);
-						dst[8 * 64 + 3 * 16] = corner(1);
-					}
-				} else {
-					// steps: 5, 6 for y interval 0; 7 .. for the x basis functions 5, 6; then two per further y interval
-					const int ystep = 5 + 2 * cb + ((cb >= 1) ? (na - 1) : 0);
-#pragma unroll
-					for (int g = 0; g < 4; ++g) {
-						dst[ystep * 64 + g * 16] = kk[0][g][4] - lo_e4[g];
-						double cv = 0.0;
-						if (g == 0) cv = corner(0);
-						else if (g == 1 && na > 1) cv = corner(1);
-						else if (g == 2 && na > 2) cv = corner(2);
-						dst[(ystep + 1) * 64 + g * 16] = cv;
-					}
-					if (cb == 0) {
-#pragma unroll
-						for (int ca = 1; ca < 3; ++ca) {
-							if (ca < na) {
-#pragma unroll
-								for (int g = 0; g < 4; ++g) dst[(6 + ca) * 64 + g * 16] = kk[ca][4][g] - kk[ca - 1][4][g];
-							}
-						}
-					}
-				}
-			}
-		}
-		return;
-	}
-	for (int s = 0; s < ns; ++s) {
-		const StarPlan p = plans[(int64_t)target * kMaxStars + s];
-		const int ncols = p.jmax - p.jmin + 1, nrows = p.imax - p.imin + 1;
-		if (p.nc <= 0 || ncols <= 0 || nrows <= 0) continue;
-		const int nitems = p.nc * ncols * nrows;
-		// one thread per item: the 13 x 13 patch of the table is read once and contracted into all 25 coefficients (the sums
-		// run over q inside, over p outside)
-		for (int item = tid; item < nitems; item += kCoefThreads) {
-			const int pix = item / p.nc, co = item - pix * p.nc;
-			const int ii = pix / ncols, jj = pix - ii * ncols;
-			const int cx = co / p.nby, cy = co - cx * p.nby;
-			int ax = (p.axmin + cx) + 9 * (p.jmin + jj), by = (p.bymin + cy) + 9 * (p.imin + ii);
-			ax = ax < 0 ? 0 : (ax > n - 13 ? n - 13 : ax);
-			by = by < 0 ? 0 : (by > n - 13 ? n - 13 : by);
-			double kk[5][5];
-			patch_coefficients(C, n, ax, by, h2, kk);
-			double* dst = store + (p.item_off + item) * 25;
-#pragma unroll
-			for (int e = 0; e < 5; ++e)
-#pragma unroll
-				for (int bcol = 0; bcol < 5; ++bcol) dst[e * 5 + bcol] = kk[e][bcol];
-		}
-	}
 }
 
 template <int S, int SLO>
@@ -1497,39 +820,6 @@ namespace {
 
 #define TP_TRY(call) do { const int _rc = (call); if (_rc != TP_OK) return _rc; } while (0)
 
-inline size_t align256(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
-
-// What the plan kernel leaves for the kernels after it: the head of the context's scratch, every array on a 256-byte boundary.
-// The many-star kernels' list and scratch lie behind it (`bytes` from the start).  The scratch may MOVE when it grows, and d_todo
-// and d_total live in this head: so it is grown a second time only where nothing in flight or still to come reads the head -- for
-// the any-grid kernels after the totals' synchronise, for the targets of more than 8 stars after a synchronise of their own.
-struct PlanScratch {
-	int32_t* todo; StarPlan* plans; unsigned long long* total; int32_t* order; MPlan* mplans; uint16_t* ulist; uint8_t* usig;
-	int32_t* lists; SegPlan* segs; int32_t* seglists; double* alast;
-	size_t todo_bytes, bytes;
-};
-constexpr size_t kTotalWords = 32;
-static_assert(kTotCount <= kTotalWords, "the counters fit their block");
-
-// the arrays of the head from the address `base` on (0: only their sizes are wanted)
-void carve_plan_scratch(uintptr_t base, size_t n_targets, size_t n_cad, bool with_alast, PlanScratch& h)
-{
-	size_t off = 0;
-	auto take = [&](auto*& p, size_t count) { p = reinterpret_cast<std::remove_reference_t<decltype(p)>>(base + off); off += align256(count * sizeof(*p)); };
-	take(h.todo, n_targets); h.todo_bytes = off;
-	take(h.plans, n_targets * kMaxStars);
-	take(h.total, kTotalWords);
-	take(h.order, n_targets * n_cad);
-	take(h.mplans, n_targets);
-	take(h.ulist, n_targets * kMfmaPixels);
-	take(h.usig, n_targets * kMfmaPixels);
-	take(h.lists, n_targets * kMfmaClasses);
-	take(h.segs, n_targets * kMfmaSegs);
-	take(h.seglists, n_targets * kMfmaSegs * kMfmaClasses);
-	take(h.alast, with_alast ? n_targets * kMfmaStars * kMfmaPixels : 0);
-	h.bytes = off;
-}
-
 // dynamic LDS: the knot vectors; the coefficient table before them; red[256] behind them (finalise kernels)
 inline size_t knots_lds(const FitArgs& a) { return ((size_t)(a.n + 4) + (size_t)(a.ny + 4)) * sizeof(double); }
 inline size_t table_lds(const FitArgs& a) { return (size_t)a.n * a.ny * sizeof(double) + knots_lds(a); }
@@ -1629,41 +919,6 @@ int fit_many_star_targets(tp_ctx* ctx, const FitArgs& a, const FinArgs& fa, int 
 	TP_LAUNCH(ctx, TPK_LINPSF_FIN, (tp_linpsf_finalize_kernel<S, SLO>), dim3((unsigned)n_targets), dim3(kFinThreads), fin_lds(a), fa); \
 	TP_LAUNCH_CHECK(ctx, "tp_linpsf_finalize_kernel"); } while (0)
 
-// Polynomial path: plan (boxes, item counts, the order of the cadences, the matrix-core lists) and the totals the host needs to
-// size the store and the launches.  `use_mfma`: the matrix-core fit is on and can take this batch.
-int run_plan(tp_ctx* ctx, const FitArgs& a, int n_targets, const PlanScratch& h, int use_mfma, unsigned long long (&totals)[kTotCount])
-{
-	const int max_origins = 36;   // a star that visits more table origins sends its target to the direct kernel
-	// cadences sorted by origin in LDS (8 bytes per slot, next power of two); beyond 8192 cadences the order stays natural
-	int sort_n = 64;
-	while (sort_n < a.n_cad) sort_n <<= 1;
-	if (sort_n > 8192) sort_n = 0;
-	TP_HIP(ctx, hipMemsetAsync(h.todo, 0, h.todo_bytes, ctx->stream));
-	TP_HIP(ctx, hipMemsetAsync(h.total, 0, kTotalWords * sizeof(unsigned long long), ctx->stream));
-	// The uniform-grid kernels (all but the any-grid ones) need the SPOC layout of the PRF grid: 9 samples per pixel, the table
-	// resident in LDS, the cut-off inside the evenly spaced part of the knots.  Whether that holds is decided where the knots are.
-	// (a table with axes of different lengths is never the SPOC layout: the general kernels, the only ones that read a.ny)
-	const int force = (a.n != a.ny || a.n < 32 || a.n > 140 || !(a.cutoff <= 5.25)) ? 1 : 0;
-	hipLaunchKernelGGL(tp_linpsf_grid_kernel, dim3(1), dim3(64), 0, ctx->stream, a.knots_x, a.knots_y, a.n, a.cutoff, force, h.total);
-	TP_LAUNCH_CHECK(ctx, "tp_linpsf_grid_kernel");
-	if (sort_n > 4096) TP_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(tp_linpsf_plan_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sort_n * sizeof(unsigned long long))));
-	TP_LAUNCH(ctx, TPK_LINPSF_PLAN, tp_linpsf_plan_kernel, dim3((unsigned)n_targets), dim3(256), (size_t)sort_n * sizeof(unsigned long long), a, h.plans, h.todo, h.total, max_origins, h.order, sort_n,
-		h.mplans, h.ulist, h.usig, use_mfma, h.lists, n_targets, h.segs, h.seglists);
-	TP_LAUNCH_CHECK(ctx, "tp_linpsf_plan_kernel");
-	// one round trip in the middle of the call (measured: the plan kernel's 0.2 ms and the launch of the coefficient kernel hide
-	// it -- the step's wall time equals the sum of its kernels to 0.05 ms)
-	TP_HIP(ctx, hipMemcpyAsync(totals, h.total, sizeof(totals), hipMemcpyDeviceToHost, ctx->stream));
-	TP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	int64_t* c = ctx->linpsf_counts;   // tp_linpsf_last_counts
-	for (int i = 0; i < 16; ++i) c[i] = 0;
-	for (int k = 0; k < kMfmaClasses; ++k) {
-		c[0] += (int64_t)totals[kTotClass0 + k]; c[1] += (int64_t)totals[kTotSeg0 + k];
-		c[5 + k] = (int64_t)totals[kTotClass0 + k]; c[9 + k] = (int64_t)totals[kTotSeg0 + k];
-	}
-	c[2] = (int64_t)totals[kTotPolyTargets]; c[3] = (int64_t)totals[kTotDirectTargets];
-	return TP_OK;
-}
-
 int linpsf_fit_impl(tp_ctx* ctx, const FitArgs& a, FinArgs fa, int n_targets, int max_stars)
 {
 	PlanScratch h;
@@ -1690,11 +945,7 @@ int linpsf_fit_impl(tp_ctx* ctx, const FitArgs& a, FinArgs fa, int n_targets, in
 	}
 	double* d_store = static_cast<double*>(ctx->store);
 	double* d_kstore = d_store + poly_doubles;
-	const size_t coef_lds = (size_t)a.n * a.n * sizeof(double);
-	TP_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(tp_linpsf_coef_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)coef_lds));
-	TP_LAUNCH(ctx, TPK_LINPSF_COEF, tp_linpsf_coef_kernel, dim3((unsigned)n_targets), dim3(kCoefThreads), coef_lds, a, (const StarPlan*)h.plans, (const int32_t*)h.todo, d_store,
-		(const MPlan*)h.mplans, (const uint16_t*)h.ulist, (const uint8_t*)h.usig, d_kstore, (const SegPlan*)h.segs);
-	TP_LAUNCH_CHECK(ctx, "tp_linpsf_coef_kernel");
+	TP_TRY(launch_coefficients(ctx, a, n_targets, h, d_store, d_kstore));
 	// the matrix-core fit of the targets marked for it (up to 4 stars, up to 256 reachable pixels)
 	if (use_mfma) {
 		TP_TRY(fit_mfma_launch(ctx, a, n_targets, totals + kTotSeg0, h.segs, h.seglists, h.mplans, h.ulist, h.usig, d_kstore, h.alast));

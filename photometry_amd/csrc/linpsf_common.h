@@ -1,17 +1,15 @@
-// linpsf_common.h -- definitions shared by the LinPSF translation units (linpsf.hip: plan / coefficient store / vector-ALU
-// fit kernels and the C entry; linpsf_mfma.hip: the matrix-core fit kernel).
+// linpsf_common.h -- definitions shared by the LinPSF translation units (linpsf_plan.hip: plan / coefficient store; linpsf.hip:
+// vector-ALU fit kernels, finalisers and the C entry; linpsf_mfma.hip: the matrix-core fit kernel; linpsf_err.hip: the flux errors).
+// The plan's records, constants and rules are those of linpsf_plan_rules.h.
 #pragma once
 #include "common.h"
 #include "linpsf_dev.h"
+#include "linpsf_plan_rules.h"
 #include <cmath>
 
 namespace tp_linpsf {
 
 using namespace tp_prf;
-
-constexpr int kMaxStars = 8;      // register-resident vector-ALU kernels (fit2 / direct)
-constexpr int kMfmaStars = 4;     // matrix-core kernel (linpsf_mfma.hip)
-constexpr int kMfmaPixels = 256;  // pixels of a target's union list U (16 tiles of 16)
 
 //--------------------------------------------------------------------------------------------------
 // P2..P4
@@ -202,54 +200,27 @@ __device__ __forceinline__ bool chol_solve(const double (&G)[S][S], const double
 	return true;
 }
 
-// plan of one fitted star: the table origins its cadences visit and the pixels its cut-off circle can reach
-struct StarPlan { int axmin, bymin, nby, nc, jmin, jmax, imin, imax; long long item_off; };
 
-// matrix-core path, per target: the pixels inside the cut-off of ANY fitted star at ANY cadence form the list U (ordered by
-// which stars reach them -- Gray-code order of the membership bits, then raster -- so that the pixels of one star are
-// contiguous), cut into tiles of 16; star s touches the tiles of `tiles[s]`.
-struct MPlan {
-	int32_t n_pix, n_tiles;
-	uint32_t tiles[kMfmaStars];
-	uint32_t edge_tiles[kMfmaStars];   // tiles with a pixel that is inside the star's cut-off at some cadences only
-	int32_t n_seg;                     // segments of the series (records target * kMfmaSegs .. + n_seg of the segment array)
-};
-// The series of a target is cut into SEGMENTS of consecutive 16-cadence tiles inside which every fitted star visits at most
-// kMfmaSpan knot intervals per axis: a star that drifts across the pixel during the series (pointing drift, velocity aberration:
-// half a pixel is 4.5 knot intervals) stays on the matrix cores, each stretch of the series with the spline of the intervals it
-// visits THEN.  Without drift the jitter gives one segment.
-// Per (target, segment): the coefficients of ONE tensor-product quartic spline per star over its na x nb intervals
-// (linpsf_mfma.hip), laid out as the A operands of the matrix instruction: [star][rank of the tile among its tiles][step][64
-// lanes] doubles, the whole segment contiguous from `koff` (that image is copied to LDS as it is), star s from
-// `koff + 64 * ksub[s]`, `mfma_steps(na, nb)` steps per tile.  One workgroup of the fit kernel per segment.
-struct SegPlan {
-	int32_t target;
-	int32_t tile0, tile1;              // 16-cadence tiles [tile0, tile1) of the series
-	int32_t kdoubles;                  // size of the segment's image (a multiple of 64)
-	int64_t koff;                      // doubles from the start of the matrix-core store
-	int32_t axmin[kMfmaStars], bymin[kMfmaStars];   // first knot interval the star visits in this segment, per axis
-	uint16_t ksub[kMfmaStars];         // in blocks of 64 doubles
-	uint8_t na[kMfmaStars], nb[kMfmaStars];   // knot intervals visited along x / y (1..3; 0: the star is never on the stamp)
-};
-constexpr int kMfmaSpan = 3;          // knot intervals per axis a star may visit inside a segment
-constexpr int kMfmaSegs = 8;          // segments per target (more: the vector-ALU kernels take the target)
-constexpr int kMfmaCadTiles = 256;    // 16-cadence tiles of a series the plan kernel can cut into segments (4096 cadences: a sector at 600 s)
-// steps of v_mfma_f64_16x16x4_f64 per (star, pixel tile): (4 + na) basis functions of x times the first four of y, then two steps
-// for each of the nb remaining basis functions of y -- except for the commonest case, 2 x 2 intervals (36 products), which is
-// packed into 9 steps instead of 10: the half-empty second step of y basis function 4 also carries x basis functions 0, 1 of y
-// basis function 5, and one more step the other four (mfma_is22)
-__host__ __device__ constexpr bool mfma_is22(int na, int nb) { return na == 2 && nb == 2; }
-__host__ __device__ constexpr int mfma_steps(int na, int nb) { return mfma_is22(na, nb) ? 9 : ((4 + na) + 2 * nb); }
-// LDS bytes for the coefficient image of a segment: "small" leaves room for two workgroups per CU, "large" (three and four
-// stars only: their kernels run one workgroup per CU anyway) takes the LDS of the CU
-constexpr int kMfmaLdsSmall = 75776, kMfmaLdsLarge = 157696;
-// the plan kernel lists the targets and the segments of the matrix-core path by their number of fitted stars: class = stars - 1
-constexpr int kMfmaClasses = kMfmaStars;
-// counters the plan kernel keeps (64-bit words of one 256-byte block): kTotClass0 + c targets, kTotSeg0 + c segments of class c
-enum { kTotPolyItems = 0, kTotKDoubles = 1, kTotPolyTargets = 2, kTotDirectTargets = 3, kTotGeneral = 4, kTotClass0 = 8, kTotSeg0 = 16, kTotCount = 24 };
+inline size_t align256(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
 
-// `todo` flag of a target (written by the plan kernel): which kernel fits it
-enum { kPathPoly = 0, kPathDirect = 1, kPathMfma = 2 };
+// What the plan kernel leaves for the kernels after it: the head of the context's scratch, every array on a 256-byte boundary.
+// The many-star kernels' list and scratch lie behind it (`bytes` from the start).  The scratch may MOVE when it grows, and d_todo
+// and d_total live in this head: so it is grown a second time only where nothing in flight or still to come reads the head -- for
+// the any-grid kernels after the totals' synchronise, for the targets of more than 8 stars after a synchronise of their own.
+struct PlanScratch {
+	int32_t* todo; StarPlan* plans; unsigned long long* total; int32_t* order; MPlan* mplans; uint16_t* ulist; uint8_t* usig;
+	int32_t* lists; SegPlan* segs; int32_t* seglists; double* alast;
+	size_t todo_bytes, bytes;
+};
+
+// linpsf_plan.hip
+// the arrays of the head from the address `base` on (0: only their sizes are wanted)
+void carve_plan_scratch(uintptr_t base, size_t n_targets, size_t n_cad, bool with_alast, PlanScratch& h);
+// Polynomial path: plan (boxes, item counts, the order of the cadences, the matrix-core lists) and the totals the host needs to
+// size the store and the launches.  `use_mfma`: the matrix-core fit is on and can take this batch.
+int run_plan(tp_ctx* ctx, const FitArgs& a, int n_targets, const PlanScratch& h, int use_mfma, unsigned long long (&totals)[kTotCount]);
+// the coefficients of what the plan counted: polynomial items into d_store, the matrix-core images into d_kstore
+int launch_coefficients(tp_ctx* ctx, const FitArgs& a, int n_targets, const PlanScratch& h, double* d_store, double* d_kstore);
 
 // linpsf_mfma.hip
 int fit_mfma_launch(tp_ctx* ctx, const FitArgs& a, int n_targets, const unsigned long long* seg_counts, const SegPlan* d_segs,

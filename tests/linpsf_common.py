@@ -7,7 +7,8 @@ The fit kernels (``photometry_amd/csrc/linpsf.hip``, ``linpsf_mfma.hip``) decide
 the number of fitted stars, the knot intervals of the PRF grid the stars visit, the pixels inside their cut-off circles, the
 length of the series.  The scenes of ``simulate.make_scene`` leave that to chance and always put the target first in its
 catalogue.  Here a target is built BY DESIGN -- star count, the target's place in the fitted list, positions, a per-star motion
-series -- and the class it must reach is restated on the host (:func:`plan_class`, from the rules of ``tp_linpsf_plan_kernel``),
+series -- and the class it must reach is restated on the host (:func:`plan_class`, from the rules of ``tp_linpsf_plan_kernel``,
+``photometry_amd/csrc/linpsf_plan_rules.h``: ``test_linpsf_plan_host.py`` holds the two to each other without a GPU),
 so that every row of :data:`CASES` names its class, the counters of ``tp_linpsf_last_counts`` that prove it, and the CPU test
 checks the row's design facts before the GPU ever sees it.
 
@@ -17,7 +18,7 @@ noise); the oracle (``oracle.linpsf.do_photometry``) fits them with the pixel-in
 
 import numpy as np
 
-# ---- constants of the kernels, restated (photometry_amd/csrc/linpsf_common.h, linpsf.hip) ----
+# ---- constants of the kernels, restated (photometry_amd/csrc/linpsf_plan_rules.h, linpsf.hip; test_linpsf_plan_host.py compares) ----
 MAX_STARS = 8            # kMaxStars: register-resident vector-ALU kernels
 MFMA_STARS = 4           # kMfmaStars
 MFMA_PIXELS = 256        # kMfmaPixels
@@ -25,7 +26,7 @@ MFMA_SPAN = 3            # kMfmaSpan
 MFMA_SEGS = 8            # kMfmaSegs
 MFMA_CAD_TILES = 256     # kMfmaCadTiles (4096 cadences)
 MFMA_LDS_SMALL, MFMA_LDS_LARGE = 75776, 157696
-MAX_ORIGINS = 36         # linpsf_fit_impl: more table origins per star -> the general direct kernel
+MAX_ORIGINS = 36         # kMaxOrigins: more table origins per star -> the general direct kernel
 MAX_MANY_STARS = 64
 CUTOFF = 5.0
 
@@ -144,11 +145,12 @@ def _gray_rank4(g):
 	return g & 15
 
 
-def union_plan(pos_rows, pos_cols, H, W, cutoff=CUTOFF):
+def union_plan(pos_rows, pos_cols, H, W, cutoff=CUTOFF, with_keys=False):
 	"""
 	The union list of the matrix-core path: the pixels nearer than the cut-off to the rectangle a star's position sweeps, for any
 	star on the stamp; ordered as the plan kernel orders them; cut into tiles of 16.  Returns ``(n_pix, tiles)`` with ``tiles[s]``
-	the number of tiles star ``s`` touches (``None`` beyond ``MFMA_PIXELS`` pixels: no list is made).
+	the number of tiles star ``s`` touches (``None`` beyond ``MFMA_PIXELS`` pixels: no list is made); ``with_keys``: and the keys
+	the list is ordered by, in raster order of their pixels (``pixel_key`` of linpsf_plan_rules.h).
 	"""
 	S = pos_rows.shape[0]
 	reach, always = (cutoff + 1e-6)**2, (cutoff - 1e-6)**2
@@ -171,12 +173,12 @@ def union_plan(pos_rows, pos_cols, H, W, cutoff=CUTOFF):
 	p = np.flatnonzero(sig.ravel())
 	n_pix = len(p)
 	if n_pix > MFMA_PIXELS:
-		return n_pix, None
+		return (n_pix, None, None) if with_keys else (n_pix, None)
 	sg, ed = sig.ravel()[p], edge.ravel()[p]
 	keys = (_gray_rank4(sg.copy()) << 25) | ((ed != 0).astype('int64') << 24) | (ed << 20) | (sg << 16) | p
 	rank = np.argsort(np.argsort(keys))
 	tiles = [len(set((rank[(sg >> s) & 1 == 1] >> 4).tolist())) for s in range(S)]
-	return n_pix, tiles
+	return (n_pix, tiles, keys) if with_keys else (n_pix, tiles)
 
 
 def mfma_steps(na, nb):
