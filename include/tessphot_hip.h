@@ -795,7 +795,7 @@ int tp_motion_star_positions(tp_ctx* ctx, int32_t warpmode, int32_t n_series, co
 	int32_t single, const float* d_base_col, const float* d_base_row, const int64_t* d_out_index, int64_t n_out, double* d_pos_col,
 	double* d_pos_row, int64_t pos_pitch, double* d_jitter);
 
-/* ---- Halo photometry (photometry/halo/halo_photometry.py) -------------------------------------------------------------
+/* ---- Halo photometry (photometry/halo/halo_photometry.py; csrc/halo.hip, its rules in csrc/halo_rules.h) --------------------
  * The TV-min pixel weights that halo_photometry.py:179-196 obtains from halophot's do_lc (settings of :86-97: objective 'tv',
  * sub 1, thresh -1, no sigma clipping, uniform start), defined in DESIGN.md ("Halo") and tests/halo_common.py.  One problem is
  * one light-curve segment of one target (the split times of :125-159).
@@ -820,7 +820,7 @@ int tp_halo_tvmin(tp_ctx* ctx, int32_t n_problems, const int64_t* h_p_offset, co
 int tp_halo_objective(tp_ctx* ctx, int32_t n_problems, const int64_t* h_p_offset, const int32_t* h_npix, const int32_t* h_ncad,
 	const float* d_P, const uint8_t* d_fit, const double* d_theta, double* d_f, double* d_grad);
 
-/* ---- Halo photometry of a batch of targets straight from a region's frame stack (the batched entry) --------------------------
+/* ---- Halo photometry of a batch of targets straight from a region's frame stack (the batched entry; csrc/halo_stack.hip) ----
  * The problems of halo_photometry.py:160-196 (one per segment of every target; the definition is tests/halo_common.py::problems)
  * are built on the device from the image-major stack d_images float32 [n_frames][frame_rows][frame_cols] (contiguous) that covers
  * the CCD rows / columns from row0 / col0.  h_stamps: HOST int32 [n_targets][4] (row1, row2, col1, col2 in CCD coordinates), all

@@ -1,6 +1,6 @@
 # -*- coding: utf-8 -*-
 """
-Halo photometry in the batched frames entry (csrc/halo.hip: select / gather / outputs on the device; ``halo.photometry_frames``,
+Halo photometry in the batched frames entry (csrc/halo_stack.hip: select / gather / outputs on the device; ``halo.photometry_frames``,
 ``pipeline.halo_frames``, the switch of ``tessphot_frames``) against the restatement (tests/halo_common.py), against the
 per-target plugin path on host cubes cut from the same frames, and against ``tessphot(None, ...)``.
 """
@@ -403,3 +403,44 @@ def test_tessphot_frames_switches_like_tessphot(ctx, region_run, monkeypatch, tm
 			if b.method == 'halo':
 				for x, y in zip(a.halo_weightmap['weightmap'], b.halo_weightmap['weightmap']):
 					assert _same_bits(x, y)
+
+
+@pytest.mark.parametrize('T', (64, 256, 65, 257))
+def test_norm_median_on_heavy_ties(ctx, monkeypatch, T):
+	"""The norm kernel's selection (the block selection shared with the solver's stat kernel, 256 threads) on a light curve of a few
+	values with many copies each: frames periodic in time (period 4 for an even count of fitted cadences -- the two middle ranks fall
+	on different values -- and 5 for an odd one), one 6 x 6 stamp with the full mask inside a 12 x 12 stack, one segment, cadences
+	8 .. 11 not fitted.  ``halo.photometry`` takes numpy's median of the same ``l``: corr_flux and the weight map must equal it bit
+	for bit."""
+	from photometry_amd import halo
+	from photometry_amd.plugins import mag2flux
+	rng = np.random.default_rng(T)
+	period = 4 if T % 2 == 0 else 5
+	R = C = 12
+	base = rng.uniform(50, 1000, (R, C, period)).astype('float32')
+	frames = {'images': np.ascontiguousarray(base[:, :, np.arange(T) % period]), 'images_err': rng.uniform(1, 2, (R, C, T)).astype('float32'),
+		'backgrounds': np.zeros((R, C, T), dtype='float32')}
+	row0, col0 = 100, 200
+	stamp = np.array([[row0 + 3, row0 + 9, col0 + 2, col0 + 8]], dtype='int64')
+	mask = np.ones((6, 6), dtype=bool)
+	time = 1500.0 + np.arange(T) * 1800.0 / 86400.0
+	quality = np.zeros(T, dtype='int32')
+	quality[8:12] = 32
+	targets = {'starid': np.array([1], dtype='int64'), 'tmag': np.array([5.0]), 'row': np.array([row0 + 6.0]), 'column': np.array([col0 + 5.0])}
+	stack = _stack(ctx, frames, row0, col0)
+	monkeypatch.setattr(halo, 'frames_stamps', lambda limits, tg: (stamp, np.ones(1, dtype=bool)))
+	monkeypatch.setattr(halo, 'frames_pixel_masks', lambda *a, **k: mask[None])
+	got = halo.photometry_frames(ctx, stack, targets, time, quality)
+	assert got['segments'].max() == 0 and got['usable'][0] and got['npix'][0, 0] == 36 and got['ncad'][0, 0] == T
+	assert got['status'][0, 0] != halo.DEGENERATE
+	cube, cube_err = _cut(frames, 'images', stamp[0], row0, col0), _cut(frames, 'images_err', stamp[0], row0, col0)
+	# the device's fitted l: as many distinct values as the period, with T / period copies each
+	prob = halo.build_problems(cube, quality, mask, got['segments'])
+	dev = halo.tvmin(ctx, prob)
+	fitted = dev['l'][0][prob[0].fit]
+	assert len(fitted) == T - 4 and len(np.unique(fitted)) <= 6
+	assert _same_bits(got['w'][0][0], dev['w'][0]) and got['iterations'][0, 0] == dev['iterations'][0]
+	ref = halo.photometry(ctx, cube, cube_err, quality, time, np.zeros(T), np.arange(T), mask, -1, mag2flux(5.0))
+	assert ref['status'][0] == got['status'][0, 0]
+	assert _same_bits(got['corr_flux'][0], ref['corr_flux'])
+	assert _same_bits(got['weightmap'][0][0], ref['weightmap']['weightmap'][0])

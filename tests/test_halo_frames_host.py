@@ -1,81 +1,14 @@
 # -*- coding: utf-8 -*-
 """
-The batched Halo path without a GPU: the counting rule the select kernel uses for ``nanmedian < minflux`` against numpy, the
-column predicate of the method switch against ``halo_switch_reason``, and the test region of tests/test_gpu_halo_frames.py held to
-its conditions on the oracle alone.
+The batched Halo path without a GPU: the column predicate of the method switch against ``halo_switch_reason``, and the test region
+of tests/test_gpu_halo_frames.py held to its conditions on the oracle alone.  (The counting rule the select kernel uses for
+``nanmedian < minflux``, ``drop_pixel`` of csrc/halo_rules.h, is held to numpy in tests/test_halo_rules_host.py, which runs the C++.)
 """
 import configparser
 import numpy as np
 import pytest
 import halo_common as hc
 import halo_frames_common as fc
-
-MINFLUX = -100.0
-
-
-def counting_rule(x, minflux=MINFLUX):
-	"""``nanmedian(float64(x)) < minflux`` as csrc/halo.hip (drop_pixel) decides it: from the count ``n`` of non-NaN values, the
-	count ``c`` of values below ``minflux``, ``a = max{x < minflux}`` and ``b = min{x >= minflux}``, without a sort."""
-	x = np.asarray(x, dtype='float32')
-	x = x[~np.isnan(x)]
-	n = len(x)
-	below = x.astype('float64') < minflux
-	c = int(np.count_nonzero(below))
-	if n == 0:
-		return False
-	if n % 2:
-		return c >= (n + 1) // 2
-	if c >= n // 2 + 1:
-		return True
-	if c < n // 2:
-		return False
-	a, b = np.max(x[below]), np.min(x[~below])
-	with np.errstate(invalid='ignore'):
-		return bool((np.float64(a) + np.float64(b)) / 2.0 < minflux)
-
-
-def numpy_rule(x, minflux=MINFLUX):
-	import warnings
-	x = np.asarray(x, dtype='float32')
-	with warnings.catch_warnings():
-		warnings.simplefilter('ignore', RuntimeWarning)
-		with np.errstate(invalid='ignore'):
-			med = np.nanmedian(x.astype('float64')) if len(x) else np.nan
-	return bool(med < minflux)
-
-
-def _hand_cases():
-	below, above = np.nextafter(np.float32(MINFLUX), np.float32(-np.inf)), np.nextafter(np.float32(MINFLUX), np.float32(np.inf))
-	cases = [[], [np.nan], [np.nan] * 4, [MINFLUX], [MINFLUX] * 2, [MINFLUX] * 5, [below], [above], [-150, MINFLUX], [-150, -50], [-150, -50.5],
-		[-120, -80], [-120, -79.99], [-120.01, -80], [below, MINFLUX], [below, above], [-200, -150, -50, 10], [-200, -150, -100, 10],
-		[-200, -100.5, -99.5, 10], [-200, -100.5, -99.25, 10], [-200, -100.75, -99.5, 10], [np.inf], [-np.inf], [np.inf, -np.inf],
-		[-np.inf, -np.inf, np.inf, np.inf], [-np.inf, -150, np.inf], [-np.inf, np.nan, np.inf], [-150, np.nan, -50, np.nan, MINFLUX],
-		[np.inf, np.inf, -150], [-np.inf, -150, -50, np.inf]]
-	for n in list(range(1, 10)) + [1299, 1300]:
-		for c in {0, n // 2 - 1, n // 2, n // 2 + 1, (n + 1) // 2, n} & set(range(n + 1)):
-			cases.append([-150.0] * c + [-50.0] * (n - c))
-			cases.append([-100.5] * c + [MINFLUX] * (n - c))
-	return cases
-
-
-def test_counting_rule_equals_numpy_on_the_hand_cases():
-	for x in _hand_cases():
-		assert counting_rule(x) == numpy_rule(x), x
-
-
-def test_counting_rule_equals_numpy_on_random_series():
-	rng = np.random.default_rng(11)
-	lengths = list(range(1, 10)) + [599, 600, 601, 1299, 1300]
-	for k in range(10000):
-		n = lengths[k % len(lengths)] if k % 4 else int(rng.integers(1, 40))
-		x = (MINFLUX + rng.normal(size=n) * rng.choice([0.01, 1.0, 50.0])).astype('float32')
-		x[rng.random(n) < 0.05] = np.float32(MINFLUX)
-		x[rng.random(n) < 0.03] = np.nan
-		if k % 7 == 0:
-			x[rng.random(n) < 0.2] = np.inf
-		if k % 11 == 0:
-			x[rng.random(n) < 0.2] = -np.inf
-		assert counting_rule(x) == numpy_rule(x), (k, x)
 
 
 # -- the switch predicate ------------------------------------------------------------------------------------------------------
