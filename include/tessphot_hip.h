@@ -571,6 +571,46 @@ int tp_psf_fit(tp_ctx* ctx, const tp_cube_desc* desc, const float* d_images, con
 	double variance_floor, double cutoff_radius, int32_t maxiter_first, int32_t maxiter,
 	double* d_flux, double* d_flux_err, double* d_centroid_row, double* d_centroid_col, int64_t out_pitch,
 	double* d_params_out, int32_t* d_nit, int32_t* d_status);
+/* tp_psf_flux_err: the uncertainty of the PSFPhotometry light-curve flux, propagated from the pixel errors.  The reference has none --
+ * psf_photometry.py:175 writes flux_err[k] = NaN ("FIXME: Add errors!"), BasePhotometry.photometry() then refuses the light curve --
+ * and tp_psf_fit keeps doing exactly that; this is a separate pass beside it, defined here.  The 'Gaussian_d'
+ * likelihood is a weighted chi-square whose weights do not depend on the model, so the Gauss-Newton normal matrix at the fit's end
+ * point is the Fisher information.  For one target and one cadence k, in float64 unless said otherwise:
+ *   theta    = the parameters of cadence k, (row_s, col_s, f_s) of the S = min(n_fitted, 5) fitted stars, star 0 the target: d_params
+ *              float64 [n_fit_stars * 3][params_pitch], the layout of tp_psf_fit's d_params_out.  A non-finite entry (the fit did not
+ *              finish) gives flux_err = NaN, as does S = 0;
+ *   img, w   = the fit's own float32 values, widened: var = |img + bkg| + (float)variance_floor, raised to 1e-9; w = 1 / var, raised to
+ *              1e-9 (psf_photometry.py:75-86); bkg = 0 when d_backgrounds is NULL;
+ *   good     = the pixels whose chi-square term the fit's nansum keeps: img and w finite;
+ *   a_s(p)   = the pixel-integrated unit PRF of star s at pixel p (psf.py:122-148), zero where sqrt((j - col_s)^2 + (i - row_s)^2)
+ *              >= cutoff_radius; the set of pixels inside the cut-off is frozen at theta;
+ *   J        = the Jacobian of the model, good x 3S: columns f_s * da_s/drow_s, f_s * da_s/dcol_s, a_s.  The position derivatives are
+ *              exact: the box integral over [e_lo, e_hi] of a spline axis has the derivative -(N(e_hi) - N(e_lo)) with respect to the
+ *              star's position, N the cubic B-spline values at an edge; a limit that fpintb clips to the knot span contributes 0;
+ *   N        = J^T diag(w) J;  d_i = sqrt(N_ii), 1 where that is 0;  N' = N / (d d^T);  Ninv = D^-1 pinv(N') D^-1 with numpy's rule
+ *              that eigenvalues <= 1e-15 * max count as zero (N itself is badly conditioned: position and flux columns differ by
+ *              the star's flux);
+ *   F        = f_0 + sum over (mini aperture and good) of (img_p - mdl_p(theta)), the light-curve flux (psf_photometry.py:162-171);
+ *              g = e_{f_0} - sum over (mini and good) of J_p;  q = Ninv g;  m_p = w_p (J_p . q) + [p in mini and good], the response
+ *              of F to pixel p;
+ *   flux_err = sqrt(sum over good pixels of (m_p * err_p)^2), err the float32 d_images_err value widened.
+ * The sum is a plain sum: a non-finite err at a good pixel makes the cadence NaN, also where m_p is 0 (a flag, not arithmetic); a
+ * cadence without a good pixel gives 0.  Two approximations are deliberate: the weights' own dependence on the image is ignored,
+ * and the linearisation is taken at the simplex's end point as it stands (often a maxiter stop), not at the exact minimiser.
+ * Conventions of tp_psf_fit: the layouts of desc (t_pitch honoured), d_backgrounds and d_images_err laid out like d_images, d_coef /
+ * d_knots_* / d_star_offsets / d_mini_aperture / variance_floor / cutoff_radius as there (+infinity = no cut-off), params_pitch and
+ * out_pitch >= n_cad, d_flux_err float64 [n_targets][out_pitch] with the values beyond n_cad left untouched.  One wavefront per
+ * (target, cadence) and one code path for every PRF grid (the FITPACK box integral and its edge derivative); the Jacobian of a
+ * cadence lives in LDS, a stamp too large for that is refused.  No atomics: two calls give the same bits, and a target alone the bits
+ * it gives inside a batch. */
+int tp_psf_flux_err_xy(tp_ctx* ctx, const tp_cube_desc* desc, const float* d_images, const float* d_backgrounds, const float* d_images_err,
+	const double* d_coef, const double* d_knots_x, const double* d_knots_y, int32_t n_coef_axis_x, int32_t n_coef_axis_y,
+	const int64_t* d_star_offsets, const double* d_params, int64_t params_pitch, const uint8_t* d_mini_aperture,
+	double variance_floor, double cutoff_radius, double* d_flux_err, int64_t out_pitch);
+int tp_psf_flux_err(tp_ctx* ctx, const tp_cube_desc* desc, const float* d_images, const float* d_backgrounds, const float* d_images_err,
+	const double* d_coef, const double* d_knots_x, const double* d_knots_y, int32_t n_coef_axis,
+	const int64_t* d_star_offsets, const double* d_params, int64_t params_pitch, const uint8_t* d_mini_aperture,
+	double variance_floor, double cutoff_radius, double* d_flux_err, int64_t out_pitch);
 
 /* ---- light-curve diagnostics ---------------------------------------------
  * replaces the diagnostics block of BasePhotometry.photometry (photometry/BasePhotometry.py:1343-1407)

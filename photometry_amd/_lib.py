@@ -145,6 +145,8 @@ SIGNATURES = {
 		_p, _p, _p, c_int64, _p, _p, _p]),
 	'tp_linpsf_flux_err': (c_int, [c_void_p, _desc_p, _p, _p, _p, _p, _p, c_int32, c_int32, _p, _p, _p, _p, c_int64, c_double, _p, c_int64]),
 	'tp_linpsf_flux_err_xy': (c_int, [c_void_p, _desc_p, _p, _p, _p, _p, _p, c_int32, c_int32, c_int32, _p, _p, _p, _p, c_int64, c_double, _p, c_int64]),
+	'tp_psf_flux_err': (c_int, [c_void_p, _desc_p, _p, _p, _p, _p, _p, _p, c_int32, _p, _p, c_int64, _p, c_double, c_double, _p, c_int64]),
+	'tp_psf_flux_err_xy': (c_int, [c_void_p, _desc_p, _p, _p, _p, _p, _p, _p, c_int32, c_int32, _p, _p, c_int64, _p, c_double, c_double, _p, c_int64]),
 	'tp_psf_fit_xy': (c_int, [c_void_p, _desc_p, _p, _p, _p, _p, _p, c_int32, c_int32, _p, _p, _p, c_double, c_double, c_int32, c_int32,
 		_p, _p, _p, _p, c_int64, _p, _p, _p]),
 	'tp_lightcurve_diagnostics': (c_int, [c_void_p, c_int32, c_int32, _p, _p, _p, _p, c_int64, _p, _p, c_int64, c_uint32,

@@ -69,6 +69,7 @@ static const char* const kKernelNames[TPK_COUNT] = {
 	"tp_motion_interp_kernel",
 	"tp_motion_positions_kernel",
 	"tp_linpsf_err_kernel",
+	"tp_psf_err_kernel",
 };
 
 extern "C" {

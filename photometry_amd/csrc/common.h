@@ -67,6 +67,7 @@ enum tp_kernel_id {
 	TPK_MOTION_INTERP,
 	TPK_MOTION_POSITIONS,
 	TPK_LINPSF_FLUX_ERR,
+	TPK_PSF_FLUX_ERR,
 	TPK_COUNT
 };
 

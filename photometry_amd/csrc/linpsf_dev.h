@@ -221,6 +221,43 @@ __device__ __forceinline__ double edge_cumulative(const EdgeInt& g, int i)   // 
 	return (q == 0) ? g.s[0] : ((q == 1) ? g.s[1] : ((q == 2) ? g.s[2] : g.s[3]));
 }
 
+// edge_integrals together with the VALUES of the cubic B-splines at the edge: v[q] = N_{l - 3 + q}(e), q = 0 .. 3 (every other one is
+// zero there).  de Boor's recurrence passes through degree 3 on its way to degree 4, so they are a by-product; out is what
+// edge_integrals gives, bit for bit (the same statements in the same order).  The derivative of the box integral of N_i over
+// [e_lo, e_hi] with respect to a shift of both limits is N_i(e_hi) - N_i(e_lo): tp_psf_flux_err's position columns (psf_err.hip).
+__device__ __forceinline__ void edge_integrals_values(const double* __restrict__ t, int n, double e, EdgeInt& out, double (&v)[4])
+{
+	int lo = 3, hi = n - 1;
+	while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (t[mid] <= e) lo = mid; else hi = mid - 1; }
+	const int l = lo;
+	double b[5] = {1.0, 0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+	for (int j = 1; j <= 4; ++j) {
+		if (j == 4) { v[0] = b[0]; v[1] = b[1]; v[2] = b[2]; v[3] = b[3]; }
+		double saved = 0.0;
+#pragma unroll
+		for (int r = 0; r < j; ++r) {
+			const double tr = t[l + r + 1], tl = t[l + r + 1 - j];
+			const double f = b[r] / (tr - tl);
+			b[r] = saved + f * (tr - e);
+			saved = f * (e - tl);
+		}
+		b[j] = saved;
+	}
+	out.l = l;
+	out.s[3] = b[4];
+	out.s[2] = b[3] + out.s[3];
+	out.s[1] = b[2] + out.s[2];
+	out.s[0] = b[1] + out.s[1];
+}
+
+__device__ __forceinline__ double edge_value(const EdgeInt& g, const double (&v)[4], int i)   // N_i(e)
+{
+	const int q = i - (g.l - 3);
+	if (q < 0 || q > 3) return 0.0;
+	return (q == 0) ? v[0] : ((q == 1) ? v[1] : ((q == 2) ? v[2] : v[3]));
+}
+
 // integral of the unit PRF spline over the pixel [xa, xb] x [ya, yb] (x: first spline axis = column direction, psf.py:146)
 // (n, ny: coefficients along the first / the second axis; the table is [n][ny], RectBivariateSpline's layout)
 __device__ inline double prf_pixel_general(const double* __restrict__ C, int n, int ny, const double* __restrict__ tx, const double* __restrict__ ty,

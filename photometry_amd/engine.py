@@ -407,3 +407,28 @@ def psf_fit(ctx, images, backgrounds, coef, knots_x, knots_y, star_offsets, para
 		out['flux'].ptr, out['flux_err'].ptr, out['centroid_row'].ptr, out['centroid_col'].ptr, T, out['params'].ptr, out['nit'].ptr,
 		out['status'].ptr))
 	return out
+
+
+def psf_flux_err(ctx, images, backgrounds, images_err, coef, knots_x, knots_y, star_offsets, params, mini_aperture, variance_floor=9.0,
+	cutoff_radius=5.0, out=None):
+	"""
+	The uncertainty of the PSFPhotometry light-curve flux, propagated from the pixel errors (``tp_psf_flux_err_xy``; the reference has
+	none, psf_photometry.py:175): per cadence ``sqrt(sum_good (m_px * err_px)^2)`` with ``m`` the response of the light-curve flux to
+	the pixels through the Gauss-Newton normal matrix of the likelihood at the fit's end point -- a separate pass beside
+	:func:`psf_fit`, which it leaves untouched.  ``images_err``: a :class:`DeviceCube` laid out like ``images``; ``backgrounds`` may be
+	``None``; ``params``: ``psf_fit(...)['params']``, float64 ``(n_fit * 3, >= T)``; the other arguments as for :func:`psf_fit`.
+	Returns a float64 ``(Nt, T)`` device array (``out``: a caller-owned one of at least ``T`` columns, written up to ``T``).
+	"""
+	n, ny = knots_x.shape[0] - 4, knots_y.shape[0] - 4
+	if cutoff_radius is None:
+		cutoff_radius = float('inf')
+	if out is None:
+		out = ctx.zeros((images.n_targets, images.n_cad), 'float64')
+	assert params.shape[1] >= images.n_cad
+	assert images_err.t_pitch == images.t_pitch and images_err.data.shape == images.data.shape
+	assert backgrounds is None or (backgrounds.t_pitch == images.t_pitch and backgrounds.data.shape == images.data.shape)
+	assert out.shape[0] >= images.n_targets and out.shape[1] >= images.n_cad
+	desc = images.desc
+	ctx._check(ctx.lib.tp_psf_flux_err_xy(ctx.handle, ctypes.byref(desc), images.ptr, _ptr(backgrounds), images_err.ptr, coef.ptr, knots_x.ptr, knots_y.ptr,
+		n, ny, star_offsets.ptr, params.ptr, params.shape[1], mini_aperture.ptr, float(variance_floor), float(cutoff_radius), out.ptr, out.shape[1]))
+	return out

@@ -1010,12 +1010,14 @@ def linpsf_frames(ctx, stack, targets, catalog, time, quality, prf_model, jitter
 	return out.finish()
 
 
-def psf_frames(ctx, stack, targets, catalog, time, quality, prf_model, readnoise=10.0, gain=100.0, n_readout=720, cutoff_radius=5):
+def psf_frames(ctx, stack, targets, catalog, time, quality, prf_model, readnoise=10.0, gain=100.0, n_readout=720, cutoff_radius=5, flux_errors=False):
 	"""
 	``PSFPhotometry.do_photometry`` (psf_photometry.py:111-196) for every target of a CCD region held in a :class:`FrameStack`:
 	default stamps grouped by size, images and backgrounds cut on the device, per target the up to five stars the plugin fits
 	(:117-130) with their catalogue positions and fluxes as the first guess, the 3 x 3 minimum aperture of the finite sum-image
 	pixels (:29-41), one ``tp_psf_fit`` per group (the cadences of a target are a warm-start chain, the targets run side by side).
+	``flux_errors``: also cut the ``images_err`` stack per stamp group and fill ``flux_err`` with the pixel errors propagated through
+	the fit at its own end points (``tp_psf_flux_err``); by default it is NaN as the reference leaves it (:175).
 	Returns a :class:`PSFFramesResult` (status OK, as the plugin: NaN fluxes are only logged there, :190-194).
 	"""
 	from .plugins import psf_star_selection, mag2flux
@@ -1037,6 +1039,7 @@ def psf_frames(ctx, stack, targets, catalog, time, quality, prf_model, readnoise
 		stamps_dev = ctx.array(cur[idx].astype('int32'))
 		images = engine.cut_stamps(ctx, stack.dev['images'], stamps_dev, H, W, stack.row0, stack.col0)
 		backgrounds = engine.cut_stamps(ctx, stack.dev['backgrounds'], stamps_dev, H, W, stack.row0, stack.col0)
+		err_cube = None
 		try:
 			# bit 1 of the aperture image (BasePhotometry.py:1033-1074) from the sum image -- for an FFI target a crop of the region's (:1001-1006)
 			finite = np.isfinite(engine.crop_sumimage(ctx, full_sumimage, stamps_dev, H, W, stack.row0, stack.col0).to_host()).reshape(len(idx), H, W)
@@ -1053,14 +1056,21 @@ def psf_frames(ctx, stack, targets, catalog, time, quality, prf_model, readnoise
 				cols, rows = np.meshgrid(np.arange(c1 + 1, cur[i, 3] + 1, dtype='int32'), np.arange(r1 + 1, cur[i, 1] + 1, dtype='int32'))
 				mini[j] = (np.abs(cols - tcol[i] - 1) <= 1) & (np.abs(rows - trow[i] - 1) <= 1) & finite[j]
 			coef = engine.linpsf_prf(ctx, base_coef, ctx.array(prf_model.weights(cur[idx])))
-			res = engine.psf_fit(ctx, images, backgrounds, coef, tx, ty, ctx.array(np.asarray(offsets, dtype='int64')), ctx.array(np.concatenate(params0, axis=0)),
-				ctx.array(mini), variance_floor=n_readout * readnoise**2 / gain**2, cutoff_radius=cutoff_radius)
+			d_offsets, d_mini = ctx.array(np.asarray(offsets, dtype='int64')), ctx.array(mini)
+			res = engine.psf_fit(ctx, images, backgrounds, coef, tx, ty, d_offsets, ctx.array(np.concatenate(params0, axis=0)),
+				d_mini, variance_floor=n_readout * readnoise**2 / gain**2, cutoff_radius=cutoff_radius)
+			if flux_errors:
+				err_cube = engine.cut_stamps(ctx, stack.dev['images_err'], stamps_dev, H, W, stack.row0, stack.col0)
+				engine.psf_flux_err(ctx, images, backgrounds, err_cube, coef, tx, ty, d_offsets, res['params'], d_mini,
+					variance_floor=n_readout * readnoise**2 / gain**2, cutoff_radius=cutoff_radius, out=res['flux_err'])
 			flux, flux_err = res['flux'].to_host(), res['flux_err'].to_host()
 			crow, ccol = res['centroid_row'].to_host(), res['centroid_col'].to_host()
 		finally:
 			ctx.sync()
 			images.free()
 			backgrounds.free()
+			if err_cube is not None:
+				err_cube.free()
 		out.flux[idx] = flux[:, :T]
 		out.flux_err[idx] = flux_err[:, :T]
 		out.pos_centroid[idx, :, 0] = crow[:, :T]

@@ -31,7 +31,7 @@ from . import engine, pipeline, stamps
 # [linpsf] flux_errors is this engine's own switch as well: the reference's LinPSF plugin has no flux errors (linpsf_photometry.py:169)
 # and ends in an error for it; the propagated pixel errors are a definition of this engine, on only when asked for
 DEFAULT_SETTINGS = {'todolist': {'faint_limit': '15.0'}, 'haloswitch': {'tmag_limit': '6.0', 'flux_limit': '0.01'},
-	'halo': {'enabled': 'false'}, 'linpsf': {'flux_errors': 'false'}}
+	'halo': {'enabled': 'false'}, 'linpsf': {'flux_errors': 'false'}, 'psf': {'flux_errors': 'false'}}
 
 TESS_DEFAULT_BITMASK = engine.TESS_DEFAULT_BITMASK
 #: PixelQualityFlags.BackgroundShenanigans / CorrectorQualityFlags.BackgroundShenanigans (photometry/quality.py:163, :85)
@@ -901,6 +901,14 @@ class PSFPhotometry(BasePhotometry):
 		self.readnoise = getattr(self.source, 'readnoise', 10)
 		self.gain = getattr(self.source, 'gain', 100)
 
+	@staticmethod
+	def flux_errors(settings=None):
+		"""Whether the flux errors are propagated from the pixel errors: the ``[psf] flux_errors`` switch of the settings
+		(``TESSPHOT_SETTINGS``), off by default -- the reference has none (psf_photometry.py:175)."""
+		if settings is None:
+			settings = load_settings()
+		return settings.getboolean('psf', 'flux_errors', fallback=False)
+
 	def _minimum_aperture(self):
 		"""psf_photometry.py:29-41"""
 		cols, rows = self.get_pixel_grid()
@@ -917,13 +925,26 @@ class PSFPhotometry(BasePhotometry):
 		params0 = np.column_stack((np.asarray(cat['row_stamp'][sel], dtype='float64'), np.asarray(cat['column_stamp'][sel], dtype='float64'),
 			mag2flux(np.asarray(cat['tmag'][sel], dtype='float64'))))
 		coef = engine.linpsf_prf(ctx, ctx.array(model.base_coef), ctx.array(model.weights(np.asarray([self._stamp]))))
-		res = engine.psf_fit(ctx, DeviceCube.from_host(ctx, self.images_cube), DeviceCube.from_host(ctx, self.backgrounds_cube), coef,
-			ctx.array(model.tx), ctx.array(model.ty), ctx.array(np.array([0, len(sel)], dtype='int64')), ctx.array(params0),
-			ctx.array(self._minimum_aperture().astype('uint8')[None]), variance_floor=self.n_readout * self.readnoise**2 / self.gain**2,
-			cutoff_radius=self.cutoff_radius)
+		variance_floor = self.n_readout * self.readnoise**2 / self.gain**2
 		lc = self.lightcurve
+		if self.flux_errors(self.settings):
+			# the same device arrays for the fit and the error pass after it, at the fit's own end points
+			images, backgrounds = DeviceCube.from_host(ctx, self.images_cube), DeviceCube.from_host(ctx, self.backgrounds_cube)
+			tx, ty, d_offsets = ctx.array(model.tx), ctx.array(model.ty), ctx.array(np.array([0, len(sel)], dtype='int64'))
+			d_mini = ctx.array(self._minimum_aperture().astype('uint8')[None])
+			res = engine.psf_fit(ctx, images, backgrounds, coef, tx, ty, d_offsets, ctx.array(params0), d_mini, variance_floor=variance_floor,
+				cutoff_radius=self.cutoff_radius)
+			lc['flux_err'] = engine.psf_flux_err(ctx, images, backgrounds, DeviceCube.from_host(ctx, self.images_err_cube), coef, tx, ty, d_offsets,
+				res['params'], d_mini, variance_floor=variance_floor, cutoff_radius=self.cutoff_radius).to_host()[0]
+			self.psf_params = res['params'].to_host()[:3 * len(sel)].T.reshape(self.Ntimes, len(sel), 3)   # (T, S, 3): the end points the pass used
+			self.additional_headers['PSF_FERR'] = (True, 'flux errors propagated from pixel errors')
+		else:
+			res = engine.psf_fit(ctx, DeviceCube.from_host(ctx, self.images_cube), DeviceCube.from_host(ctx, self.backgrounds_cube), coef,
+				ctx.array(model.tx), ctx.array(model.ty), ctx.array(np.array([0, len(sel)], dtype='int64')), ctx.array(params0),
+				ctx.array(self._minimum_aperture().astype('uint8')[None]), variance_floor=variance_floor,
+				cutoff_radius=self.cutoff_radius)
+			lc['flux_err'] = res['flux_err'].to_host()[0]
 		lc['flux'] = res['flux'].to_host()[0]
-		lc['flux_err'] = res['flux_err'].to_host()[0]
 		lc['pos_centroid'] = np.column_stack((res['centroid_row'].to_host()[0], res['centroid_col'].to_host()[0]))   # (row, column) as upstream (:176)
 		if np.any(np.isnan(lc['flux'])):
 			logging.getLogger(__name__).warning("We should flag that this has not gone well.")
