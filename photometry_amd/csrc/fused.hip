@@ -14,7 +14,8 @@
 // Masks above 128 pixels (rare) are left to tp_aperture_big_kernel, launched right after on the same stream.
 //
 // LDS plan per wavefront: the K2P2 work arrays (k2p2::shared_bytes); during A1 the good-cadence flags alias the
-// phase-shared region of the K2P2 arrays (k.srt), during A6 the mask pixel list aliases k.lab.
+// phase-shared region of the K2P2 arrays (k.srt), during A6 the mask pixel list aliases k.lab, and the extraction's pixel table
+// and the staged series take the start of the block (k.S onwards, dead by then).
 #include "sumimage_dev.h"
 #include "aperture_dev.h"
 #include "k2p2_args.h"
@@ -29,7 +30,7 @@ constexpr int kRows = 8; // pixel rows per A1 step: 8 x 1 KiB loads in flight pe
 // A1: the sum image is formed here (streams the whole images cube); false: it is an input (tp_background_sumimage formed it
 // while it streamed the raw cube for the background) and the kernel reads in-mask pixel rows only
 template <int VEC, bool VEC4, bool HAS_SUB, int BKG, bool A1>
-__global__ __launch_bounds__(64, 2) void tp_aperture_fused_kernel(tp_ap::Args a, k2p2::BatchArgs ka, k2p2::Params prm,
+__global__ __launch_bounds__(64, (BKG == 0 && VEC == 2) ? 2 : 3) void tp_aperture_fused_kernel(tp_ap::Args a, k2p2::BatchArgs ka, k2p2::Params prm,
 	const double* __restrict__ twid, const int32_t* __restrict__ quality, int64_t quality_stride, uint32_t bitmask,
 	double* __restrict__ sumimage_out, const int32_t* __restrict__ order)
 {
@@ -156,10 +157,14 @@ __global__ __launch_bounds__(64, 2) void tp_aperture_fused_kernel(tp_ap::Args a,
 		if (lane == 0 && a.big_list) a.big_list[1 + atomicAdd(&a.big_list[0], 1)] = target;
 		return;
 	}
-	tp_ap::pack_rows(s_list, M, a.width, lane, 64);
+	// the pixel table of the streamed extraction, at the start of the LDS (the mask builder's arrays are dead; the list lies at
+	// least 3 072 bytes in -- S, tmp, red, Z, dist and hval of a stamp of 64 pixels or fewer come before it -- and the table of at
+	// most kMaxList entries takes 2 560)
+	const size_t table_bytes = (size_t)tp_ap::pixel_table_entries(M) * tp_ap::kPixelEntryBytes;
+	const tp_ap::PixelTable table = tp_ap::build_pixel_table(smem, s_list, M, a, target, lane, 64);
 	__syncthreads();
 	// the series a lane needs in every pixel group (subtracted series, background series: the same array in the background-in-
-	// the-step configuration) are staged once in the part of the LDS the mask builder no longer needs: [smem, s_list)
+	// the-step configuration) are staged once in the part of the LDS the mask builder no longer needs: [table end, s_list)
 	const float* lds_sub = nullptr;
 	const float* lds_ser = nullptr;
 	{
@@ -167,8 +172,8 @@ __global__ __launch_bounds__(64, 2) void tp_aperture_fused_kernel(tp_ap::Args a,
 		const float* gsub = HAS_SUB ? (a.subtract + (int64_t)target * a.subtract_pitch) : nullptr;
 		const float* gser = SER ? (a.backgrounds + (int64_t)target * a.bkg_series_pitch) : nullptr;
 		const int nflt = (a.n_cad + VEC - 1) / VEC * VEC;                       // what the VEC-wide reads touch
-		const int room = (int)((reinterpret_cast<unsigned char*>(s_list) - smem) / sizeof(float));
-		float* stage = reinterpret_cast<float*>(smem);
+		const int room = (int)((reinterpret_cast<unsigned char*>(s_list) - (smem + table_bytes)) / sizeof(float));
+		float* stage = reinterpret_cast<float*>(smem + table_bytes);
 		const bool same = HAS_SUB && SER && (gsub == gser);
 		const int need = ((HAS_SUB ? 1 : 0) + ((SER && !same) ? 1 : 0)) * nflt;
 		if ((HAS_SUB || SER) && need > 0 && need <= room) {
@@ -180,8 +185,18 @@ __global__ __launch_bounds__(64, 2) void tp_aperture_fused_kernel(tp_ap::Args a,
 			__syncthreads();
 		}
 	}
-	if ((HAS_SUB && lds_sub) || (BKG == 1 && lds_ser)) tp_ap::extract_small_stream<VEC, HAS_SUB, BKG, true>(a, target, s_list, M, lane, 64, lds_sub, lds_ser);
-	else tp_ap::extract_small_stream<VEC, HAS_SUB, BKG, false>(a, target, s_list, M, lane, 64);
+	// the fused centroid terms need an exact product: CCD columns and rows of the stamp below 2^29 in magnitude (StreamState::side)
+	const int64_t cmax = (int64_t)std::abs((int64_t)a.stamps[target * 4 + 2] + 1) + a.width;
+	const int64_t rmax = (int64_t)std::abs((int64_t)a.stamps[target * 4 + 0] + 1) + a.height;
+	const bool fuse = cmax < ((int64_t)1 << 29) && rmax < ((int64_t)1 << 29);
+	const bool lds = (HAS_SUB && lds_sub) || (BKG == 1 && lds_ser);
+	if (lds) {
+		if (fuse) tp_ap::extract_small_stream<VEC, HAS_SUB, BKG, true, true>(a, target, table, M, lane, 64, lds_sub, lds_ser);
+		else tp_ap::extract_small_stream<VEC, HAS_SUB, BKG, true, false>(a, target, table, M, lane, 64, lds_sub, lds_ser);
+	} else {
+		if (fuse) tp_ap::extract_small_stream<VEC, HAS_SUB, BKG, false, true>(a, target, table, M, lane, 64);
+		else tp_ap::extract_small_stream<VEC, HAS_SUB, BKG, false, false>(a, target, table, M, lane, 64);
+	}
 }
 
 } // namespace
@@ -246,8 +261,9 @@ static int aperture_photometry_impl(tp_ctx* ctx, const tp_cube_desc* desc, bool 
 	size_t shmem = lay.total;
 	const size_t a1_bytes = lay.off_region + (size_t)((desc->n_cad + 3) & ~3) + 16; // flags live in the shared region
 	if (!given_sumimage && a1_bytes > shmem) shmem = a1_bytes;
-	if (shmem > 160 * 1024) {
-		// a stamp (or light curve) beyond the LDS-resident per-target state: the three stages one after the other, same results
+	if (shmem > 160 * 1024 || !tp_ap::stream_offsets_fit(P, desc->t_pitch)) {
+		// a stamp (or light curve) beyond the LDS-resident per-target state, or a cube whose row offsets within a target do not fit
+		// the 32-bit lane offsets of the streamed extraction: the three stages one after the other, same results
 		// (tp_k2p2_masks keeps its work arrays in HBM for such stamps)
 		int rc = given_sumimage ? TP_OK : tp_sumimage(ctx, desc, d_images, d_quality, quality_target_stride, bitmask, d_subtract, subtract_pitch, d_sumimage);
 		if (rc != TP_OK) return rc;
