@@ -934,6 +934,27 @@ int tp_wcs_star_positions(tp_ctx* ctx, const double* d_params, int32_t n_frames,
 	int32_t n_cad, const int32_t* d_k1, const int32_t* d_k2, const double* d_dt, const double* d_dx, double tolerance, int32_t maxiter,
 	double* d_pos_col, double* d_pos_row, int64_t pos_pitch, int32_t* d_status);
 
+/* ---- FITS image data units (csrc/fitsin.hip; the rules in csrc/fits_rules.h) -------------------------------------------------
+ * What FFIImage does with astropy on the host -- `np.asarray(hdu[1].data[0:2048, 44:2092], dtype='float32')` and the same for the
+ * uncertainty HDU (io.py:46-48), or the whole image of HDU 0 / 1 for other files (io.py:80-82) -- on a data unit that lies in device
+ * memory byte for byte as in the file (big-endian, NAXIS1 fastest).
+ * tp_fits_unpack: the window [row0, row0 + rows) x [col0, col0 + cols) of the naxis2 x naxis1 image at d_raw (16-byte aligned; the
+ *   host layer puts a unit on a 256-byte boundary) into d_out [rows][out_row_pitch] float32 (out_row_pitch >= cols, in values; what
+ *   lies between two rows is never written).  bitpix -32: the bytes of every value swapped, nothing else -- NaN payloads, +-inf,
+ *   -0.0 and denormals keep their bits.  bitpix -64: swapped, then float64 -> float32 rounded to nearest even like a C cast / numpy's
+ *   astype (denormal results kept, overflow to inf, NaN quiet with the top of its payload).  Rows whose 16-byte boundaries agree
+ *   between file and output move as 16-byte loads and stores with single values before and after (the TESS science window: all
+ *   of it), any other geometry value by value.  Any other bitpix (integer images, BSCALE / BZERO), a window that leaves the image
+ *   or is empty, a pitch below cols, a misaligned pointer: TP_ERR_INVALID and nothing is written.
+ * tp_fits_datasum: the DATASUM of the FITS checksum convention for the nbytes (a multiple of 4, < 2^34; a data unit with its
+ *   padding) at d_raw (16-byte aligned): the ones'-complement sum of the big-endian 32-bit words, i.e. their 64-bit integer sum with
+ *   the carries folded back, in d_wordsum[0] (device, 8-byte aligned).  Integer atomics only: the result is exact and
+ *   the same in every run.
+ * Both are asynchronous on the context's stream.                                                                                */
+int tp_fits_unpack(tp_ctx* ctx, const void* d_raw, int32_t bitpix, int32_t naxis1, int32_t naxis2, int32_t row0, int32_t col0, int32_t rows,
+	int32_t cols, float* d_out, int64_t out_row_pitch);
+int tp_fits_datasum(tp_ctx* ctx, const void* d_raw, uint64_t nbytes, uint64_t* d_wordsum);
+
 /* ---- synthetic data (bench / test utility, not part of the reference path) -----------------
  * Fill images / images_err / backgrounds cubes on the device from scene parameters, following
  * the data model of simulation/simulateFITS.py:338-405 (see photometry_amd/simulate.py).

@@ -70,6 +70,10 @@ static const char* const kKernelNames[TPK_COUNT] = {
 	"tp_motion_positions_kernel",
 	"tp_linpsf_err_kernel",
 	"tp_psf_err_kernel",
+	"tp_fits_unpack_kernel",
+	"tp_fits_unpack_scalar_kernel",
+	"tp_fits_datasum_kernel",
+	"tp_fits_fold_kernel",
 };
 
 extern "C" {

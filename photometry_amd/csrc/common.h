@@ -68,6 +68,10 @@ enum tp_kernel_id {
 	TPK_MOTION_POSITIONS,
 	TPK_LINPSF_FLUX_ERR,
 	TPK_PSF_FLUX_ERR,
+	TPK_FITS_UNPACK,
+	TPK_FITS_UNPACK_SCALAR,
+	TPK_FITS_DATASUM,
+	TPK_FITS_FOLD,
 	TPK_COUNT
 };
 

@@ -200,6 +200,51 @@ def _parse_value(s):
 		return float(s.replace('D', 'E'))
 
 
+def read_header_blocks(next_block):
+	"""
+	The header of one HDU from its 2880-byte blocks: ``next_block()`` returns the next block (bytes) until the ``END`` card has been
+	seen.  Returns ``(header dict, raw 80-column cards up to and including END)``; an empty or short block raises ``EOFError``.
+	"""
+	header = {}
+	raw_cards = []
+	done = False
+	while not done:
+		block = next_block()
+		if len(block) < BLOCK:
+			raise EOFError("FITS header ends before its END card")
+		block = block.decode('ascii')
+		for i in range(0, BLOCK, 80):
+			c = block[i:i + 80]
+			raw_cards.append(c)
+			key = c[:8].strip()
+			if key == 'END':
+				done = True
+				break
+			if c[8:10] == '= ':
+				val = c[10:]
+				if val.lstrip().startswith("'"):
+					q = val.index("'")
+					end = q + 1
+					while True:
+						end = val.index("'", end)
+						if end + 1 < len(val) and val[end + 1] == "'":
+							end += 2
+							continue
+						break
+					header[key] = _parse_value(val[:end + 1])
+				else:
+					header[key] = _parse_value(val.split('/')[0])
+	return header, raw_cards
+
+
+def data_unit_bytes(header):
+	"""``(shape, bytes of the data unit without its padding)`` of an image or table HDU from its header."""
+	naxis = header.get('NAXIS', 0)
+	shape = [header[f'NAXIS{i}'] for i in range(naxis, 0, -1)]
+	nbytes = (abs(header.get('BITPIX', 8)) // 8) * int(np.prod(shape, dtype='int64')) if naxis else 0
+	return shape, nbytes
+
+
 def read(path):
 	"""Returns a list of ``(header dict, data)``; data is None, an ndarray (image) or a dict of column arrays (table)."""
 	opener = gzip.open if str(path).endswith('.gz') else open
@@ -207,34 +252,14 @@ def read(path):
 		blob = fh.read()
 	out = []
 	pos = 0
+
+	def next_block():
+		nonlocal pos
+		pos += BLOCK
+		return blob[pos - BLOCK:pos]
+
 	while pos < len(blob):
-		header = {}
-		raw_cards = []
-		done = False
-		while not done:
-			block = blob[pos:pos + BLOCK].decode('ascii')
-			pos += BLOCK
-			for i in range(0, BLOCK, 80):
-				c = block[i:i + 80]
-				raw_cards.append(c)
-				key = c[:8].strip()
-				if key == 'END':
-					done = True
-					break
-				if c[8:10] == '= ':
-					val = c[10:]
-					if val.lstrip().startswith("'"):
-						q = val.index("'")
-						end = q + 1
-						while True:
-							end = val.index("'", end)
-							if end + 1 < len(val) and val[end + 1] == "'":
-								end += 2
-								continue
-							break
-						header[key] = _parse_value(val[:end + 1])
-					else:
-						header[key] = _parse_value(val.split('/')[0])
+		header, raw_cards = read_header_blocks(next_block)
 		naxis = header.get('NAXIS', 0)
 		shape = [header[f'NAXIS{i}'] for i in range(naxis, 0, -1)]
 		nbytes = (abs(header.get('BITPIX', 8)) // 8) * int(np.prod(shape)) if naxis else 0
