@@ -14,7 +14,15 @@
 // loads of some wavefronts hide under the sorting of others (the round-1 kernel -- a quad per frame, 64 values per
 // lane, 185 VGPRs, 2 wavefronts per SIMD -- spent 40 % of its life waiting for its loads and ran at 10.9 ms).
 //   1. loads: buffer_load_dword with a per-lane voffset and a scalar soffset per pixel row (no address arithmetic on
-//      the vector ALU); pixel mask of backgrounds.py:89-94 and the float64 sums of the unclipped frame on the fly;
+//      the vector ALU); the float64 sums of the unclipped frame on the fly (widen, add, multiply-add per value).  The pixel
+//      mask of backgrounds.py:89-94 is settled per REGISTER ROW, not per value: a row (one v[j] across the wavefront = 8 pixels
+//      of each of its 8 frames) is put to ONE integer comparison of the bit patterns against the cutoff's, which writes the
+//      wavefront's mask into a scalar pair, and a scalar branch falls through when no lane objects -- the value stays as it
+//      is, enters the sums as it is and nothing is counted (the count starts from the slots the lane holds; a masked pixel
+//      takes one off).  A row with a masked value (NaN, negative, above the cutoff; also -0.0, which the exact test then
+//      keeps) runs the exact statements -- two float compares, two selects, the count -- and joins the same sums.  At 1e-3
+//      NaN per pixel-cadence 0.94 of the rows are clean (a frame: 0.80, a wavefront: 0.16 -- the grains earlier fast paths
+//      chose); real stamps are cleaner.  The partial last row and the instances for other stamp sizes test every slot;
 //   2. each lane sorts its 32 values with an unrolled bitonic network (v_min_f32 / v_max_f32 on compile-time register
 //      indices), then three cross-lane merge levels (2, 4, 8 lanes): a MIRROR stage (register j against register 31-j
 //      of the partner lane: DPP quad_perm / row_half_mirror) turns two ascending runs into two bitonic halves, the
@@ -204,21 +212,49 @@ __device__ __forceinline__ FrameSums bkg_frame_sort(const BkgArgs& a, float (&v)
 	constexpr int R = 256 / G;             // values per lane
 	constexpr int NREAL = (JFULL >= 0 && JFULL + 1 < R) ? (JFULL + 1) : R;   // registers 0..NREAL-1 can hold a pixel (JFULL: the first lanes only)
 	const float inf = __builtin_inff();
-	int n = 0;
+	// The mask is settled per REGISTER ROW (one v[j] across the wavefront: G pixels of each of its frames).  A masked pixel is
+	// rare, and the selects and the count do nothing for a row without one: a complete row (j < JFULL) is first put to one
+	// integer comparison, whose result is the wavefront's mask in a scalar pair, and a scalar branch falls through when no lane
+	// objects.  The bit pattern of a float in [+0.0, cutoff] is, read as unsigned, at most the cutoff's: NaN, negative values,
+	// -inf, -0.0 and values above the cutoff all lie above it.  -0.0 is NOT masked (`< 0` is false): the pre-test only sends its
+	// row to the exact statements, which keep it.  (The two float compares as the pre-test: 0.07 ms slower)
+	// A cutoff that is negative, -0.0 or NaN (its bit pattern orders nothing) is launched on the JFULL = -1 instances.
+	// The complete rows are counted up front and a masked pixel takes one off, so that a clean row counts nothing.
+	const unsigned cut_bits = __float_as_uint(a.flux_cutoff);
+	int n = (JFULL > 0) ? JFULL : 0;
 	double s1 = 0.0, s2 = 0.0;
 #pragma unroll
 	for (int j = 0; j < NREAL; ++j) {
 		const float x = v[j];
-		// backgrounds.py:91-94: mask = ~isfinite | > flux_cutoff | < 0; slots past the last pixel are masked too
-		bool ok = (x >= 0.f) && (x <= a.flux_cutoff);
-		if (JFULL < 0 || j >= JFULL) ok = ok && (j * G + g < a.n_pix);
-		n += ok ? 1 : 0;
-		v[j] = ok ? x : inf;
-		float z = ok ? x : 0.f;
-		asm("" : "+v"(z));   // keep the conversion in the loop (else R doubles stay live)
-		const double zd = (double)z;
+		float kept = x;
+		double zd;
+		if (JFULL >= 0 && j < JFULL) {
+			// The clean row's results are formed BEFORE the test and the rare arm overwrites them in place: the arms meet in the same
+			// registers, so there is one copy of the sums, nothing new that lives and no move to join them on the clean path (an if / else that
+			// meets in a new value cost a copy per row, and the sums of 28 rows sank below the loop: 132 bytes of scratch per lane).
+			// The widening is written as an instruction so that it stays in the loop (else R doubles stay live); `volatile` in the
+			// rare arm keeps it a branch (the optimiser turns the triangle back into selects).
+			asm("v_cvt_f64_f32 %0, %1" : "=v"(zd) : "v"(x));
+			if (__builtin_expect(tp_any(__float_as_uint(x) > cut_bits), 0)) {
+				const bool ok = (x >= 0.f) && (x <= a.flux_cutoff);   // backgrounds.py:91-94, as below
+				n -= ok ? 0 : 1;
+				kept = ok ? x : inf;
+				const float z = ok ? x : 0.f;
+				asm volatile("v_cvt_f64_f32 %0, %1" : "=v"(zd) : "v"(z));
+			}
+		} else {
+			// backgrounds.py:91-94: mask = ~isfinite | > flux_cutoff | < 0; slots past the last pixel are masked too
+			const bool ok = (x >= 0.f) && (x <= a.flux_cutoff) && (j * G + g < a.n_pix);
+			n += ok ? 1 : 0;
+			kept = ok ? x : inf;
+			float z = ok ? x : 0.f;
+			asm("" : "+v"(z));   // keep the conversion in the loop (else R doubles stay live)
+			zd = (double)z;
+		}
+		v[j] = kept;
 		s1 += zd;
 		s2 = __builtin_fma(zd, zd, s2);
+		if (JFULL >= 0 && j < JFULL) asm volatile("" : "+v"(s1), "+v"(s2));   // the sums are taken row by row, between the branches
 	}
 	n = frame_sum<G>(n);
 	s1 = frame_sum<G>(s1);
@@ -1014,6 +1050,11 @@ __global__ __launch_bounds__(256) void tp_bkg_subtract_kernel(const float* __res
 	}
 }
 
+// bkg_frame_sort's per-row pre-test reads the cutoff's bit pattern as an unsigned bound: that orders the floats only for a
+// cutoff in [+0.0, +inf].  Any other (negative, -0.0, NaN: every pixel or all but the zeros masked) takes the JFULL = -1
+// instances, which put every value to the exact statements.
+bool row_pretest_ok(float flux_cutoff) { return flux_cutoff >= 0.f && !std::signbit(flux_cutoff); }
+
 } // namespace
 
 extern "C" int tp_background_stamp(tp_ctx* ctx, const tp_cube_desc* desc, const float* d_raw,
@@ -1038,7 +1079,7 @@ extern "C" int tp_background_stamp(tp_ctx* ctx, const tp_cube_desc* desc, const 
 		dim3 grid((unsigned)desc->n_targets, (unsigned)((desc->n_cad + kFramesPerBlock - 1) / kFramesPerBlock));
 		constexpr int G = 8;   // lanes per frame; 4 (16 frames per wavefront, 64 values per lane, 109 VGPRs, 16 KB of LDS per wavefront) measured 6.4 ms against 5.6
 		dim3 block(kFramesPerBlock * G);
-		const int jfull = a.n_pix / G;
+		const int jfull = row_pretest_ok(a.flux_cutoff) ? a.n_pix / G : -1;
 		if (jfull == 225 / G) TP_LAUNCH(ctx, TPK_BKG_STAMP, (tp_bkg_stamp_kernel<G, 225 / G>), grid, block, shmem, a, frame_stride);        // 15 x 15
 		else if (jfull == 121 / G) TP_LAUNCH(ctx, TPK_BKG_STAMP, (tp_bkg_stamp_kernel<G, 121 / G>), grid, block, shmem, a, frame_stride);   // 11 x 11
 		else TP_LAUNCH(ctx, TPK_BKG_STAMP, (tp_bkg_stamp_kernel<G, -1>), grid, block, shmem, a, frame_stride);
@@ -1097,7 +1138,7 @@ extern "C" int tp_background_sumimage(tp_ctx* ctx, const tp_cube_desc* desc, con
 	s.b.flux_cutoff = (float)flux_cutoff; s.b.exclude_fraction = (float)(exclude_percentile / 100.0);
 	s.smooth = d_bkg; s.quality = d_quality; s.quality_stride = quality_target_stride; s.bitmask = bitmask; s.sumimage = d_sumimage; s.w = w;
 	const dim3 grid((unsigned)desc->n_targets), block(256);
-	const int jfull = n_pix / 8;
+	const int jfull = row_pretest_ok(s.b.flux_cutoff) ? n_pix / 8 : -1;
 #define TP_BKG_SUM_LAUNCH(JF, WW) do { \
 		auto kern = tp_bkg_stamp_sum_kernel<JF, WW>; \
 		if (shmem > 64 * 1024) TP_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem)); \
