@@ -6,6 +6,7 @@
 // frame against 117 MB of algorithmic bytes).  Both functions return exactly the float32 the materialising kernels store.
 #pragma once
 #include "common.h"
+#include "radial_rules.h"
 
 struct ZoomImage {
 	const double* coef; const double* vmin; const double* vmax;   // [frame][ny][nx], [frame], [frame] (tp_background_mesh_finish)
@@ -84,7 +85,8 @@ struct RadialSpline {
 // The ring profile of a frame staged for evaluation: knots t[0..n), coefficients c[0..n-4) and, per knot interval l, the six
 // reciprocals of the knot differences de Boor's recursion divides by (one division per interval and difference instead of six
 // per pixel: the quotient and the product by the correctly rounded reciprocal differ by an ulp at most, 1e-16 in the exponent
-// of a value that is stored as float32).  `stage` = kMaxKnotsStaged-strided arrays in LDS, filled by stage_radial().
+// of a value that is stored as float32).  `stage` = max_knots-strided arrays in LDS, filled by stage_radial(); what is staged and
+// how it is evaluated: radial_rules.h (knot_reciprocals, radial_value).
 constexpr int kRadialStageDoubles(int max_knots) { return 8 * max_knots; }
 
 __device__ __forceinline__ void stage_radial(double* stage, int max_knots, const RadialSpline& sp, int frame, int n, int tid, int nthreads)
@@ -97,40 +99,13 @@ __device__ __forceinline__ void stage_radial(double* stage, int max_knots, const
 		c[i] = sp.coefs[(int64_t)frame * sp.max_knots + i];
 	}
 	__syncthreads();
-	for (int l = 3 + tid; l <= n - 5; l += nthreads) {
-		inv[6 * l + 0] = 1.0 / (t[l + 3] - t[l]);
-		inv[6 * l + 1] = 1.0 / (t[l + 2] - t[l - 1]);
-		inv[6 * l + 2] = 1.0 / (t[l + 1] - t[l - 2]);
-		inv[6 * l + 3] = 1.0 / (t[l + 2] - t[l]);
-		inv[6 * l + 4] = 1.0 / (t[l + 1] - t[l - 1]);
-		inv[6 * l + 5] = 1.0 / (t[l + 1] - t[l]);
-	}
+	for (int l = 3 + tid; l <= n - 5; l += nthreads) tp_radial::knot_reciprocals(t, l, inv + 6 * l);
 	__syncthreads();
 }
 
-// 10**spline(r) - zeropoint at one pixel (backgrounds.py:186-188; ext = 3: the boundary value outside the end knots) from the
-// staged profile; n = the frame's number of knots (< 8: no radial component, 0)
+// 10**spline(r) - zeropoint at one pixel from the staged profile; n = the frame's number of knots (< 8: no radial component, 0)
 __device__ __forceinline__ double radial_value(const double* stage, int max_knots, int n, double zeropoint, double col_offset, double xcen, double ycen,
 	int row, int col)
 {
-	if (n < 8) return 0.0;
-	const double* t = stage;
-	const double* c = stage + max_knots;
-	const double dx = ((double)col + col_offset) - xcen, dy = (double)row - ycen;
-	double x = sqrt(dx * dx + dy * dy);
-	x = fmin(fmax(x, t[3]), t[n - 4]);
-	// interval t[l] <= x < t[l + 1], 3 <= l <= n - 5
-	int l = 3, h = n - 4;
-	while (h - l > 1) { const int m = (l + h) >> 1; if (x >= t[m]) l = m; else h = m; }
-	const double* iv = stage + 2 * max_knots + 6 * l;
-	// de Boor, cubic
-	double d0 = c[l - 3], d1 = c[l - 2], d2 = c[l - 1], d3 = c[l];
-	double al;
-	al = (x - t[l]) * iv[0];     d3 = (1.0 - al) * d2 + al * d3;
-	al = (x - t[l - 1]) * iv[1]; d2 = (1.0 - al) * d1 + al * d2;
-	al = (x - t[l - 2]) * iv[2]; d1 = (1.0 - al) * d0 + al * d1;
-	al = (x - t[l]) * iv[3];     d3 = (1.0 - al) * d2 + al * d3;
-	al = (x - t[l - 1]) * iv[4]; d2 = (1.0 - al) * d1 + al * d2;
-	al = (x - t[l]) * iv[5];     d3 = (1.0 - al) * d2 + al * d3;
-	return exp10(d3) - zeropoint;
+	return tp_radial::radial_value(stage, stage + max_knots, stage + 2 * max_knots, n, zeropoint, col_offset, xcen, ycen, row, col);
 }

@@ -1,5 +1,5 @@
 // halo_rules.h -- what Halo photometry decides (halo.hip: the TV-min solver; halo_stack.hip: the frames path), each rule stated once
-// over plain values: the order-preserving keys and the bookkeeping of a radix pass, the pixel and cadence rules of the frames path,
+// over plain values: the order-preserving keys and the bookkeeping of a radix pass (select_rules.h), the pixel and cadence rules of the frames path,
 // the optimiser's state machine (line search, pair keeping, history slots, stopping tests, direction), and the host tables of the
 // entries with their argument checks.  No device code, no HIP runtime: the kernels call these from their parallel plumbing
 // (halo_dev.h), tests/hostsim/halo_rules_host.cpp composes them serially under AddressSanitizer and UBSan, and
@@ -10,14 +10,7 @@
 #include <cmath>
 #include <cstdint>
 #include <vector>
-
-#ifndef TP_RULE
-#if defined(__HIPCC__)
-#define TP_RULE __host__ __device__
-#else
-#define TP_RULE
-#endif
-#endif
+#include "select_rules.h"
 
 namespace tp_halo {
 
@@ -66,54 +59,22 @@ struct NormProb {
 	int32_t q, npix, ncad, pad;
 };
 
-//--------------------------------------------------------------------------------------------------
-// keys: unsigned integers in the order of the values (-inf < ... < -0 < +0 < ... < +inf), and back
-//--------------------------------------------------------------------------------------------------
-TP_RULE inline uint64_t okey(double v)
-{
-	const uint64_t u = __builtin_bit_cast(uint64_t, v);
-	return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
-}
-TP_RULE inline double from_key(uint64_t k) { return __builtin_bit_cast(double, (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k); }
-TP_RULE inline uint32_t fkey(float v)
-{
-	const uint32_t u = __builtin_bit_cast(uint32_t, v);
-	return (u >> 31) ? ~u : (u | 0x80000000u);
-}
-TP_RULE inline float from_fkey(uint32_t k) { return __builtin_bit_cast(float, (k >> 31) ? (k & 0x7fffffffu) : ~k); }
+// the order-preserving keys and the bookkeeping of a radix pass: select_rules.h, visible here under their names
+using tp_select::okey;
+using tp_select::from_key;
+using tp_select::fkey;
+using tp_select::from_fkey;
+using tp_select::RadixPass;
+using tp_select::radix_begin;
+using tp_select::radix_takes_part;
+using tp_select::radix_digit;
+using tp_select::radix_walk;
+using tp_select::radix_next;
 
 // numpy's median of nf values: the ranks (0-based, ascending) of the one or two middle values, and the median from their keys
 TP_RULE inline int mid_lo(int nf) { return (nf - 1) / 2; }
 TP_RULE inline int mid_hi(int nf) { return nf / 2; }
 TP_RULE inline double median_of_keys(uint64_t lo, uint64_t hi, bool two) { return two ? (from_key(lo) + from_key(hi)) / 2.0 : from_key(lo); }
-
-// Radix selection of the key of rank k, most significant byte first: a pass counts the digit at `shift` of the keys that agree with
-// `prefix` on the bytes above (`mask`); the bin that holds the rank becomes the next byte of the prefix, the rank goes on as the
-// remainder inside the bin.  After the last pass the prefix is the key and `krem` counts the equal keys before the selected one.
-struct RadixPass {
-	uint64_t prefix, mask;
-	int shift, krem;
-};
-TP_RULE inline RadixPass radix_begin(int k) { return RadixPass{0, 0, 56, k}; }
-TP_RULE inline bool radix_takes_part(const RadixPass& p, uint64_t key) { return (key & p.mask) == p.prefix; }
-TP_RULE inline int radix_digit(const RadixPass& p, uint64_t key) { return (int)((key >> p.shift) & 255); }
-// bins c[0 .. n) starting at number b with `cum` keys below them: on to the bin that holds rank krem (the last one takes the rest)
-TP_RULE inline void radix_walk(const int* c, int n, int krem, int& b, int& cum)
-{
-	for (int i = 0; i + 1 < n && krem >= cum + c[i]; i++) {
-		cum += c[i];
-		b++;
-	}
-}
-// false after the last pass
-TP_RULE inline bool radix_next(RadixPass& p, int bin, int rem)
-{
-	p.prefix |= (uint64_t)bin << p.shift;
-	p.mask |= (uint64_t)255 << p.shift;
-	p.krem = rem;
-	p.shift -= 8;
-	return p.shift >= 0;
-}
 
 //--------------------------------------------------------------------------------------------------
 // the frames path: pixels and cadences of a problem

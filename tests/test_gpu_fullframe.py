@@ -9,6 +9,7 @@ B2, B3 and A1 are bit-exact (A1: float64 sums of float32 values in frame order o
 """
 import numpy as np
 import pytest
+import radial_common
 
 pytestmark = pytest.mark.gpu
 
@@ -544,3 +545,156 @@ def test_median_filter_15_shared_columns(ctx):
 			want = median_filter(x, size=15)
 			want[~np.isfinite(want)] = np.nan
 			np.testing.assert_array_equal(got[k], want)
+
+
+# ---- the ring kernel and the profile kernel at their own boundaries (hand-made rings: the camera geometry never gives these) ----------
+HAND_RING_SIZES = (0, 1, 2, 3, 255, 256, 257, 2047, 2048, 2049, 4097)
+HAND_CUTOFF = 8e4
+
+
+def _hand_rings(seed=3):
+	"""Two 64 x 80 frames and 19 hand-made rings over them (rings share pixels): lists of the sizes around the ring kernel's block (256)
+	and batch (2048) boundaries, each sprinkled with masked pixels of the four kinds (negative, above the cutoff, NaN, manually
+	excluded) so that the ordered compaction matters; three rings whose KEPT count sits on 256 / 2048 / 2049; an all-equal ring of odd
+	and one of even kept count (zero bandwidth: the median -- 3 and 8 samples, whose sum and mean are exact in every order
+	of summation, so that neither side's standard deviation is a rounding residue); a ring of kept count 0 and one of kept count 1 after masking.  The second
+	frame has further NaN pixels, so its kept counts differ.  The kept pixels' logarithms are ``2.0 + normal(0, 2e-3)`` to float32
+	rounding (the samples of test_radial_rules_host).  Returns a dict: ``frames`` (2, 64, 80) float32, ``exclude`` (64, 80) uint8,
+	``square`` (2, 64, 80) float32 (constant on the all-equal rings), ``pixels`` / ``offsets`` int32, ``names``."""
+	rng = np.random.default_rng(seed)
+	R, C = 64, 80
+	P = R * C
+	perm = rng.permutation(P)
+	masked, equal, small, big, zero = perm[:400], perm[400:440], perm[440:520], perm[520:-1], perm[-1]
+	f = np.empty((2, P), dtype='float32')
+	for k in range(2):
+		f[k] = (10.0**(2.0 + rng.normal(0, 2e-3, P)) - 1.0).astype('float32')
+	f[:, masked[:100]] = -3.0
+	f[:, masked[100:200]] = 9e4
+	f[:, masked[200:300]] = np.nan
+	exclude = np.zeros(P, dtype='uint8')
+	exclude[masked[300:400]] = 1
+	f[:, equal] = 150.0
+	f[:, zero] = 0.0                                                    # the frames' minimum, in no ring: zero point 1
+	f[1, big[rng.random(len(big)) < 0.03]] = np.nan                       # frame 1 only: other kept counts in the large rings
+	square = (20.0 + 0.05 * np.arange(P) / C + rng.normal(0, 0.01, (2, P))).astype('float32')
+	square[:, equal] = 20.0
+
+	def sprinkled(good, n_masked):
+		"""``good`` with ``n_masked`` masked pixels at random places of the list"""
+		ring = np.concatenate([good, rng.choice(masked, n_masked, replace=False)])
+		where = rng.permutation(len(ring))
+		return ring[where]
+	rings, names = [], []
+	for S in HAND_RING_SIZES:
+		nm = min(S // 10, 300) if S > 3 else 0
+		rings.append(sprinkled(rng.choice(big if S > 3 else small, S - nm, replace=False), nm)); names.append(f'list of {S}')
+	for S in (256, 2048, 2049):
+		rings.append(sprinkled(rng.choice(big, S, replace=False), 31)); names.append(f'{S} kept in frame 0')
+		assert np.isnan(f[0, rings[-1]]).sum() == np.isin(rings[-1], masked[200:300]).sum()     # frame 0: no NaN but the sprinkled ones
+	rings.append(sprinkled(equal[:3], 3)); names.append('all equal, 3 kept')
+	rings.append(sprinkled(equal[3:11], 2)); names.append('all equal, 8 kept')
+	rings.append(masked[[0, 100, 200, 300, 1]].copy()); names.append('0 kept')
+	rings.append(np.array([masked[2], masked[101], small[0], masked[201], masked[301]])); names.append('1 kept')
+	rings.append(np.array([masked[3], small[1], masked[102], small[2]])); names.append('2 kept')
+	offsets = np.concatenate([[0], np.cumsum([len(r) for r in rings])]).astype('int32')
+	return {'frames': f.reshape(2, R, C), 'exclude': exclude.reshape(R, C), 'square': square.reshape(2, R, C),
+		'pixels': np.concatenate(rings).astype('int32'), 'offsets': offsets, 'names': names}
+
+
+def _hand_ring_logs(h, with_square):
+	"""Per frame the zero point and per ring the kept pixels' logarithms, in list order, as ``fit_background_tess(device_arithmetic=True)``
+	forms them: first round float32 arithmetic with the correctly rounded float32 log10, with a square component float64."""
+	from oracle import backgrounds as ob
+	zps, logs = [], []
+	for k in range(2):
+		img = h['frames'][k].ravel()
+		keep = ~ob.stamp_mask(img, HAND_CUTOFF, h['exclude'].ravel())
+		if with_square:
+			v = img.astype('float64') - h['square'][k].ravel().astype('float64')
+			zp = -np.min(v[keep]) + 1.0
+			arg = np.where(keep, v, 1.0) + zp
+		else:
+			zp = -np.float64(np.min(img[keep])) + 1.0
+			arg = (np.where(keep, img, np.float32(1)) + np.float32(zp)).astype('float64')
+		u, inverse = np.unique(arg, return_inverse=True)                  # (one log10 per value: numpy's vector and scalar loops differ by an ulp)
+		lg = np.log10(u)[inverse]
+		if not with_square:
+			lg = lg.astype('float32').astype('float64')
+		zps.append(zp)
+		logs.append([lg[p][keep[p]] for p in (h['pixels'][a:b] for a, b in zip(h['offsets'][:-1], h['offsets'][1:]))])
+	return np.array(zps), logs
+
+
+def _run_hand_rings(ctx, h, with_square):
+	zps, logs = _hand_ring_logs(h, with_square)
+	n_rings, P = len(h['offsets']) - 1, h['frames'][0].size
+	d_f, d_ex, d_sq, d_zp = ctx.array(h['frames']), ctx.array(h['exclude']), ctx.array(h['square']), ctx.array(zps)
+	d_pix, d_off = ctx.array(h['pixels']), ctx.array(h['offsets'])
+	out = []
+	for _ in range(2):
+		scratch, modes, counts = ctx.empty((2, int(h['offsets'][-1])), 'float64'), ctx.empty((2, n_rings), 'float64'), ctx.empty((2, n_rings), 'int32')
+		ctx._check(ctx.lib.tp_radial_ring_modes(ctx.handle, d_f.ptr, 2, P, P, d_sq.ptr if with_square else None, P, d_ex.ptr, 0, HAND_CUTOFF, d_zp.ptr,
+			d_pix.ptr, d_off.ptr, n_rings, int(h['offsets'][-1]), float(radial_common.BW_CONSTANT), scratch.ptr, modes.ptr, counts.ptr))
+		out.append((modes.to_host(), counts.to_host()))
+	return zps, logs, out
+
+
+@pytest.mark.parametrize('with_square', (False, True))
+def test_ring_modes_of_hand_made_rings(ctx, with_square):
+	"""tp_radial_ring_modes called directly with the rings of ``_hand_rings``, two frames in one call, without a square image (float32
+	first-round arithmetic) and with one (float64): the counts exact, the modes against ``oracle.backgrounds.reduce_mode(binning='fixed')``
+	on the logarithms of the kept pixels in list order -- same NaN pattern, same grid point (radial_common: what that is held to and
+	the margin asserted on the oracle), the all-equal rings exactly their value -- and a second call bit for bit the same."""
+	import warnings
+	h = _hand_rings()
+	zps, logs, ((modes, counts), (modes2, counts2)) = _run_hand_rings(ctx, h, with_square)
+	assert np.array_equal(modes.view('uint64'), modes2.view('uint64')) and np.array_equal(counts, counts2)
+	assert np.array_equal(counts, [[len(x) for x in frame] for frame in logs])
+	assert list(counts[0][:4]) == [0, 1, 2, 3] and list(counts[0][11:14]) == [256, 2048, 2049] and list(counts[0][14:]) == [3, 8, 0, 1, 2]
+	assert counts[0][10] > 2048 + 1024 and np.all(counts[1][4:14] <= counts[0][4:14]) and np.any(counts[1][4:14] < counts[0][4:14])
+	rules = []
+	for k in range(2):
+		for j, x in enumerate(logs[k]):
+			with warnings.catch_warnings():
+				warnings.simplefilter('ignore', RuntimeWarning)
+				rules.append(radial_common.assert_same_mode(modes[k, j], x, label=(k, h['names'][j])))
+	per_frame = ['nan', 'nan', 'tie'] + ['argmax'] * 11 + ['median', 'median', 'nan', 'nan', 'tie']
+	assert rules == per_frame * 2
+	for k in range(2):
+		assert modes[k, 14] == logs[k][14][0] and modes[k, 15] == logs[k][15][0]
+
+
+def test_ring_profiles_of_64_rings_and_of_exactly_four(ctx):
+	"""tp_radial_profiles at the kernel's limit of 64 rings (68 knots: the lanes take two turns at the knots) and with exactly 4
+	usable rings (the smallest system; 3 give none), with the assertions of test_mesh_finish_and_ring_profiles_on_device."""
+	from scipy.interpolate import InterpolatedUnivariateSpline
+	from photometry_amd import prepare
+	rng = np.random.default_rng(22)
+	nr = 64
+	bc = 2400.0 + 15.0 * np.arange(nr) + 7.5
+	s2 = 2.0 + 0.3 * np.sin(bc / 100.0)[None, :] + rng.normal(0, 2e-3, (5, nr))
+	s2[1, [0, 1, 30, 31, 32, 63]] = np.nan
+	s2[2, :] = np.nan; s2[2, [2, 9, 40, 63]] = [2.0, 2.2, 2.1, 2.4]         # exactly 4 usable rings
+	s2[3, :] = np.nan; s2[3, [2, 40, 63]] = [2.0, 2.1, 2.4]                 # 3: no spline
+	s2[4, ::2] = np.nan
+	seen = set()
+	for smooth in (0, 3, 8):
+		K = nr + 4
+		knots, coefs, nk = ctx.zeros((5, K), 'float64'), ctx.zeros((5, K), 'float64'), ctx.zeros((5,), 'int32')
+		d_s2, d_bc = ctx.array(s2), ctx.array(bc)
+		ctx._check(ctx.lib.tp_radial_profiles(ctx.handle, 5, nr, d_s2.ptr, d_bc.ptr, smooth, K, knots.ptr, coefs.ptr, nk.ptr))
+		kn, co, n = knots.to_host(), coefs.to_host(), nk.to_host()
+		for k in range(5):
+			prof = prepare._move_median_central(s2[k], smooth) if smooth else s2[k]
+			good = ~np.isnan(prof)
+			seen.add(int(good.sum()))
+			if good.sum() < 4:
+				assert n[k] == 0
+				continue
+			t, c, _ = InterpolatedUnivariateSpline(bc[good], prof[good], k=3, ext=3)._eval_args
+			assert n[k] == len(t)
+			np.testing.assert_array_equal(kn[k, :len(t)], t)
+			m = int(good.sum())
+			np.testing.assert_allclose(co[k, :m], c[:m], rtol=1e-11, atol=1e-12)
+	assert {64, 4, 3} <= seen
