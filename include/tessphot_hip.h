@@ -955,6 +955,25 @@ int tp_fits_unpack(tp_ctx* ctx, const void* d_raw, int32_t bitpix, int32_t naxis
 	int32_t cols, float* d_out, int64_t out_row_pitch);
 int tp_fits_datasum(tp_ctx* ctx, const void* d_raw, uint64_t nbytes, uint64_t* d_wordsum);
 
+/* ---- target pixel files (csrc/tpfin.hip; the rules in csrc/tpf_rules.h) ---------------------------------------------------------
+ * What BasePhotometry._load_cube does with astropy on the host for a `tpf` run -- `cube[:, :, k] = data[field][k]` for every row k
+ * of the PIXELS table (BasePhotometry.py:720-751) -- on the table's data unit as it lies in device memory byte for byte as in the
+ * file: n_rows rows of row_bytes bytes, one cadence per row, big-endian.
+ * tp_tpf_unpack: n_cols (1..4) image columns of TFORM `E` (big-endian float32, n_pix values each, beginning h_col_offsets[c] bytes
+ *   into a row; HOST array) into the cubes h_d_out[c] (HOST array of device pointers), each [n_pix][t_pitch] float32 with the
+ *   cadence fastest and the pixels in the row's own order (TDIM lists the fastest axis first: pixel = r * W + c).  h_rows (HOST;
+ *   may be NULL: all rows, T == n_rows): the T table rows that are kept, strictly increasing -- the reference drops the rows whose
+ *   TIME is not finite (BasePhotometry.py:339-340); the list is checked before anything is queued.  The bytes of every value are
+ *   swapped and nothing else: NaN payloads, signalling NaNs, -0.0 and denormals keep their bits.  The pad cadences [T, t_pitch) of
+ *   every pixel are written as 0.0, so the cubes need no memset.  One launch for all columns.
+ *   TP_ERR_INVALID and nothing written: a null pointer, d_table or a cube not 4-byte aligned, row_bytes or a column offset that
+ *   is no multiple of 4, a column that leaves the row (offset + 4 * n_pix > row_bytes), n_cols outside [1, 4], n_pix outside
+ *   [1, 2^22], n_rows outside [1, 2^31), n_rows * row_bytes at or above 2^34 (the bound of tp_fits_datasum, which checks the table's
+ *   DATASUM), T outside [1, n_rows], t_pitch below T or no multiple of 32, a row list that is out of range or does not rise.
+ * Asynchronous on the context's stream.                                                                                        */
+int tp_tpf_unpack(tp_ctx* ctx, const void* d_table, int64_t row_bytes, int64_t n_rows, const int32_t* h_rows, int64_t T, int32_t n_cols,
+	const int64_t* h_col_offsets, int64_t n_pix, float* const* h_d_out, int64_t t_pitch);
+
 /* ---- synthetic data (bench / test utility, not part of the reference path) -----------------
  * Fill images / images_err / backgrounds cubes on the device from scene parameters, following
  * the data model of simulation/simulateFITS.py:338-405 (see photometry_amd/simulate.py).

@@ -74,6 +74,7 @@ static const char* const kKernelNames[TPK_COUNT] = {
 	"tp_fits_unpack_scalar_kernel",
 	"tp_fits_datasum_kernel",
 	"tp_fits_fold_kernel",
+	"tp_tpf_unpack_kernel",
 };
 
 extern "C" {

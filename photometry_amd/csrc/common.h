@@ -72,6 +72,7 @@ enum tp_kernel_id {
 	TPK_FITS_UNPACK_SCALAR,
 	TPK_FITS_DATASUM,
 	TPK_FITS_FOLD,
+	TPK_TPF_UNPACK,
 	TPK_COUNT
 };
 

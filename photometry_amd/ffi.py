@@ -12,8 +12,9 @@ csrc/fitsin.hip).  The FITS ``DATASUM`` of every unit is checked on the device a
 :func:`find_ffi_files` is the reference's file-name rule, :func:`read_ffi_header` what ``FFIImage`` learns from the headers,
 :func:`load_ffis` the streaming loader and :func:`prepare_ffis` the prepare stage from a list of files to a ``.tpstack``.
 
-Not covered: target pixel files, integer images (``BSCALE`` / ``BZERO``), tile-compressed FITS, the smear rows, and the time-offset
-fix of early data releases (``fixes.time_offset``: the adapter's job, see plugins.py).
+Not covered: integer images (``BSCALE`` / ``BZERO``), tile-compressed FITS, the smear rows, and the time-offset fix of early data
+releases for FFIs (``fixes.time_offset``: the adapter's job, see plugins.py; ``tpf.time_offset`` restates the rule for both data
+types).  Target pixel files have a loader of their own, ``photometry_amd.tpf``.
 """
 
 import gzip

@@ -362,7 +362,12 @@ class BasePhotometry(object):
 
 	@property
 	def aperture(self):
-		"""BasePhotometry.py:1033-1074 (FFI branch)."""
+		"""BasePhotometry.py:1033-1074: from the sum image for FFI data, the file's own APERTURE image for a target pixel file."""
+		if self._aperture is None and self.datasource.startswith('tpf') and getattr(self.source, 'aperture_image', None) is not None:
+			# :1063-1072: the crop to the current stamp, without the flags of SPOC's mask (2) and centroid pixels (8)
+			r0, c0 = self._max_stamp[0], self._max_stamp[2]
+			ap = np.array(self.source.aperture_image[self._stamp[0] - r0:self._stamp[1] - r0, self._stamp[2] - c0:self._stamp[3] - c0], dtype='int32')
+			self._aperture = ap & ~np.int32(2 | 8)
 		if self._aperture is None:
 			cols, rows = self.get_pixel_grid()
 			ap = np.asarray(np.isfinite(self.sumimage), dtype='int32')
@@ -687,14 +692,18 @@ def weightmap_hdu(weightmap, shape, cards=()):
 #--------------------------------------------------------------------------------------------------
 class _OneTargetScene(object):
 	"""Adapter: a plugin object as a batch of one for ``pipeline.ApertureBatch``."""
-	def __init__(self, pho):
-		cubes = pho._load()
+	def __init__(self, pho, device_cubes=None):
 		self.n_targets = 1
-		H, W, T = cubes['images'].shape
+		if device_cubes is None:
+			cubes = pho._load()
+			H, W, T = cubes['images'].shape
+			self.images = cubes['images'][None]
+			self.images_err = cubes['images_err'][None]
+			self.backgrounds = cubes['backgrounds'][None]
+		else:
+			# (the batch adopts the source's cubes: nothing is cut out on the host)
+			H, W, T = (getattr(device_cubes['images'], k) for k in ('height', 'width', 'n_cad'))
 		self.n_cad, self.height, self.width = T, H, W
-		self.images = cubes['images'][None]
-		self.images_err = cubes['images_err'][None]
-		self.backgrounds = cubes['backgrounds'][None]
 		self.quality = np.asarray(pho.lightcurve['quality'], dtype='int32')
 		self.time = np.asarray(pho.lightcurve['time'], dtype='float64')
 		self.stamps = np.asarray([pho._stamp], dtype='int32')
@@ -750,9 +759,26 @@ class AperturePhotometry(BasePhotometry):
 	loop around it grows the stamp while the mask touches an edge (:75-170, decisions in :mod:`photometry_amd.stamps`).
 	"""
 
+	def _device_cubes(self):
+		"""The source's own device cubes when they can stand in for the cut-out: made on this object's context, of one target, and the
+		current stamp is the whole of them (the first attempt of a ``tpf`` run, whose stamp is the whole postage stamp); else None."""
+		cubes = getattr(self.source, 'device_cubes', None)
+		if not cubes or any(cubes.get(k) is None for k in ('images', 'images_err', 'backgrounds')):
+			return None
+		im = cubes['images']
+		if any(c.ctx is not self.ctx or c.data.ptr is None for c in cubes.values()) or im.n_targets != 1 or im.n_cad != self.Ntimes:
+			return None
+		if tuple(self._stamp) != tuple(self.source.max_stamp) or (im.height, im.width) != (self._stamp[1] - self._stamp[0], self._stamp[3] - self._stamp[2]):
+			return None
+		return cubes
+
 	def _attempt(self):
 		"""One pass over the current stamp: device results of this target as a dict of host arrays."""
-		res = pipeline.run_aperture(self.ctx, _OneTargetScene(self), cubes='host', diagnostics=False)
+		cubes = self._device_cubes()
+		if cubes is not None:
+			res = pipeline.run_aperture(self.ctx, _OneTargetScene(self, device_cubes=cubes), cubes=cubes, diagnostics=False)
+		else:
+			res = pipeline.run_aperture(self.ctx, _OneTargetScene(self), cubes='host', diagnostics=False)
 		self._sumimage = res['sumimage'][0]
 		return res
 
