@@ -974,6 +974,23 @@ int tp_fits_datasum(tp_ctx* ctx, const void* d_raw, uint64_t nbytes, uint64_t* d
 int tp_tpf_unpack(tp_ctx* ctx, const void* d_table, int64_t row_bytes, int64_t n_rows, const int32_t* h_rows, int64_t T, int32_t n_cols,
 	const int64_t* h_col_offsets, int64_t n_pix, float* const* h_d_out, int64_t t_pitch);
 
+/* ---- per-stamp flag series (csrc/stampflags.hip; the rules in csrc/stampflags_rules.h) ------------------------------------------
+ * What save_lightcurve does on the host for one target -- `quality[np.any(self.pixelflags_cube & PixelQualityFlags.BackgroundShenanigans
+ * != 0, axis=(0, 1))] |= CorrectorQualityFlags.BackgroundShenanigans` (BasePhotometry.py:1445-1449) -- for every target of a batch in
+ * one launch, on the region's pixel-flag stack d_flags: uint8, n_frames frames of frame_rows x frame_cols pixels (columns fastest),
+ * frame_stride bytes from one frame to the next, covering CCD rows [row0, row0 + frame_rows) and columns [col0, col0 + frame_cols).
+ * tp_stamp_flag_series: h_stamps (HOST, [n_targets][4]: r1, r2, c1, c2 in CCD pixels, rows [r1, r2), columns [c1, c2)) are the
+ *   targets' stamps.  d_out[i * out_pitch + t] = out_value when any pixel of stamp i in frame t has `flags & flag_mask != 0`, else 0,
+ *   for t in [0, n_frames); [n_frames, out_pitch) of a row is never written.  A stamp of (-1, -1, -1, -1) -- a target without a
+ *   stamp -- gives a row of zeros.  Integers: the result is exact and the same in every run.
+ *   TP_ERR_INVALID, checked on the host before anything is queued, nothing written: a stamp that leaves the frames or has r2 <= r1 or
+ *   c2 <= c1 (other than the all -1 form), a null pointer, d_out not 4-byte aligned, flag_mask == 0, n_frames < 1, n_targets < 1,
+ *   out_pitch < n_frames, frame_stride < frame_rows * frame_cols, a frame of 2^31 pixels or more, ceil(n_frames / 16) *
+ *   ceil(n_targets / 4) at or above 2^31.
+ * Asynchronous on the context's stream; one launch per call.                                                                     */
+int tp_stamp_flag_series(tp_ctx* ctx, const uint8_t* d_flags, int32_t n_frames, int32_t frame_rows, int32_t frame_cols, int64_t frame_stride,
+	int32_t row0, int32_t col0, int32_t n_targets, const int64_t* h_stamps, uint32_t flag_mask, int32_t out_value, int32_t* d_out, int64_t out_pitch);
+
 /* ---- synthetic data (bench / test utility, not part of the reference path) -----------------
  * Fill images / images_err / backgrounds cubes on the device from scene parameters, following
  * the data model of simulation/simulateFITS.py:338-405 (see photometry_amd/simulate.py).

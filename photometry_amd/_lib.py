@@ -203,6 +203,7 @@ SIGNATURES = {
 	'tp_fits_unpack': (c_int, [c_void_p, _p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, _p, c_int64]),
 	'tp_fits_datasum': (c_int, [c_void_p, _p, c_uint64, _p]),
 	'tp_tpf_unpack': (c_int, [c_void_p, _p, c_int64, c_int64, _p, c_int64, c_int32, _p, c_int64, _p, c_int64]),
+	'tp_stamp_flag_series': (c_int, [c_void_p, _p, c_int32, c_int32, c_int32, c_int64, c_int32, c_int32, c_int32, _p, c_uint32, c_int32, _p, c_int64]),
 	'tp_synth_fill': (c_int, [c_void_p, _desc_p, c_int32, _p, _p, _p, _p, _p, c_double, c_double, c_uint64, _p, _p, _p, _p]),
 }
 

@@ -75,6 +75,7 @@ static const char* const kKernelNames[TPK_COUNT] = {
 	"tp_fits_datasum_kernel",
 	"tp_fits_fold_kernel",
 	"tp_tpf_unpack_kernel",
+	"tp_stamp_flags_kernel",
 };
 
 extern "C" {

@@ -73,6 +73,7 @@ enum tp_kernel_id {
 	TPK_FITS_DATASUM,
 	TPK_FITS_FOLD,
 	TPK_TPF_UNPACK,
+	TPK_STAMP_FLAGS,
 	TPK_COUNT
 };
 

@@ -16,6 +16,44 @@ __device__ inline double wave_max(double v) {
 	return v;
 }
 
+// numpy's pairwise add.reduce over term(0) .. term(n - 1) -- what np.nansum does once the NaNs are replaced (loops_utils.h.src) --
+// by a whole wavefront, bit for bit: a leaf of up to 128 terms keeps eight running sums, the terms 8 apart, joined as
+// ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7)), then the tail in order; above 128 terms pw(n) = pw(n2) + pw(n - n2) with
+// n2 = n / 2 rounded down to a multiple of 8.  Lane j holds running sum j mod 8 (the lanes above 7 repeat the first eight, so every
+// lane ends with the result); the recursion is an explicit stack, the same in every lane (12 levels: 128 * 2^12 terms).
+template <class Term> __device__ double wave_np_pairwise_leaf(Term&& term, int off, int n, int lane) {
+	if (n < 8) { double r = 0.0; for (int i = 0; i < n; ++i) r += term(off + i); return r; }
+	const int j = lane & 7;
+	double r = term(off + j);
+	int i = 8;
+	for (; i < n - (n % 8); i += 8) r += term(off + i + j);
+	double q[8];
+	for (int k = 0; k < 8; ++k) q[k] = __shfl(r, k, 64);
+	double res = ((q[0] + q[1]) + (q[2] + q[3])) + ((q[4] + q[5]) + (q[6] + q[7]));
+	for (; i < n; ++i) res += term(off + i);
+	return res;
+}
+template <class Term> __device__ double wave_np_pairwise_sum(Term&& term, int n, int lane) {
+	constexpr int kLevels = 12;
+	int off[kLevels], len[kLevels], state[kLevels];
+	double left[kLevels];
+	int sp = 0;
+	off[0] = 0; len[0] = n; state[0] = 0;
+	double ret = 0.0;
+	while (true) {
+		int n2 = len[sp] / 2; n2 -= n2 % 8;
+		if (state[sp] == 0) {
+			if (len[sp] > 128 && sp < kLevels - 1) { state[sp] = 1; off[sp + 1] = off[sp]; len[sp + 1] = n2; state[sp + 1] = 0; ++sp; continue; }
+			ret = wave_np_pairwise_leaf(term, off[sp], len[sp], lane);
+		} else if (state[sp] == 1) {
+			left[sp] = ret; state[sp] = 2; off[sp + 1] = off[sp] + n2; len[sp + 1] = len[sp] - n2; state[sp + 1] = 0; ++sp; continue;
+		} else ret = left[sp] + ret;
+		if (sp == 0) break;
+		--sp;
+	}
+	return ret;
+}
+
 // fixed-order block reductions (every thread gets the result)
 template <int NT> __device__ double block_sum(double v, double* red) {
 	v = wave_sum(v);

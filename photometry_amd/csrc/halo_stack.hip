@@ -240,13 +240,13 @@ __global__ __launch_bounds__(kThreads) void tp_halo_lightcurve_kernel(StackGeom 
 	const int32_t* st = stamps + 4 * i;
 	const double* wm = weightmap + q * HW;
 	const float* err = images_err + (int64_t)t * g.frame_rows * g.frame_cols;
-	double s = 0.0;
-	for (int p = lane; p < HW; p += 64) {
+	// np.nansum(wm^2 err^2) over the stamp in numpy's own order: the sum the per-target path forms on the host (halo.flux_err), bit
+	// for bit, so that a target's light-curve file is the same whichever path wrote it
+	const double s = wave_np_pairwise_sum([&](int p) {
 		const double e = (double)err[stamp_offset(g, st, p)];
 		const double term = (wm[p] * wm[p]) * (e * e);
-		if (term == term) s += term;   // nansum
-	}
-	s = wave_sum(s);
+		return term == term ? term : 0.0;   // nansum: a NaN term counts as 0
+	}, HW, lane);
 	if (lane == 0) {
 		const int r = run[q];
 		const int pos = cadpos[o];

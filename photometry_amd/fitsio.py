@@ -173,11 +173,12 @@ def bintable_hdu(name, columns, cards=()):
 	return _hdu_bytes(base, _pad(rec.tobytes()))
 
 
-def write(path, hdus):
-	"""``hdus``: list of byte strings from :func:`primary_hdu`, :func:`bintable_hdu`, :func:`image_hdu`."""
+def write(path, hdus, compresslevel=9):
+	"""``hdus``: list of byte strings from :func:`primary_hdu`, :func:`bintable_hdu`, :func:`image_hdu`.  ``compresslevel``: of a
+	``.gz`` file (9: what ``gzip.open`` uses)."""
 	blob = b''.join(hdus)
 	if str(path).endswith('.gz'):
-		with gzip.open(path, 'wb') as fh:
+		with gzip.open(path, 'wb', compresslevel=compresslevel) as fh:
 			fh.write(blob)
 	else:
 		with open(path, 'wb') as fh:

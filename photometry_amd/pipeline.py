@@ -338,7 +338,9 @@ class FrameStack(object):
 		"""``frames``: host arrays (uploaded) or float32 DeviceArrays ``(T, R, C)`` already in HBM (e.g. from ``frameio.load_stack``).
 		``sumimage`` (or ``frames['sumimage']``): the region's sum image, float64 ``(R, C)`` -- the HDF5 dataset ``sumimage`` of the
 		reference's file (prepare.py:450-453, 459; ``prepare.prepare_frames`` returns it); without one it is formed from the image
-		stack when a batch first needs it (:meth:`sumimage_for`)."""
+		stack when a batch first needs it (:meth:`sumimage_for`).  Optionally ``frames['pixel_flags']``, uint8 ``(T, R, C)`` (host array or
+		DeviceArray, as ``prepare.prepare_frames`` returns it), and ``frames['backgrounds_pixels_used']``, ``(R, C)``: kept for the
+		light-curve files (``BatchResults.save_lightcurves``), read by nothing else."""
 		from .device import DeviceArray
 		self.ctx = ctx
 		self.row0, self.col0 = int(row0), int(col0)
@@ -356,6 +358,40 @@ class FrameStack(object):
 				raise ValueError('the sum image must have the shape of a frame')
 			self._sumimage_key = 'given'
 			ctx.sync()
+		#: the pixel flags of the prepare stage, uint8 DeviceArray ``(T, R, C)`` (``pixel_flags/%04d`` of the reference's file), or None:
+		#: only the light-curve files read them (:meth:`stamp_flag_series`); they live and go with the stack
+		self.pixel_flags = None
+		#: ``backgrounds_pixels_used`` of the prepare stage, bool host image ``(R, C)``, or None (bit 4 of the files' APERTURE images)
+		self.backgrounds_pixels_used = None
+		if hasattr(frames, 'get'):
+			flags, used = frames.get('pixel_flags'), frames.get('backgrounds_pixels_used')
+			if flags is not None:
+				self.pixel_flags = flags if isinstance(flags, DeviceArray) else ctx.array(np.ascontiguousarray(flags, dtype='uint8'))
+				if tuple(self.pixel_flags.shape) != (self.n_cad, self.n_rows, self.n_cols) or self.pixel_flags.dtype != np.uint8:
+					raise ValueError('the pixel flags must be uint8 with the shape of the image stack')
+			if used is not None:
+				used = used.to_host() if isinstance(used, DeviceArray) else np.asarray(used)
+				if used.shape != (self.n_rows, self.n_cols):
+					raise ValueError('backgrounds_pixels_used must have the shape of a frame')
+				self.backgrounds_pixels_used = used.astype(bool)
+
+	def stamp_flag_series(self, stamps, flag_mask, out_value):
+		"""
+		``(N, T)`` int32 on the host: ``out_value`` where any pixel of stamp ``stamps[i]`` (``(r1, r2, c1, c2)`` in CCD pixels; all -1: no
+		stamp) carries a bit of ``flag_mask`` in frame ``t``, else 0 -- ``np.any(pixelflags_cube & flag_mask != 0, axis=(0, 1))`` of
+		save_lightcurve (BasePhotometry.py:1445-1449) for a whole batch: one launch (``tp_stamp_flag_series``), one download.  All zero
+		for a stack without pixel flags, as for a source without them (``BasePhotometry.pixelflags_cube``).
+		"""
+		st = np.ascontiguousarray(stamps, dtype='int64').reshape(-1, 4)
+		if self.pixel_flags is None or len(st) == 0:
+			return np.zeros((len(st), self.n_cad), dtype='int32')
+		ctx = self.ctx
+		out = ctx.empty((len(st), self.n_cad), 'int32')
+		ctx._check(ctx.lib.tp_stamp_flag_series(ctx.handle, self.pixel_flags.ptr, self.n_cad, self.n_rows, self.n_cols, self.n_rows * self.n_cols, self.row0, self.col0,
+			len(st), st.ctypes.data, int(flag_mask), int(out_value), out.ptr, self.n_cad))
+		host = out.to_host()
+		out.free()
+		return host
 
 	def sumimage_for(self, quality):
 		"""

@@ -34,11 +34,8 @@ DEFAULT_SETTINGS = {'todolist': {'faint_limit': '15.0'}, 'haloswitch': {'tmag_li
 	'halo': {'enabled': 'false'}, 'linpsf': {'flux_errors': 'false'}, 'psf': {'flux_errors': 'false'}}
 
 TESS_DEFAULT_BITMASK = engine.TESS_DEFAULT_BITMASK
-#: PixelQualityFlags.BackgroundShenanigans / CorrectorQualityFlags.BackgroundShenanigans (photometry/quality.py:163, :85)
-PIXEL_BACKGROUND_SHENANIGANS = 4
-#: PROCVER card of the light-curve files this package writes
-PROCVER = 'photometry_amd-0.2'
-CORRECTOR_BACKGROUND_SHENANIGANS = 256
+#: the flag values and the PROCVER card of the light-curve files, and the WEIGHTMAP table of Halo targets, live with the file writer
+from .lcfile import PIXEL_BACKGROUND_SHENANIGANS, CORRECTOR_BACKGROUND_SHENANIGANS, PROCVER, weightmap_hdu # noqa: E402,F401
 
 
 def load_settings(path=None):
@@ -369,17 +366,9 @@ class BasePhotometry(object):
 			ap = np.array(self.source.aperture_image[self._stamp[0] - r0:self._stamp[1] - r0, self._stamp[2] - c0:self._stamp[3] - c0], dtype='int32')
 			self._aperture = ap & ~np.int32(2 | 8)
 		if self._aperture is None:
-			cols, rows = self.get_pixel_grid()
-			ap = np.asarray(np.isfinite(self.sumimage), dtype='int32')
-			ap[(45 <= cols) & (cols <= 556)] |= 32
-			ap[(557 <= cols) & (cols <= 1068)] |= 64
-			ap[(1069 <= cols) & (cols <= 1580)] |= 128
-			ap[(1581 <= cols) & (cols <= 2092)] |= 256
-			bpu = getattr(self.source, 'backgrounds_pixels_used', None)
-			if bpu is not None: # pixels used for the background calculation (:1052-1061)
-				r0, c0 = self.source.max_stamp[0], self.source.max_stamp[2]
-				ap[bpu[self._stamp[0] - r0:self._stamp[1] - r0, self._stamp[2] - c0:self._stamp[3] - c0]] |= 4
-			self._aperture = ap
+			from .lcfile import ffi_aperture
+			self._aperture = ffi_aperture(self.sumimage, self._stamp, getattr(self.source, 'backgrounds_pixels_used', None),
+				self.source.max_stamp[0], self.source.max_stamp[2])
 		return self._aperture
 
 	@property
@@ -520,9 +509,7 @@ class BasePhotometry(object):
 		``WCS``, :1659-1661); a source without one gets the stamp limits written instead (``STAMP_*``).  ``DATE-OBS`` /
 		``DATE-END`` are converted from TDB by :func:`fitsio.tdb_to_utc_isot`.
 		"""
-		import datetime
-		from . import fitsio
-		from .fitsio import card
+		from . import fitsio, lcfile
 		if output_folder is None:
 			output_folder = self.output_folder
 		if version is None:
@@ -531,162 +518,20 @@ class BasePhotometry(object):
 			version = self.version
 		os.makedirs(output_folder, exist_ok=True)
 		cadence = int(self.cadence) if self.cadence else 1800
-		data_rel = int(self.data_rel or 0)
-		SumImage = np.asarray(self.sumimage, dtype='float64')
 		lc = self.lightcurve
 		# Background Shenanigans anywhere in the stamp at a timestamp -> CorrectorQualityFlags.BackgroundShenanigans (:1445-1449)
 		quality = np.zeros(len(lc['time']), dtype='int32')
 		quality[np.any(self.pixelflags_cube & PIXEL_BACKGROUND_SHENANIGANS != 0, axis=(0, 1))] |= CORRECTOR_BACKGROUND_SHENANIGANS
-		# timestamps without a defined time are dropped (:1451-1452); upstream leaves QUALITY at its full length there, which no
-		# table can hold -- it is cut to the same rows here
-		indx = np.isfinite(lc['time'])
-		quality = quality[indx]
-		col = {k: np.asarray(lc[k])[indx] for k in lc.keys()}
-		tgt = self.target
-		undef = fitsio.Undefined()
-
-		def opt(key): # "undefined" card for a missing or zero value, as upstream writes it (:1487-1490)
-			v = tgt.get(key)
-			return undef if not v else v
-		if tgt.get('pm_ra') is None or tgt.get('pm_decl') is None:
-			pmtotal = undef
-		else:
-			pmtotal = np.sqrt(tgt['pm_ra']**2 + tgt['pm_decl']**2)
-		hdr = self.header
-		prim = [
-			card('NEXTEND', 3 + int(getattr(self, 'halo_weightmap', None) is not None), 'number of standard extensions'), card('EXTNAME', 'PRIMARY', 'name of extension'),
-			card('ORIGIN', 'TASOC/Aarhus', 'institution responsible for creating this file'),
-			card('DATE', datetime.datetime.now().strftime("%Y-%m-%d"), 'date the file was created'),
-			card('TELESCOP', 'TESS', 'telescope'), card('INSTRUME', 'TESS Photometer', 'detector type'),
-			card('FILTER', 'TESS', 'Photometric bandpass filter'), card('OBJECT', f"TIC {self.starid:d}", 'string version of TICID'),
-			card('TICID', int(self.starid), 'unique TESS target identifier'), card('CAMERA', int(self.camera), 'Camera number'),
-			card('CCD', int(self.ccd), 'CCD number'), card('SECTOR', int(self.sector), 'Observing sector'),
-			card('PROCVER', PROCVER, 'Version of photometry pipeline'), card('FILEVER', '1.5', 'File format version'),
-			card('DATA_REL', self.data_rel, 'Data release number'), card('VERSION', int(version), 'Version of the processing'),
-			card('PHOTMET', self.method, 'Photometric method used'),
-			card('RADESYS', 'ICRS', 'reference frame of celestial coordinates'), card('EQUINOX', 2000.0, 'equinox of celestial coordinate system'),
-			card('RA_OBJ', tgt.get('ra_J2000'), '[deg] Right ascension'), card('DEC_OBJ', tgt.get('decl_J2000'), '[deg] Declination'),
-			card('PMRA', opt('pm_ra'), '[mas/yr] RA proper motion'), card('PMDEC', opt('pm_decl'), '[mas/yr] Dec proper motion'),
-			card('PMTOTAL', pmtotal, '[mas/yr] total proper motion'),
-			card('TESSMAG', float(tgt['tmag']), '[mag] TESS magnitude'), card('TEFF', opt('teff'), '[K] Effective temperature'),
-			card('TICVER', self.ticver, 'TESS Input Catalog version'),
-			card('CRMITEN', hdr.get('CRMITEN'), 'spacecraft cosmic ray mitigation enabled'),
-			card('CRBLKSZ', hdr.get('CRBLKSZ'), '[exposures] s/c cosmic ray mitigation block siz'),
-			card('CRSPOC', hdr.get('CRSPOC'), 'SPOC cosmic ray cleaning enabled'),
-		]
-		for key, value in self.additional_headers.items(): # K2P2 settings, AP_CONT, ... (:1497-1499)
-			if isinstance(value, (tuple, list)):
-				prim.append(card(key, value[0], value[1] if len(value) > 1 else None))
-			else:
-				prim.append(card(key, value))
-		prim.append(card('DATAVAL', 0, 'Data validation flags'))
-
-		n = len(col['time'])
-		nan = np.full(n, np.nan)
-		f64 = 'column format: 64-bit floating point'
-		i32 = 'column format: signed 32-bit integer'
-		disp = 'column display format'
-
-		def column(name, fmt, arr, unit=None, dsp=None, title=None, unitc=None):
-			return {'name': name, 'format': fmt, 'array': arr, 'unit': unit, 'disp': dsp,
-				'comments': {'TTYPE': title, 'TFORM': f64 if fmt == 'D' else ('column format: 32-bit floating point' if fmt == 'E' else i32),
-					'TUNIT': unitc, 'TDISP': disp}}
-		columns = [
-			column('TIME', 'D', col['time'], 'BJD - 2457000, days', 'D14.7', 'column title: data time stamps', 'column units: Barycenter corrected TESS Julian'),
-			column('TIMECORR', 'E', col['timecorr'], 'd', 'E13.6', 'column title: barycenter - timeslice correction', 'column units: day'),
-			column('CADENCENO', 'J', col['cadenceno'], None, 'I10', 'column title: unique cadence number'),
-			column('FLUX_RAW', 'D', col['flux'], 'e-/s', 'E26.17', 'column title: photometric flux', 'column units: electrons per second'),
-			column('FLUX_RAW_ERR', 'D', col['flux_err'], 'e-/s', 'E26.17', 'column title: photometric flux error', 'column units: electrons per second'),
-			column('FLUX_BKG', 'D', col['flux_background'], 'e-/s', 'E26.17', 'column title: photometric background flux', 'column units: electrons per second'),
-			column('FLUX_CORR', 'D', nan, 'ppm', 'E26.17', 'column title: corrected photometric flux', 'column units: rel. flux in parts-per-million'),
-			column('FLUX_CORR_ERR', 'D', nan, 'ppm', 'E26.17', 'column title: corrected photometric flux error', 'column units: parts-per-million'),
-			column('QUALITY', 'J', quality, None, 'B16.16', 'column title: photometry quality flags'),
-			column('PIXEL_QUALITY', 'J', col['quality'], None, 'B16.16', 'column title: pixel quality flags'),
-			column('MOM_CENTR1', 'D', col['pos_centroid'][:, 0], 'pixels', 'F10.5', 'column title: moment-derived column centroid', 'column units: pixels'),
-			column('MOM_CENTR2', 'D', col['pos_centroid'][:, 1], 'pixels', 'F10.5', 'column title: moment-derived row centroid', 'column units: pixels'),
-			column('POS_CORR1', 'D', col['pos_corr'][:, 0], 'pixels', 'F14.7', 'column title: column position correction', 'column units: pixels'),
-			column('POS_CORR2', 'D', col['pos_corr'][:, 1], 'pixels', 'F14.7', 'column title: row position correction', 'column units: pixels'),
-		]
-		# time keywords (:1602-1641)
-		tdel = cadence / 86400
-		tstart = float(col['time'][0] - tdel/2) if n else float('nan')
-		tstop = float(col['time'][-1] + tdel/2) if n else float('nan')
-		telapse = tstop - tstart
-		frametime, int_time, readtime = 2.0, 1.98, 0.02
-		if hdr.get('CRMITEN'):
-			crblocksize = hdr['CRBLKSZ']
-			deadc = (int_time * (crblocksize-2)/crblocksize) / frametime
-		else:
-			deadc = int_time / frametime
-		num_frm = self.num_frm
-		bjdref = 2457000
-		tcards = [
-			card('INHERIT', True, 'inherit the primary header'),
-			card('TIMEREF', 'SOLARSYSTEM', 'barycentric correction applied to times'),
-			card('TIMESYS', 'TDB', 'time system is Barycentric Dynamical Time (TDB)'),
-			card('BJDREFI', bjdref, 'integer part of BTJD reference date'), card('BJDREFF', 0.0, 'fraction of the day in BTJD reference date'),
-			card('TIMEUNIT', 'd', 'time unit for TIME, TSTART and TSTOP'),
-			card('TSTART', tstart, 'observation start time in BTJD'), card('TSTOP', tstop, 'observation stop time in BTJD'),
-			card('DATE-OBS', fitsio.tdb_to_utc_isot(tstart, bjdref) if n else None, 'TSTART as UTC calendar date'),
-			card('DATE-END', fitsio.tdb_to_utc_isot(tstop, bjdref) if n else None, 'TSTOP as UTC calendar date'),
-			card('MJD-BEG', tstart + (bjdref - 2400000.5), 'observation start time in MJD'),
-			card('MJD-END', tstop + (bjdref - 2400000.5), 'observation start time in MJD'),
-			card('TELAPSE', telapse, '[d] TSTOP - TSTART'), card('LIVETIME', telapse*deadc, '[d] TELAPSE multiplied by DEADC'),
-			card('DEADC', deadc, 'deadtime correction'), card('EXPOSURE', telapse*deadc, '[d] time on source'),
-			card('XPOSURE', frametime*deadc*num_frm, '[s] Duration of exposure'),
-			card('TIMEPIXR', 0.5, 'bin time beginning=0 middle=0.5 end=1'), card('TIMEDEL', tdel, '[d] time resolution of data'),
-			card('INT_TIME', int_time, '[s] photon accumulation time per frame'), card('READTIME', readtime, '[s] readout time per frame'),
-			card('FRAMETIM', frametime, '[s] frame time (INT_TIME + READTIME)'), card('NUM_FRM', num_frm, 'number of frames per time stamp'),
-			card('NREADOUT', int(self.n_readout), 'number of read per cadence'),
-		]
-		mask = np.array(self.aperture, dtype='int32', copy=True) # :1643-1649
-		if self.final_phot_mask is not None:
-			mask[self.final_phot_mask] |= 2
-		if self.final_position_mask is not None:
-			mask[self.final_position_mask] |= 8
-		# image extensions: the WCS of the stamp (:1651-1661) when the source has one, then INHERIT
-		wcs_header = getattr(self.source, 'wcs_header', None)
-		if wcs_header is not None:
-			icards = [card(*c) for c in wcs_header(self._stamp)]
-		else:
-			icards = [card('STAMP_R1', int(self._stamp[0]), 'first CCD row of the stamp'), card('STAMP_R2', int(self._stamp[1]), 'last CCD row + 1'),
-				card('STAMP_C1', int(self._stamp[2]), 'first CCD column of the stamp'), card('STAMP_C2', int(self._stamp[3]), 'last CCD column + 1')]
-		icards.append(card('INHERIT', True, 'inherit the primary header'))
-		fname = (f'tess{self.starid:011d}-s{int(self.sector):03d}-{int(self.camera):d}-{int(self.ccd):d}-c{cadence:04d}'
-			f'-dr{data_rel:02d}-v{int(version):02d}-tasoc_lc.fits.gz')
-		path = os.path.join(output_folder, fname)
-		hdus = [fitsio.primary_hdu(prim), fitsio.bintable_hdu('LIGHTCURVE', columns, tcards),
-			fitsio.image_hdu('SUMIMAGE', SumImage, icards), fitsio.image_hdu('APERTURE', mask, icards)]
-		if getattr(self, 'halo_weightmap', None) is not None:
-			hdus.append(weightmap_hdu(self.halo_weightmap, SumImage.shape, icards))
+		# the aperture image with bits 2 (photometry) and 8 (position) (:1643-1649); the WCS of the stamp when the source has one (:1651-1661)
+		mask = lcfile.aperture_with_masks(self.aperture, self.final_phot_mask, self.final_position_mask)
+		icards = lcfile.image_cards(self._stamp, getattr(self.source, 'wcs_header', None))
+		hdus = lcfile.lightcurve_hdus(self.target, self.starid, self.sector, self.camera, self.ccd, cadence, self.data_rel, version, self.method, self.ticver,
+			self.header, self.num_frm, self.n_readout, self.additional_headers, {k: lc[k] for k in lc.keys()}, quality, self.sumimage, mask, icards,
+			weightmap=getattr(self, 'halo_weightmap', None))
+		path = os.path.join(output_folder, lcfile.lightcurve_filename(self.starid, self.sector, self.camera, self.ccd, cadence, self.data_rel, version))
 		fitsio.write(path, hdus)
-		# relative to the input folder when the output lies inside it, else to the base output folder (:1722-1726)
-		base = self.output_folder_base
-		inp = self.input_folder if isinstance(self.input_folder, (str, bytes, os.PathLike)) else None
-		if inp is not None and os.path.realpath(output_folder).startswith(os.path.realpath(inp)):
-			base = os.path.abspath(inp)
-		self._details['filepath_lightcurve'] = os.path.relpath(path, base).replace('\\', '/')
+		self._details['filepath_lightcurve'] = lcfile.relative_filepath(path, output_folder, self.output_folder_base, self.input_folder)
 		return path
-
-
-def weightmap_hdu(weightmap, shape, cards=()):
-	"""The ``WEIGHTMAP`` binary table of Halo photometry (BasePhotometry.py:1673-1706): one row per segment."""
-	from . import fitsio
-	npx = int(np.prod(shape))
-	i32, disp = 'column format: signed 32-bit integer', 'column display format'
-	wms = np.asarray(weightmap['weightmap'], dtype='float32').reshape(-1, shape[0], shape[1])
-	columns = [
-		{'name': 'CADENCENO1', 'format': 'J', 'array': np.asarray(weightmap['initial_cadence'], dtype='int32'), 'disp': 'I10',
-			'comments': {'TTYPE': 'column title: first cadence number', 'TFORM': i32, 'TDISP': disp}},
-		{'name': 'CADENCENO2', 'format': 'J', 'array': np.asarray(weightmap['final_cadence'], dtype='int32'), 'disp': 'I10',
-			'comments': {'TTYPE': 'column title: last cadence number', 'TFORM': i32, 'TDISP': disp}},
-		{'name': 'SAT_PIXELS', 'format': 'J', 'array': np.asarray(weightmap['sat_pixels'], dtype='int32'), 'disp': 'I10',
-			'comments': {'TTYPE': 'column title: Saturated pixels', 'TFORM': i32, 'TDISP': disp}},
-		{'name': 'WEIGHTMAP', 'format': f'{npx:d}E', 'array': wms, 'disp': 'E14.7', 'dim': (int(shape[1]), int(shape[0])),
-			'comments': {'TTYPE': 'column title: Weightmap', 'TFORM': 'column format: image of 32-bit floating point', 'TDISP': disp,
-				'TDIM': 'column dimensions: pixel aperture array'}},
-	]
-	return fitsio.bintable_hdu('WEIGHTMAP', columns, cards)
 
 
 #--------------------------------------------------------------------------------------------------

@@ -203,9 +203,34 @@ class BatchResults(object):
 		#: ``(N, T, 2)`` changes in column and row of every target's position (``lightcurve['pos_corr']``, BasePhotometry.py:473) when
 		#: the entry was given movement kernels, else None
 		self.pos_corr = None
+		#: the stack and the ``targets`` dict the batch was run over (set by :func:`tessphot_frames`): what :meth:`save_lightcurves` reads
+		#: the pixel flags, the sum image and ``tmag`` from.  The results keep the stack, and its HBM, alive.
+		self.stack = self.targets = None
+		#: path of every target's light-curve file once :meth:`save_lightcurves` has run (``None``: no file), else None
+		self.filepaths = None
+		self._filepath_rel = {}
 
 	def __len__(self):
 		return len(self.frames)
+
+	def save_lightcurves(self, output_folder, info, time, quality, version, *, timecorr=None, cadenceno=None, targets=None, workers=None, compresslevel=9):
+		"""
+		Write ``tess…-tasoc_lc.fits.gz`` for every target whose final status is OK or WARNING (the rule of :func:`run_plugin`): the file
+		``tessphot('aperture', ...)`` -- or, for a target switched to Halo photometry, ``tessphot(None, ...)`` -- writes for it, into
+		``output_folder`` under the reference's name (:mod:`photometry_amd.lcfile`).  ``info``: a :class:`~photometry_amd.lcfile.FileInfo`;
+		``time`` / ``quality`` / ``timecorr`` / ``cadenceno``: the shared vectors of the batch (``TIME``, ``PIXEL_QUALITY``, ``TIMECORR``,
+		``CADENCENO``; rows without a finite time are dropped from every column); ``targets``: the batch's ``targets`` dict (default: the
+		one the entry was called with), which may carry the catalogue columns ``ra_J2000, decl_J2000, pm_ra, pm_decl, teff``.
+		``QUALITY`` comes from the stack's pixel flags over the final stamps of the whole batch in one launch (all zero for a stack
+		without flags).  ``workers`` threads (default ``min(16, os.cpu_count())``, never more than 16) build and compress the files;
+		``compresslevel`` is gzip's (9: what the per-target plugin writes with).  Returns the paths, ``None`` where no file was written
+		(also ``self.filepaths``); ``results[i]._details['filepath_lightcurve']`` is set as the plugin sets it.
+		"""
+		from . import lcfile
+		if self.stack is None:
+			raise ValueError("these results do not know their frame stack: run the batch through tessphot_frames")
+		return lcfile.save_lightcurves(self, self.stack, output_folder, info, time, quality, version, timecorr=timecorr, cadenceno=cadenceno,
+			targets=self.targets if targets is None else targets, workers=workers, compresslevel=compresslevel)
 
 	def edge_flux_column(self):
 		"""``details['edge_flux']`` of every target as a column (NaN: none): the flux on the stuck edge of the haloswitch quick break,
@@ -267,6 +292,8 @@ class BatchResults(object):
 		details['errors'] = errors + ['Automatically switched to Halo photometry']
 		ef = self._aperture_edge_flux[i]
 		details['edge_flux'] = None if np.isnan(ef) else float(ef)
+		if i in self._filepath_rel:
+			details['filepath_lightcurve'] = self._filepath_rel[i]
 		out = BatchResult(int(self.starid[i]), status, 'halo', details, lc, mask)
 		out.halo_weightmap = r['weightmap']
 		return out
@@ -309,6 +336,10 @@ class BatchResults(object):
 				lc['pos_corr'] = self.pos_corr[int(i)]
 			if status in (STATUS.OK, STATUS.WARNING):
 				status = _diagnostics_into(details, r['diagnostics'], status)
+		if self._filepath_rel:
+			k = int(i) + len(self) if int(i) < 0 else int(i)
+			if k in self._filepath_rel:
+				details['filepath_lightcurve'] = self._filepath_rel[k]
 		return BatchResult(int(self.starid[int(i)]), status, 'aperture', details, lc, mask)
 
 	def __iter__(self):
@@ -343,7 +374,20 @@ def _pos_corr(ctx, movement, targets, time, timecorr):
 	return movement.jitter_many(t, targets['column'], targets['row']).to_host()
 
 
-def tessphot_frames(ctx, stack, targets, catalog, time, quality, settings=None, sector=None, timecorr=None, cadenceno=None, movement=None):
+def _finish_batch(ctx, out, stack, targets, time, quality, timecorr, cadenceno, movement, output_folder, fileinfo, version):
+	"""What both batched entries do with a batch after the method switch: ``pos_corr``, the stack and targets, the files when asked for."""
+	if movement is not None:
+		out.pos_corr = _pos_corr(ctx, movement, targets, time, timecorr)
+	out.stack, out.targets = stack, targets
+	if output_folder is not None:
+		if fileinfo is None:
+			raise ValueError("output_folder needs fileinfo (a photometry_amd.lcfile.FileInfo)")
+		out.save_lightcurves(output_folder, fileinfo, time, quality, version, timecorr=timecorr, cadenceno=cadenceno)
+	return out
+
+
+def tessphot_frames(ctx, stack, targets, catalog, time, quality, settings=None, sector=None, timecorr=None, cadenceno=None, movement=None,
+	output_folder=None, fileinfo=None, version=None):
 	"""
 	Aperture photometry of every target of a CCD region resident in HBM (:class:`photometry_amd.pipeline.FrameStack`), stamp
 	resizes included: what ``tessphot('aperture', ...)`` returns per target, for the whole batch in a few device passes.
@@ -353,24 +397,25 @@ def tessphot_frames(ctx, stack, targets, catalog, time, quality, settings=None, 
 	(``method == 'halo'``, ``halo_weightmap``).
 	``movement``: a :class:`~photometry_amd.motion.MovementKernel` with a loaded series: ``BatchResults.pos_corr`` and every light
 	curve's ``'pos_corr'`` are then its jitter at the targets' positions at ``time - timecorr``, as the plugins write it.
+	``output_folder`` with ``fileinfo`` (a :class:`~photometry_amd.lcfile.FileInfo`) and ``version``: the light-curve files of the batch
+	are written as well (:meth:`BatchResults.save_lightcurves`), as ``run_plugin`` writes them per target.
 	Returns a :class:`BatchResults`: columns for the whole batch, one :class:`BatchResult` per target on demand (``results[i]``).
 	"""
 	from . import pipeline
 	res = pipeline.aperture_frames(ctx, stack, targets, catalog, time, quality, settings=settings)
 	out = _halo_switch_frames(ctx, stack, BatchResults(res, targets['starid']), targets, catalog, time, quality, settings, sector, timecorr, cadenceno)
-	if movement is not None:
-		out.pos_corr = _pos_corr(ctx, movement, targets, time, timecorr)
-	return out
+	return _finish_batch(ctx, out, stack, targets, time, quality, timecorr, cadenceno, movement, output_folder, fileinfo, version)
 
 
 def tessphot_frames_pipelined(ctx, stack, batches, catalog, time, quality, settings=None, in_flight=4, sector=None, timecorr=None, cadenceno=None,
-	movement=None):
+	movement=None, output_folder=None, fileinfo=None, version=None):
 	"""
 	:func:`tessphot_frames` over consecutive batches of targets of one CCD region -- what a run over a whole CCD does, a few
 	thousand targets per call -- with ``in_flight`` batches on the device at a time (``pipeline.aperture_frames_pipelined``: the
 	first round of a batch runs under the latency-bound resize rounds of the one before it).  ``batches``: an iterable of
 	``targets`` dicts; yields one :class:`BatchResults` per batch, in order, equal to what a call of its own returns (the switch to
-	Halo photometry included, applied to each batch before it is yielded; ``movement`` as there).
+	Halo photometry included, applied to each batch before it is yielded; ``movement`` as there; with ``output_folder`` / ``fileinfo`` /
+	``version`` the files of each batch are written as it is collected).
 	"""
 	from . import pipeline
 	batches = list(batches) if not hasattr(batches, '__next__') else batches
@@ -381,9 +426,7 @@ def tessphot_frames_pipelined(ctx, stack, batches, catalog, time, quality, setti
 			yield t
 	for k, res in enumerate(pipeline.aperture_frames_pipelined(ctx, stack, feed(), catalog, time, quality, settings=settings, in_flight=in_flight)):
 		out = _halo_switch_frames(ctx, stack, BatchResults(res, seen[k]['starid']), seen[k], catalog, time, quality, settings, sector, timecorr, cadenceno)
-		if movement is not None:
-			out.pos_corr = _pos_corr(ctx, movement, seen[k], time, timecorr)
-		yield out
+		yield _finish_batch(ctx, out, stack, seen[k], time, quality, timecorr, cadenceno, movement, output_folder, fileinfo, version)
 
 
 def tessphot_batch(ctx, scene, cubes='host'):
