@@ -74,6 +74,9 @@ int tp_ctx_create_stream(int device, int high_priority, tp_ctx** out);
 int tp_ctx_destroy(tp_ctx* ctx);
 const char* tp_last_error(tp_ctx* ctx);      /* ctx may be NULL: last tp_ctx_create failure */
 int tp_device_info(tp_ctx* ctx, char* name, int name_len, int32_t* n_cu, uint64_t* hbm_bytes);
+/* Free and total device memory as the driver counts them (either pointer may be NULL).  Blocks in the allocation cache of a context
+ * (see tp_malloc) count as used: the figure is a lower bound of what the next allocations can get. */
+int tp_mem_info(tp_ctx* ctx, uint64_t* free_bytes, uint64_t* total_bytes);
 /* NUMA node of the device's PCIe slot (-1: unknown), for binding the host threads that feed it (device.bind_host_to_device). */
 int tp_device_numa_node(int device, int* node);
 
@@ -637,6 +640,16 @@ int tp_psf_flux_err(tp_ctx* ctx, const tp_cube_desc* desc, const float* d_images
 int tp_lightcurve_diagnostics(tp_ctx* ctx, int32_t n_targets, int32_t n_cad,
 	const double* d_flux, const double* d_flux_err, const double* d_centroid_col, const double* d_centroid_row, int64_t lc_pitch,
 	const double* d_time, const int32_t* d_quality, int64_t quality_target_stride, uint32_t bitmask,
+	const int32_t* d_status, const double* d_sumimage, const uint8_t* d_mask, int32_t height, int32_t width,
+	double timescale_days, double* d_diag);
+/* The same with a time vector per target (light curves of target pixel files: TIME is barycentric per target, so the files of a
+ * group share their length and nothing else).  time_target_stride == 0: d_time is float64 [n_cad], shared -- tp_lightcurve_diagnostics
+ * is this call.  Otherwise (in doubles, >= n_cad) target i reads d_time + i * time_target_stride.  A negative stride or one in
+ * (0, n_cad) is TP_ERR_INVALID and nothing is written.  Same kernel, same launch, both residencies of the series (LDS / HBM
+ * scratch): row i of a strided call has the bits of the shared-time call on target i alone with its own time vector.            */
+int tp_lightcurve_diagnostics_times(tp_ctx* ctx, int32_t n_targets, int32_t n_cad,
+	const double* d_flux, const double* d_flux_err, const double* d_centroid_col, const double* d_centroid_row, int64_t lc_pitch,
+	const double* d_time, int64_t time_target_stride, const int32_t* d_quality, int64_t quality_target_stride, uint32_t bitmask,
 	const int32_t* d_status, const double* d_sumimage, const uint8_t* d_mask, int32_t height, int32_t width,
 	double timescale_days, double* d_diag);
 

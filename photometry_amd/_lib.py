@@ -64,6 +64,7 @@ SIGNATURES = {
 	'tp_ctx_destroy': (c_int, [c_void_p]),
 	'tp_last_error': (c_char_p, [c_void_p]),
 	'tp_device_info': (c_int, [c_void_p, c_char_p, c_int, POINTER(c_int32), POINTER(c_uint64)]),
+	'tp_mem_info': (c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64)]),
 	'tp_device_numa_node': (c_int, [c_int, POINTER(c_int)]),
 	'tp_malloc': (c_int, [c_void_p, c_uint64, POINTER(c_void_p)]),
 	'tp_free': (c_int, [c_void_p, _p]),
@@ -151,7 +152,9 @@ SIGNATURES = {
 		_p, _p, _p, _p, c_int64, _p, _p, _p]),
 	'tp_lightcurve_diagnostics': (c_int, [c_void_p, c_int32, c_int32, _p, _p, _p, _p, c_int64, _p, _p, c_int64, c_uint32,
 		_p, _p, _p, c_int32, c_int32, c_double, _p]),
-	'tp_cut_stamps': (c_int, [c_void_p, _p, c_int32, c_int32, c_int32, c_int64, c_int64, c_int32, c_int32, _p, _desc_p, _p]),
+	'tp_lightcurve_diagnostics_times': (c_int, [c_void_p, c_int32, c_int32, _p, _p, _p, _p, c_int64, _p, c_int64, _p, c_int64, c_uint32,
+		_p, _p, _p, c_int32, c_int32, c_double, _p]),
+	'tp_cut_stamps':(c_int, [c_void_p, _p, c_int32, c_int32, c_int32, c_int64, c_int64, c_int32, c_int32, _p, _desc_p, _p]),
 	'tp_comm_unique_id': (c_int, [c_char_p, c_int]),
 	'tp_comm_init': (c_int, [c_void_p, c_char_p, c_int, c_int, c_int]),
 	'tp_comm_destroy': (c_int, [c_void_p]),

@@ -211,6 +211,15 @@ int tp_device_info(tp_ctx* ctx, char* name, int name_len, int32_t* n_cu, uint64_
 	return TP_OK;
 }
 
+int tp_mem_info(tp_ctx* ctx, uint64_t* free_bytes, uint64_t* total_bytes) {
+	TP_CHECK_CTX(ctx);
+	size_t f = 0, t = 0;
+	TP_HIP(ctx, hipMemGetInfo(&f, &t));
+	if (free_bytes) *free_bytes = (uint64_t)f;
+	if (total_bytes) *total_bytes = (uint64_t)t;
+	return TP_OK;
+}
+
 // NUMA node of the device's PCIe slot (sysfs), -1 when unknown: the host threads that feed a GPU and the page-locked buffers it
 // copies into are best kept on that node's cores (a process whose threads float over both sockets of a two-socket host ran the
 // batched frames entry in 20 ms instead of 13, a third of its starts)

@@ -30,7 +30,7 @@ constexpr int kThreads = 256;
 
 struct DiagArgs {
 	const double* flux; const double* flux_err; const double* ccol; const double* crow; int64_t lc_pitch;
-	const double* time; const int32_t* quality; int64_t quality_stride; uint32_t bitmask;
+	const double* time; int64_t time_stride; const int32_t* quality; int64_t quality_stride; uint32_t bitmask;
 	const int32_t* status; const double* sumimage; const uint8_t* mask; int height, width;
 	int n_cad; int tp2; double timescale; double* out;
 	unsigned char* gscratch; size_t gscratch_per_target; // series arrays in HBM when they do not fit the LDS (long light curves)
@@ -283,7 +283,7 @@ __global__ __launch_bounds__(kThreads) void tp_diagnostics_kernel(DiagArgs a)
 	const double ainv = fabs(1.0 / mean_flux);
 	for (int g = tid; g < Ng; g += kThreads) gflux[g] = (flux[gk[g]] / mean_flux) - 1.0;
 	__syncthreads();
-	const double* tptr = a.time;
+	const double* tptr = a.time + (int64_t)target * a.time_stride; // stride 0: one time vector for the launch
 	auto gtime_at = [&](int g) { return tptr[gk[g]]; };
 	auto gerr_at = [&](int g) { return ainv * ferr[gk[g]]; };
 
@@ -484,9 +484,9 @@ __global__ __launch_bounds__(kThreads) void tp_diagnostics_kernel(DiagArgs a)
 
 } // namespace
 
-extern "C" int tp_lightcurve_diagnostics(tp_ctx* ctx, int32_t n_targets, int32_t n_cad,
+extern "C" int tp_lightcurve_diagnostics_times(tp_ctx* ctx, int32_t n_targets, int32_t n_cad,
 	const double* d_flux, const double* d_flux_err, const double* d_centroid_col, const double* d_centroid_row, int64_t lc_pitch,
-	const double* d_time, const int32_t* d_quality, int64_t quality_target_stride, uint32_t bitmask,
+	const double* d_time, int64_t time_target_stride, const int32_t* d_quality, int64_t quality_target_stride, uint32_t bitmask,
 	const int32_t* d_status, const double* d_sumimage, const uint8_t* d_mask, int32_t height, int32_t width,
 	double timescale_days, double* d_diag)
 {
@@ -495,6 +495,8 @@ extern "C" int tp_lightcurve_diagnostics(tp_ctx* ctx, int32_t n_targets, int32_t
 	TP_REQUIRE(ctx, n_targets >= 0 && n_cad > 0, "tp_lightcurve_diagnostics: bad sizes");
 	TP_REQUIRE(ctx, d_flux && d_flux_err && d_centroid_col && d_centroid_row && d_time && d_quality && d_diag, "tp_lightcurve_diagnostics: null pointer");
 	TP_REQUIRE(ctx, lc_pitch >= n_cad, "tp_lightcurve_diagnostics: lc_pitch < n_cad");
+	TP_REQUIRE(ctx, time_target_stride >= 0, "tp_lightcurve_diagnostics: negative time stride");
+	TP_REQUIRE(ctx, time_target_stride == 0 || time_target_stride >= n_cad, "tp_lightcurve_diagnostics: time stride < n_cad");
 	TP_REQUIRE(ctx, quality_target_stride == 0 || quality_target_stride >= n_cad, "tp_lightcurve_diagnostics: bad quality stride");
 	TP_REQUIRE(ctx, (d_mask == nullptr) == (d_sumimage == nullptr), "tp_lightcurve_diagnostics: mask and sum image go together");
 	TP_REQUIRE(ctx, d_mask == nullptr || (height > 0 && width > 0 && (int64_t)height * width <= 2147483647ll), "tp_lightcurve_diagnostics: bad stamp geometry");
@@ -514,7 +516,7 @@ extern "C" int tp_lightcurve_diagnostics(tp_ctx* ctx, int32_t n_targets, int32_t
 	}
 	DiagArgs a;
 	a.flux = d_flux; a.flux_err = d_flux_err; a.ccol = d_centroid_col; a.crow = d_centroid_row; a.lc_pitch = lc_pitch;
-	a.time = d_time; a.quality = d_quality; a.quality_stride = quality_target_stride; a.bitmask = bitmask;
+	a.time = d_time; a.time_stride = time_target_stride; a.quality = d_quality; a.quality_stride = quality_target_stride; a.bitmask = bitmask;
 	a.status = d_status; a.sumimage = d_sumimage; a.mask = d_mask; a.height = height; a.width = width;
 	a.n_cad = n_cad; a.tp2 = tp2; a.timescale = timescale_days; a.out = d_diag;
 	a.gscratch = gscratch; a.gscratch_per_target = series_bytes;
@@ -524,4 +526,14 @@ extern "C" int tp_lightcurve_diagnostics(tp_ctx* ctx, int32_t n_targets, int32_t
 	TP_LAUNCH_CHECK(ctx, "tp_diagnostics_kernel");
 	return TP_OK;
 	TP_API_END(ctx)
+}
+
+extern "C" int tp_lightcurve_diagnostics(tp_ctx* ctx, int32_t n_targets, int32_t n_cad,
+	const double* d_flux, const double* d_flux_err, const double* d_centroid_col, const double* d_centroid_row, int64_t lc_pitch,
+	const double* d_time, const int32_t* d_quality, int64_t quality_target_stride, uint32_t bitmask,
+	const int32_t* d_status, const double* d_sumimage, const uint8_t* d_mask, int32_t height, int32_t width,
+	double timescale_days, double* d_diag)
+{
+	return tp_lightcurve_diagnostics_times(ctx, n_targets, n_cad, d_flux, d_flux_err, d_centroid_col, d_centroid_row, lc_pitch, d_time, 0,
+		d_quality, quality_target_stride, bitmask, d_status, d_sumimage, d_mask, height, width, timescale_days, d_diag);
 }

@@ -269,6 +269,12 @@ class Context(object):
 		self._check(self.lib.tp_device_info(self.handle, name, 256, ctypes.byref(ncu), ctypes.byref(hbm)))
 		return {'name': name.value.decode(), 'n_cu': ncu.value, 'hbm_bytes': hbm.value}
 
+	def mem_info(self):
+		"""``(free, total)`` bytes of device memory as the driver counts them (blocks in the allocation cache count as used)."""
+		free, total = ctypes.c_uint64(), ctypes.c_uint64()
+		self._check(self.lib.tp_mem_info(self.handle, ctypes.byref(free), ctypes.byref(total)))
+		return int(free.value), int(total.value)
+
 	# -- allocation helpers ------------------------------------------------------------------
 	def empty(self, shape, dtype):
 		return DeviceArray(self, shape, dtype)

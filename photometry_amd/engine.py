@@ -263,7 +263,8 @@ def lightcurve_diagnostics(ctx, lc, time, quality, status=None, sumimage=None, m
 	timescale=3600/86400, out=None):
 	"""
 	Light-curve diagnostics of a batch (BasePhotometry.py:1343-1407, utilities.py:227-264).
-	``lc``: :class:`LightCurves`; ``time``: float64 DeviceArray ``(T,)``; ``quality`` as in :func:`sumimage`.
+	``lc``: :class:`LightCurves`; ``time``: float64 DeviceArray ``(T,)``, or ``(Nt, T)`` with one row per target (target pixel files:
+	``tp_lightcurve_diagnostics_times``); ``quality`` as in :func:`sumimage`.
 	Returns float64 DeviceArray ``(Nt, 10)`` with the columns :data:`DIAGNOSTICS_COLUMNS`.
 	``flags`` is a sum of the bits 1 (all fluxes NaN), 2 (all errors NaN), 4 (invalid time vector, or samples but no finite one:
 	``rms_hour`` is NaN), 8 (no detrending: ``detrend = 0`` in ``variability``) and 16 (device only: more ``timescale`` bins than
@@ -276,8 +277,14 @@ def lightcurve_diagnostics(ctx, lc, time, quality, status=None, sumimage=None, m
 	H = W = 0
 	if mask is not None:
 		H, W = int(mask.shape[1]), int(mask.shape[2])
-	ctx._check(ctx.lib.tp_lightcurve_diagnostics(ctx.handle, Nt, T, lc.ptrs[0], lc.ptrs[1], lc.ptrs[3], lc.ptrs[4], lc.n_cad,
-		time.ptr, quality.ptr, qstride, int(bitmask), _ptr(status), _ptr(sumimage), _ptr(mask), H, W, float(timescale), out.ptr))
+	if len(time.shape) == 1:
+		ctx._check(ctx.lib.tp_lightcurve_diagnostics(ctx.handle, Nt, T, lc.ptrs[0], lc.ptrs[1], lc.ptrs[3], lc.ptrs[4], lc.n_cad,
+			time.ptr, quality.ptr, qstride, int(bitmask), _ptr(status), _ptr(sumimage), _ptr(mask), H, W, float(timescale), out.ptr))
+		return out
+	if time.shape[0] < Nt:
+		raise ValueError(f"lightcurve_diagnostics: {time.shape[0]} time vectors for {Nt} targets")
+	ctx._check(ctx.lib.tp_lightcurve_diagnostics_times(ctx.handle, Nt, T, lc.ptrs[0], lc.ptrs[1], lc.ptrs[3], lc.ptrs[4], lc.n_cad,
+		time.ptr, int(time.shape[1]), quality.ptr, qstride, int(bitmask), _ptr(status), _ptr(sumimage), _ptr(mask), H, W, float(timescale), out.ptr))
 	return out
 
 

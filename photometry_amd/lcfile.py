@@ -355,3 +355,61 @@ def save_lightcurves(results, stack, output_folder, info, time, quality, version
 	results.filepaths = paths
 	results._filepath_rel = {int(i): relative_filepath(paths[int(i)], output_folder, output_folder) for i in wanted}
 	return paths
+
+
+def save_tpf_lightcurves(results, output_folder, version, workers=None, compresslevel=9, timings=None):
+	"""
+	The light-curve files of a ``tessphot.TpfBatchResults`` (a chunk of ``tessphot_tpfs``): for every target whose final status is OK or
+	WARNING the file ``tessphot('aperture', starid, TpfStampSource(...), output_folder, datasource='tpf')`` writes.  Every file has a
+	:class:`FileInfo` of its own, from its headers as :meth:`FileInfo.from_source` takes it from the ``TpfStampSource``; ``TIME`` ..
+	``PIXEL_QUALITY`` and ``POS_CORR1/2`` are the file's columns, ``QUALITY`` is all zero (a target pixel file brings no pixel flags),
+	the ``APERTURE`` image is the file's without SPOC's mask and centroid flags plus this run's, the image cards are the stamp's
+	limits.  Threads, ``compresslevel``, ``timings`` (``build`` / ``gzip``) and the return value as :func:`save_lightcurves`.
+	"""
+	import time as _clock
+	if version is None:
+		raise ValueError("VERSION has not been set")
+	n = len(results)
+	output_folder = os.path.abspath(output_folder)
+	os.makedirs(output_folder, exist_ok=True)
+	status = np.asarray(results.status)
+	wanted = np.flatnonzero((status == STATUS.OK.value) | (status == STATUS.WARNING.value))
+	from .plugins import K2P2_HEADERS, K2P2_SETTINGS
+	k2p2_headers = {key: (bool(K2P2_SETTINGS[name]) if isinstance(K2P2_SETTINGS[name], bool) else K2P2_SETTINGS[name], comment) for key, name, comment in K2P2_HEADERS}
+
+	def one(i):
+		r = results[i]
+		ld = results.loaded[i]
+		header = dict(ld.header)
+		header['TIME_OFFSET_CORRECTED'] = bool(ld.time_offset_corrected)
+		info = FileInfo(ld.sector, ld.camera, ld.ccd, cadence=ld.cadence, n_readout=ld.n_readout, num_frm=ld.num_frm or 60, header=header)   # (60: BasePhotometry.py:372)
+		headers = dict(k2p2_headers)
+		if 'contamination' in r._details:
+			headers['AP_CONT'] = (r._details['contamination'], 'AP contamination')
+		stamp = tuple(int(v) for v in ld.max_stamp)
+		T = len(r.lightcurve['time'])
+		aperture = aperture_with_masks(results.aperture_image(i), r.final_phot_mask, r.final_phot_mask)
+		ta = _clock.perf_counter()
+		hdus = lightcurve_hdus({'tmag': float(results.tmag[i])}, int(results.starid[i]), info.sector, info.camera, info.ccd, info.cadence, info.data_rel, version, r.method,
+			info.ticver, info.header, info.num_frm, info.n_readout, headers, r.lightcurve, np.zeros(T, dtype='int32'), results.sumimage(i), aperture, image_cards(stamp))
+		path = os.path.join(output_folder, lightcurve_filename(results.starid[i], info.sector, info.camera, info.ccd, info.cadence, info.data_rel, version))
+		tb = _clock.perf_counter()
+		fitsio.write(path, hdus, compresslevel=compresslevel)
+		tc = _clock.perf_counter()
+		return path, tb - ta, tc - tb
+
+	workers = min(MAX_WORKERS, os.cpu_count() or 1) if workers is None else max(1, min(MAX_WORKERS, int(workers)))
+	paths = [None] * n
+	if workers == 1 or len(wanted) <= 1:
+		done = [one(int(i)) for i in wanted]
+	else:
+		with ThreadPoolExecutor(max_workers=workers) as pool:
+			done = list(pool.map(one, [int(i) for i in wanted]))
+	for i, (path, t_build, t_gzip) in zip(wanted, done):
+		paths[int(i)] = path
+		if timings is not None:
+			timings['build'] = timings.get('build', 0.0) + t_build
+			timings['gzip'] = timings.get('gzip', 0.0) + t_gzip
+	results.filepaths = paths
+	results._filepath_rel = {int(i): relative_filepath(paths[int(i)], output_folder, output_folder) for i in wanted}
+	return paths

@@ -272,6 +272,58 @@ def run_aperture(ctx, scene, cubes='host', masks=None, diagnostics=True):
 	return out
 
 
+class GroupScene(object):
+	"""
+	The ``Scene`` contract :class:`ApertureBatch` reads, for targets that share a stamp shape and a number of cadences and nothing
+	else (the files of a ``tpf.TpfGroup``): ``quality`` and ``time`` ``(n, T)``, one row per target, ``stamps`` ``(n, 4)``, the ragged
+	catalogue (``cat_offsets`` and ``catalog`` with ``starid, tmag, row, column, row_stamp, column_stamp``), the ``target_*`` columns and
+	the per-target ``aperture`` ``(n, H, W)``.
+	"""
+
+	def __init__(self, time, quality, stamps, cat_offsets, catalog, target_pos_row, target_pos_column, target_tmag, target_starid, aperture, cadence_s=120):
+		self.time = np.ascontiguousarray(time, dtype='float64')
+		self.quality = np.ascontiguousarray(quality, dtype='int32')
+		if self.time.ndim != 2 or self.quality.shape != self.time.shape:
+			raise ValueError("GroupScene: time and quality are (targets, cadences)")
+		self.n_targets, self.n_cad = self.time.shape
+		self.stamps = np.asarray(stamps, dtype='int32').reshape(self.n_targets, 4)
+		self.height, self.width = int(self.stamps[0, 1] - self.stamps[0, 0]), int(self.stamps[0, 3] - self.stamps[0, 2])
+		self.cat_offsets = np.asarray(cat_offsets, dtype='int64')
+		self.catalog = catalog
+		self.target_pos_row, self.target_pos_column = np.asarray(target_pos_row, dtype='float64'), np.asarray(target_pos_column, dtype='float64')
+		self.target_tmag, self.target_starid = np.asarray(target_tmag, dtype='float64'), np.asarray(target_starid, dtype='int64')
+		self.aperture = np.asarray(aperture, dtype='int32')
+		self.cadence_s = cadence_s
+
+	def catalog_of(self, i):
+		a, b = self.cat_offsets[i], self.cat_offsets[i + 1]
+		return {k: v[a:b] for k, v in self.catalog.items()}
+
+
+def run_aperture_group(ctx, scene, cubes):
+	"""
+	:func:`run_aperture` for a :class:`GroupScene` over device cubes as they are: one :class:`ApertureBatch`, one packed
+	:class:`ApertureWork`, one :func:`aperture_step`, one :func:`aperture_diagnostics` with the per-target time vectors, and one
+	download of the packed block.  Returns the dict of host arrays of :func:`run_aperture` (without ``diag``) and the light-curve block
+	``lc`` ``(5, n, T)`` they are planes of, all views of that one download.
+	"""
+	batch = ApertureBatch(ctx, scene, cubes=cubes)
+	if (batch.n_targets, batch.n_cad, batch.height, batch.width) != (scene.n_targets, scene.n_cad, scene.height, scene.width):
+		raise ValueError("run_aperture_group: the cubes are not the scene's targets, cadences and stamp shape")
+	n_cat = max(int(scene.cat_offsets[-1]), 1)
+	work = ApertureWork(ctx, batch, packed=True, cat_capacity=n_cat, extras=True)
+	aperture_step(ctx, batch, work)
+	aperture_diagnostics(ctx, batch, work)
+	blob = work.block.to_host()                                          # (waits for the stream)
+	out = {}
+	for name, (off, shape, dtype) in work.block_layout.items():
+		out[name] = np.frombuffer(blob, dtype=dtype, count=int(np.prod(shape)), offset=off).reshape(shape)
+	lc = out['lc']
+	out['flux'], out['flux_err'], out['flux_background'] = lc[0], lc[1], lc[2]
+	out['pos_centroid'] = np.stack((lc[3], lc[4]), axis=-1)
+	return out
+
+
 class LinPSFBatch(object):
 	"""
 	Device-resident inputs of the LinPSF pipeline (linpsf_photometry.py:79-219) for a batch:

@@ -13,6 +13,8 @@ call sites run_tessphot.py:153, run_tessphot_mpi.py:178) with the contract they 
   the final mask still carries more than ``haloswitch.flux_limit`` of the expected flux on the stamp edge.
 
 ``tessphot_batch`` / ``tessphot_frames`` are the throughput entries (not in the reference): a whole batch per device pass.
+``tessphot_tpfs`` is the one for target pixel files: ``tessphot('aperture', ..., datasource='tpf')`` for many files, one pass per group
+of files that share stamp shape and number of cadences.
 """
 
 import logging
@@ -464,3 +466,212 @@ def tessphot_batch(ctx, scene, cubes='host'):
 		lc = {k: res[k][i] for k in ('flux', 'flux_err', 'flux_background', 'pos_centroid')}
 		out.append(BatchResult(int(scene.target_starid[i]), status, 'aperture', details, lc, res['mask'][i].astype(bool)))
 	return out
+
+
+#--------------------------------------------------------------------------------------------------
+#: the share of the free device memory the three cubes of one chunk of :func:`tessphot_tpfs` may take, and the most files of a chunk
+TPF_CHUNK_SHARE = 0.25
+TPF_CHUNK_MAX = 4096
+
+
+def tpf_chunk_files(shapes, free_bytes, share=TPF_CHUNK_SHARE, most=TPF_CHUNK_MAX):
+	"""
+	Files per chunk of :func:`tessphot_tpfs` from the header shapes ``(H, W, n_rows)``: as many of the largest file's three float32
+	cubes (``H * W`` series of ``n_rows`` rounded up to 32 cadences) as fit ``share`` of ``free_bytes``; at least 1, at most ``most``
+	and the number of files.
+	"""
+	per_file = max(3 * 4 * int(H) * int(W) * (-(-int(n_rows) // 32) * 32) for H, W, n_rows in shapes)
+	return int(max(1, min(int(most), len(shapes), int(share * free_bytes) // per_file)))
+
+
+class TpfBatchResults(BatchResults):
+	"""
+	What :func:`tessphot_tpfs` yields per chunk: :class:`BatchResults` over target pixel files.  ``starid``, ``status``, ``paths`` (the
+	input files) and ``filepaths`` (the light-curve files, ``None`` where none was written or asked for) are in input order;
+	``column(name)`` as there; ``results[i]`` is the :class:`BatchResult` the per-file call ``tessphot('aperture', starid,
+	TpfStampSource(...), datasource='tpf')`` returns: its light curve carries ``time, timecorr, cadenceno, quality`` and ``pos_corr``
+	(``POS_CORR1/2``) of the file besides the photometry.  ``stamp_resizes`` is 0 throughout (a ``tpf`` stamp is the whole file) and is
+	kept in the details, as on :class:`BatchResults`; where the diagnostics raise upstream the details carry that error alone, as the
+	plugin's do.  ``loaded``: the ``tpf.LoadedTPF`` of every file (its cubes are gone once the chunk has been yielded).
+	"""
+
+	def __init__(self, frames_result, starid, tmag, paths, loaded, apertures):
+		super().__init__(frames_result, starid)
+		#: ``tmag`` of every file's main target
+		self.tmag = np.asarray(tmag, dtype='float64')
+		self.paths = list(paths)
+		self.loaded = list(loaded)
+		self._apertures = apertures
+		self.filepaths = [None] * len(self.paths)
+
+	def save_lightcurves(self, output_folder, version, workers=None, compresslevel=9):
+		"""Write the light-curve file of every OK / WARNING target as the per-file plugin call does (``lcfile.save_tpf_lightcurves``)."""
+		from . import lcfile
+		return lcfile.save_tpf_lightcurves(self, output_folder, version, workers=workers, compresslevel=compresslevel)
+
+	def aperture_image(self, i):
+		"""The APERTURE image of file ``i`` without SPOC's mask and centroid flags: ``BasePhotometry.aperture`` of a ``tpf`` run."""
+		return self._apertures[int(i)]
+
+	def sumimage(self, i):
+		i = int(i) + len(self) if int(i) < 0 else int(i)
+		return np.array(self.frames.groups[self.frames.group[i]]['sumimage'][self.frames.pos[i]])
+
+	def __getitem__(self, i):
+		i = int(i) + len(self) if int(i) < 0 else int(i)
+		out = super().__getitem__(i)
+		if (self._problems[i] & 7) and 'errors' in out._details:
+			out._details['errors'] = out._details['errors'][-1:]       # (the plugin raises: what it had logged is lost, BasePhotometry.py:1346-1349)
+		if out.lightcurve is not None:
+			ld = self.loaded[i]
+			lc = {'time': np.array(ld.time, dtype='float64'), 'timecorr': np.array(ld.timecorr, dtype='float64'), 'cadenceno': np.array(ld.cadenceno),
+				'quality': np.array(ld.quality)}
+			lc.update({k: out.lightcurve[k] for k in ('flux', 'flux_err', 'flux_background', 'pos_centroid')})
+			lc['pos_corr'] = np.array(ld.pos_corr, dtype='float64')
+			out.lightcurve = lc
+		return out
+
+
+def _one_attempt(flags):
+	"""What ``AperturePhotometry.do_photometry`` makes of the device flags of an attempt whose stamp cannot grow (a ``tpf`` run:
+	photometry.py:113-170, :243-257): ``(status, has_result, messages)`` in the words of the plugin's log."""
+	from .plugins import _MASK_EXCEPTIONS
+	from . import stamps
+	flags = int(flags)
+	kind = flags >> 8
+	if kind in _MASK_EXCEPTIONS:                                         # uncaught upstream: the traceback is all that is left
+		return STATUS.ERROR, False, ['RuntimeError: ' + _MASK_EXCEPTIONS[kind]]
+	messages = []
+	if flags & 32:
+		messages.append('ERROR: No flux above threshold.')
+	if flags & 1:
+		messages.append('WARNING: No masks found. Using minimum aperture.' if flags & (32 | 64) else 'WARNING: No mask found for main target. Using minimum aperture.')
+	if kind == 5:
+		return STATUS.ERROR, False, messages + ['ERROR: Too many masks.']
+	if stamps.edge_requests(flags):
+		messages.append('WARNING: Could not resize stamp any further.')
+	status = STATUS.OK
+	if kind == 6:
+		messages.append('ERROR: No targets in mask.')
+		status = STATUS.ERROR
+	return (STATUS.WARNING if flags & 1 else status), True, messages
+
+
+def _tpf_chunk(ctx, files, headers, starid, catalog, targets, verify):
+	"""One chunk of :func:`tessphot_tpfs`: load, one device pass per ``(H, W, T)`` group, the results in input order."""
+	from . import tpf, pipeline
+	n = len(files)
+	groups, index = tpf.load_tpf_groups(ctx, files, verify=verify, headers=headers)
+	try:
+		loaded = [groups[g].loaded[s] for g, s in index]
+		stamps_all = np.array([ld.max_stamp for ld in loaded], dtype='int64').reshape(n, 4)
+		cat_px, tgt_px = tpf.project_for_files(ctx, loaded, catalog, targets)
+		shared = None
+		if cat_px is None:
+			shared = {k: np.asarray(catalog[k]) for k in ('starid', 'tmag', 'row', 'column')}
+			offs_all, cat_all = pipeline._catalogs_of_stamps(pipeline._CatalogIndex(shared), stamps_all)
+			first = {}
+			for k, sid in enumerate(shared['starid']):
+				first.setdefault(int(sid), k)
+		tstar = None if targets is None else np.asarray(targets['starid'])
+		# per file: the stars of its stamp and its main target, as TpfStampSource and BasePhotometry.__init__ make them
+		cats, pos, lost = [], np.zeros((n, 3)), {}
+		for i, ld in enumerate(loaded):
+			r0, _, c0, _ = ld.max_stamp
+			if shared is None:
+				full = {'starid': np.asarray(catalog['starid']), 'tmag': np.asarray(catalog['tmag']),
+					'column': (cat_px[i][:, 0] + c0).astype('float32'), 'row': (cat_px[i][:, 1] + r0).astype('float32')}
+				cats.append(pipeline._catalog_of_stamp(full, ld.max_stamp))
+			else:
+				full = shared
+				cats.append({k: v[offs_all[i]:offs_all[i + 1]] for k, v in cat_all.items()})
+			hit = np.flatnonzero(tstar == starid[i]) if tstar is not None else ()
+			if len(hit):
+				k = int(hit[0])
+				if tgt_px is not None:
+					row, col = tgt_px[i][k, 1] + r0, tgt_px[i][k, 0] + c0
+				else:
+					row, col = targets['row'][k], targets['column'][k]
+				pos[i] = float(row), float(col), float(targets['tmag'][k])
+			else:
+				k = first.get(int(starid[i])) if shared is not None else next(iter(np.flatnonzero(full['starid'] == starid[i])), None)
+				if k is None:
+					lost[i] = f"RuntimeError: Star could not be found in catalog: {int(starid[i]):d}"      # BasePhotometry.py:414
+					pos[i] = 0.5 * (ld.max_stamp[0] + ld.max_stamp[1]), 0.5 * (ld.max_stamp[2] + ld.max_stamp[3]), 10.0
+				else:
+					pos[i] = float(full['row'][k]), float(full['column'][k]), float(full['tmag'][k])
+		fr = pipeline.FramesResult(n)
+		fr.stamp[:] = stamps_all
+		apertures = [None] * n
+		by_slot = [[None] * len(g) for g in groups]
+		for i, (g, s) in enumerate(index):
+			by_slot[g][s] = i
+		for g, grp in enumerate(groups):
+			ids = by_slot[g]
+			offs = np.concatenate(([0], np.cumsum([len(cats[i]['starid']) for i in ids]))).astype('int64')
+			cat = {k: np.concatenate([cats[i][k] for i in ids]) for k in ('starid', 'tmag', 'row', 'column', 'row_stamp', 'column_stamp')}
+			scene = pipeline.GroupScene(grp.time, grp.quality, stamps_all[ids], offs, cat, pos[ids, 0], pos[ids, 1], pos[ids, 2],
+				np.asarray(starid, dtype='int64')[ids], grp.aperture, cadence_s=grp.loaded[0].cadence or 1800)
+			res = pipeline.run_aperture_group(ctx, scene, grp.cubes)
+			res.update(cat_offsets=offs, cat_starid=cat['starid'], target_starid=scene.target_starid)
+			fr.groups.append(res)
+			for s, i in enumerate(ids):
+				fr.group[i], fr.pos[i] = g, s
+				apertures[i] = grp.aperture[s]
+				if i in lost:
+					fr.status[i], fr.errors[i] = STATUS.ERROR.value, [lost[i]]
+					continue
+				status, fr.has_result[i], messages = _one_attempt(res['flags'][s])
+				fr.status[i] = status.value
+				if messages:
+					fr.errors[i] = messages
+				if int(res['flags'][s]) >> 8 == 6:
+					res['contamination'][s] = np.nan                    # photometry.py:243-246
+	finally:
+		for grp in groups:
+			grp.free()
+	return TpfBatchResults(fr, starid, pos[:, 2], files, loaded, apertures)
+
+
+def tessphot_tpfs(ctx, files, catalog, targets=None, settings=None, output_folder=None, version=None, chunk_files=None, verify=True,
+	workers=None, compresslevel=9):
+	"""
+	Aperture photometry of many target pixel files: what ``tessphot('aperture', starid, tpf.TpfStampSource(loaded, catalog,
+	targets=targets), output_folder, datasource='tpf', version=version)`` returns and writes per file, with one pass of the fused
+	kernel, one launch of the diagnostics and one download per group of files that share ``(H, W, T)``.  A generator: one
+	:class:`TpfBatchResults` per chunk of ``chunk_files`` files, in input order.
+
+	``files``: the paths; ``catalog`` / ``targets``: as for :class:`~photometry_amd.tpf.TpfStampSource` -- ``row`` / ``column`` in CCD
+	pixels, or ``ra`` / ``dec``, which every file projects through the WCS of its own APERTURE header and moves by its stamp's place
+	on the CCD (``tpf.project_for_files``: all files of a chunk in one call).  The stars of a stamp are those of the whole postage
+	stamp plus the five-pixel buffer; the main target is the file's ``TICID``, or what a ``'file'`` column of ``targets`` names for the
+	path (``tpf.main_targets``; list a file once per target).
+	``chunk_files``: files per chunk; by default as many as keep the chunk's three cubes under a quarter (:data:`TPF_CHUNK_SHARE`) of
+	the device memory that is free when the run starts, at most :data:`TPF_CHUNK_MAX` (:func:`tpf_chunk_files`).  The cubes of a chunk
+	are freed before the next chunk is loaded.
+	``output_folder`` with ``version``: the ``tess…-tasoc_lc.fits.gz`` of every OK / WARNING target is written on ``workers`` threads (at
+	most 16) with gzip's ``compresslevel``; ``QUALITY`` is all zero, what the plugin writes for a source without pixel flags.
+	``verify``: the ``DATASUM`` check of ``tpf.load_tpfs``.
+	This is ``tessphot('aperture', ...)``: with ``[halo] enabled`` in the settings nothing is switched to Halo photometry, which is logged.
+	"""
+	from . import tpf, halo
+	logger = logging.getLogger(__name__)
+	files = [str(f) for f in files]
+	if not files:
+		raise ValueError("tessphot_tpfs: no files")
+	if output_folder is not None and version is None:
+		raise ValueError("VERSION has not been set")
+	settings = load_settings() if settings is None else settings
+	if halo.enabled(settings):
+		logger.info("Halo photometry is enabled in the settings, but batches of target pixel files do not switch methods: aperture results are kept.")
+	headers = [tpf.read_tpf_header(f) for f in files]
+	starid = tpf.main_targets(files, [h.header.get('TICID') for h in headers], targets)
+	if chunk_files is None:
+		chunk_files = tpf_chunk_files([h.aperture.shape + (h.table.n_rows,) for h in headers], ctx.mem_info()[0])
+	chunk_files = max(1, int(chunk_files))
+	for a in range(0, len(files), chunk_files):
+		b = min(a + chunk_files, len(files))
+		out = _tpf_chunk(ctx, files[a:b], headers[a:b], starid[a:b], catalog, targets, verify)
+		if output_folder is not None:
+			out.save_lightcurves(output_folder, version, workers=workers, compresslevel=compresslevel)
+		yield out

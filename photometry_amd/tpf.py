@@ -14,8 +14,12 @@ checked on the device with ``tp_fits_datasum``.
 :func:`find_tpf_files` is the reference's file-name rule, :func:`read_tpf_header` what the headers alone tell, :func:`load_tpfs`
 the streaming loader, :func:`time_offset` the timestamp fix of the early data releases (fixes/time_offset.py), which this loader
 applies as the reference does at BasePhotometry.py:384, and :class:`TpfStampSource` hands a loaded file to the plugin classes.
+:func:`load_tpf_groups` is the loader of a batched run (``tessphot_tpfs``): the same stream into one set of cubes per group of files
+that share ``(H, W, T)`` -- ``TIME`` is barycentric per target, so a group shares its shape and nothing else, and carries a time and a
+quality vector per file; :func:`plan_groups` is where every file ends up, :func:`project_for_files` and :func:`main_targets` make
+catalogue and main target of every file what :class:`TpfStampSource` would.
 
-Not covered: one cube for many files (``TIME`` is barycentric per target: files share no time axis), image columns other than
+Not covered: image columns other than
 ``E``, ``RAW_CNTS`` and ``FLUX_BKG_ERR``, the pixel-quality and cosmic-ray extensions, the HDF5-side inputs of a ``tpf`` run in the
 reference (the catalogue comes in as a dict), tile-compressed files.
 """
@@ -366,6 +370,332 @@ def load_tpfs(ctx, files, verify=True):
 		if up is not None:
 			up.close()
 	return loaded
+
+
+#--------------------------------------------------------------------------------------------------
+class TpfGroup(object):
+	"""
+	The files of one :func:`load_tpf_groups` call that share ``(H, W, T)``, in one cube per image column:
+
+	``shape``: ``(H, W, T)``; ``cubes``: ``{'images', 'images_err', 'backgrounds'}``, :class:`~photometry_amd.device.DeviceCube` s of
+	``n`` targets; ``loaded``: one :class:`LoadedTPF` per slot, its ``cubes`` non-owning one-target views of its slot (``free()`` on
+	them releases nothing); ``time`` ``(n, T)`` float64, ``quality`` ``(n, T)`` int32, ``aperture`` ``(n, H, W)`` int32 without the
+	flags of SPOC's mask (2) and centroid pixels (8), as ``BasePhotometry.aperture`` takes them for a ``tpf`` run.  ``free()``
+	releases the cubes of the group.
+	"""
+
+	def __init__(self, shape, cubes, owned, loaded):
+		self.shape = tuple(int(v) for v in shape)
+		self.cubes, self._owned, self.loaded = cubes, owned, loaded
+		self.time = np.stack([ld.time for ld in loaded]).astype('float64')
+		self.quality = np.stack([ld.quality for ld in loaded]).astype('int32')
+		self.aperture = np.stack([ld.aperture for ld in loaded]).astype('int32') & ~np.int32(2 | 8)
+
+	def __len__(self):
+		return len(self.loaded)
+
+	def free(self):
+		for ld in self.loaded:
+			ld.free()
+		for cube in self._owned:
+			cube.free()
+		self._owned = []
+		self.cubes = {name: None for name in self.cubes}
+
+
+def bucket_files(shapes):
+	"""``shapes``: ``(H, W, n_rows)`` of every file, from the headers.  Returns ``(keys, members)``: the distinct shapes in the order of
+	their first file and, per shape, its files in the order given -- file ``members[b][j]`` is unpacked into slot ``j`` of bucket ``b``."""
+	keys, members = [], []
+	for i, s in enumerate(shapes):
+		s = tuple(int(v) for v in s)
+		if s not in keys:
+			keys.append(s)
+			members.append([])
+		members[keys.index(s)].append(i)
+	return keys, members
+
+
+def plan_groups(shapes, kept):
+	"""
+	Where the files of :func:`load_tpf_groups` end up: a pure function of the header shapes ``(H, W, n_rows)`` and of ``kept``, the number
+	of rows with a finite ``TIME`` per file.  Returns ``(groups, index, moves)``.
+
+	``groups``: a list of ``(shape, bucket, own, files)``: ``shape = (H, W, T)``, ``bucket`` the number of the file's header shape
+	(:func:`bucket_files`), ``own`` False for the bucket's regular group -- the files whose ``T`` is the bucket's most common one (of two
+	equally common ones the one met first), which stay in the bucket's cubes -- and True for a sub-group of files with another ``T``,
+	which gets cubes of its own; ``files[slot]`` is the input number of the file in that slot.  A bucket's regular group comes first, its
+	sub-groups follow in the order of their first file.
+	``index[i] = (group, slot)`` of input file ``i``.
+	``moves``: ``(bucket, source slot, group, slot)`` in the order they have to be made: first every odd file out of its bucket slot
+	into its sub-group, then, for every hole this leaves below the number ``n`` of regular files, lowest first, the regular file
+	of the highest slot still at or above ``n`` into it.  The regular files then lie in slots ``[0, n)``.
+	"""
+	keys, members = bucket_files(shapes)
+	groups, index, moves = [], [None] * len(shapes), []
+	for b, files in enumerate(members):
+		H, W, _ = keys[b]
+		counts = {}
+		for i in files:
+			counts[int(kept[i])] = counts.get(int(kept[i]), 0) + 1
+		mode = max(counts, key=lambda t: (counts[t], -[int(kept[i]) for i in files].index(t)))
+		n = counts[mode]
+		slots = list(files)                                              # slots[j]: the file in bucket slot j
+		regular = len(groups)
+		groups.append(((H, W, mode), b, False, None))
+		sub = {}
+		for j, i in enumerate(files):
+			t = int(kept[i])
+			if t == mode:
+				continue
+			if t not in sub:
+				sub[t] = len(groups)
+				groups.append(((H, W, t), b, True, []))
+			g = sub[t]
+			moves.append((b, j, g, len(groups[g][3])))
+			groups[g][3].append(i)
+			slots[j] = None
+		high = len(slots) - 1
+		for j in range(n):
+			if slots[j] is not None:
+				continue
+			while slots[high] is None:
+				high -= 1
+			moves.append((b, high, regular, j))
+			slots[j], slots[high] = slots[high], None
+		groups[regular] = ((H, W, mode), b, False, slots[:n])
+	for g, (_, _, _, files) in enumerate(groups):
+		for slot, i in enumerate(files):
+			index[i] = (g, slot)
+	return groups, index, moves
+
+
+def load_tpf_groups(ctx, files, verify=True, headers=None):
+	"""
+	:func:`load_tpfs` for a batched run: the files are unpacked straight into cubes of many targets, one set of three cubes per group of
+	files with the same ``(H, W, T)``.  Returns ``(groups, index)``: a list of :class:`TpfGroup` and, per input file in input order, its
+	``(group, slot)``.
+
+	Every header is read and checked before anything is allocated, as in :func:`load_tpfs`, and the files are put into buckets by
+	``(H, W, NAXIS2)``.  A bucket gets three cubes ``[files][H * W][t_pitch]`` with ``t_pitch`` from ``NAXIS2``; each file streams through
+	the same two staging buffers and one ``tp_tpf_unpack`` writes it, pads included, into its slot -- its kept rows ``T`` are known on
+	the host before that call is queued.  Once all files are in, :func:`plan_groups` says which files of a bucket have another ``T`` than
+	the bucket's most common one: each of them is moved (``tp_memcpy_d2d``) into the cubes of its own sub-group, which keep the bucket's
+	``t_pitch``, and a hole it leaves among the regular files is filled from the bucket's last regular slot.  A run without odd files
+	moves nothing; an odd file costs one move out and at most one move into its hole.  No pixel passes through host memory and no file
+	lies in two cubes.  ``verify``, :class:`ffi.ChecksumError` and the promise that after any exception everything is freed are those of
+	:func:`load_tpfs`.  ``headers``: the :class:`TPFHeader` of every file when the caller has read them already.
+	"""
+	from .device import Context, DeviceCube
+	files = [str(f) for f in files]
+	if not files:
+		raise ValueError("load_tpf_groups: no files")
+	infos = [read_tpf_header(f) for f in files] if headers is None else list(headers)
+	if len(infos) != len(files):
+		raise ValueError("load_tpf_groups: one header per file")
+	_check_aperture_units(infos)
+	shapes = [h.aperture.shape + (h.table.n_rows,) for h in infos]
+	keys, members = bucket_files(shapes)
+	place = {i: (b, j) for b, m in enumerate(members) for j, i in enumerate(m)}
+	span = [(h.table.offset, h.aperture.offset + h.aperture.nbytes - h.table.offset) for h in infos]
+	stage_bytes = max(n for _, n in span)
+	slot_bytes = ffi._round_up(max(h.table.nbytes for h in infos), 256)
+	names = [name for name, _ in IMAGE_COLUMNS]
+	loaded, owned, out_groups = [], [], []
+	up = None
+	stage, done, d_slots, d_sums = [], [], None, None
+	try:
+		d_slots = ctx.empty((2, slot_bytes), 'uint8')
+		d_sums = ctx.zeros((len(infos),), 'uint64')
+		buckets = []
+		for (H, W, n_rows), m in zip(keys, members):
+			buckets.append({})
+			for name in names:
+				cube = DeviceCube(ctx, len(m), n_rows, H, W)
+				owned.append(cube)
+				buckets[-1][name] = cube
+		ctx.sync()
+		up = Context(ctx.device, high_priority=False)
+		lib = up.lib
+		stage = [ctx.pinned((stage_bytes,), 'uint8') for _ in range(2)]
+		done = [up.event(), up.event()]
+		for i, h in enumerate(infos):
+			s = i % 2
+			tb = h.table
+			stats = {'read_s': 0.0, 'wait_s': 0.0, 'bytes': int(span[i][1])}
+			if i >= 2:
+				t0 = _time.perf_counter()
+				up.event_sync(done[s])
+				stats['wait_s'] += _time.perf_counter() - t0
+			t0 = _time.perf_counter()
+			ffi._read_into(h.path, stage[s].array, span[i][0], span[i][1])
+			stats['read_s'] += _time.perf_counter() - t0
+			d_table = d_slots.ptr + s * slot_bytes
+			up._check(lib.tp_upload_cube_async(up.handle, d_table, tb.nbytes // 4, stage[s].ptr, tb.nbytes // 4, 1, tb.nbytes // 4))
+			up.record(done[s])
+			out = _host_side(h, stage[s].array)
+			out.stats = stats
+			out.cubes = {name: None for name in names}
+			loaded.append(out)
+			H, W = out.aperture.shape
+			T = len(out.time)
+			if T == 0:
+				raise ValueError(f"{h.path}: no row of the PIXELS table has a finite TIME")
+			if verify and tb.datasum is not None:
+				up._check(lib.tp_fits_datasum(up.handle, d_table, tb.nbytes, d_sums.ptr + 8 * i))
+			b, j = place[i]
+			pitch = buckets[b][names[0]].t_pitch
+			rows = None if out.rows_dropped == 0 else np.ascontiguousarray(out._kept_rows, dtype='int32')
+			offsets = (ctypes.c_int64 * 3)(*[tb.columns[col].offset for _, col in IMAGE_COLUMNS])
+			outs = (ctypes.c_void_p * 3)(*[buckets[b][name].ptr + j * H * W * pitch * 4 for name in names])
+			up._check(lib.tp_tpf_unpack(up.handle, d_table, tb.row_bytes, tb.n_rows, None if rows is None else rows.ctypes.data, T, 3,
+				ctypes.addressof(offsets), H * W, ctypes.addressof(outs), pitch))
+			del out._kept_rows
+		plan, index, moves = plan_groups(shapes, [len(ld.time) for ld in loaded])
+		cubes_of = []
+		for (H, W, T), b, own, members_g in plan:
+			if own:
+				cubes = {name: DeviceCube(ctx, len(members_g), T, H, W, t_pitch=buckets[b][name].t_pitch) for name in names}
+				owned.extend(cubes.values())
+			else:
+				cubes = buckets[b]
+			cubes_of.append(cubes)
+		if any(own for _, _, own, _ in plan):
+			ctx.sync()                                               # the cubes of the sub-groups exist before the other stream writes them
+		for b, src, g, slot in moves:
+			(H, W, _), _, _, _ = plan[g]
+			for name in names:
+				one = H * W * buckets[b][name].t_pitch * 4
+				up._check(lib.tp_memcpy_d2d(up.handle, cubes_of[g][name].ptr + slot * one, buckets[b][name].ptr + src * one, one))
+		t0 = _time.perf_counter()
+		up.sync()
+		loaded[-1].stats['wait_s'] += _time.perf_counter() - t0
+		if verify:
+			sums = d_sums.to_host()
+			for i, h in enumerate(infos):
+				if h.table.datasum is not None and int(sums[i]) != h.table.datasum:
+					raise ffi.ChecksumError(f"{h.path}: HDU {h.table.hdu}: the data unit sums to {int(sums[i])}, its DATASUM card says {h.table.datasum}")
+		for g, ((H, W, T), b, own, members_g) in enumerate(plan):
+			n = len(members_g)
+			cubes = {}
+			for name in names:
+				whole = cubes_of[g][name]
+				whole.n_cad = T
+				cubes[name] = whole if whole.n_targets == n else whole.slice0(0, n)
+			for slot, i in enumerate(members_g):
+				loaded[i].cubes = {name: cubes[name].slice0(slot, 1) for name in names}
+			out_groups.append(TpfGroup((H, W, T), cubes, [cubes_of[g][name] for name in names], [loaded[i] for i in members_g]))
+	except BaseException:
+		if up is not None and getattr(up, 'handle', None) is not None:
+			try:
+				up.sync()                                                # nothing may still write into a cube that goes back to the cache
+			except Exception: # noqa: B902
+				pass
+		for cube in owned:
+			cube.free()
+		raise
+	finally:
+		if up is not None and getattr(up, 'handle', None) is not None:
+			try:
+				up.sync()
+			except Exception: # noqa: B902
+				pass
+			for e in done:
+				up.lib.tp_event_destroy(up.handle, e)
+		for p in stage:
+			p.free()
+		for d in (d_slots, d_sums):
+			if d is not None:
+				d.free()
+		if up is not None:
+			up.close()
+	return out_groups, index
+
+
+def _needs_projection(d):
+	return d is not None and 'row' not in d and 'column' not in d and 'ra' in d and 'dec' in d
+
+
+def project_for_files(ctx, loaded, catalog, targets=None, max_points=1 << 24):
+	"""
+	The pixel positions :class:`TpfStampSource` gives a ``catalog`` / ``targets`` in ``ra`` / ``dec`` for every file of ``loaded``, without
+	one device call per file: the WCSs of the files' APERTURE headers are the frames of ``tp_wcs_world2pix`` and the points are the
+	catalogue as one batch and every target as a batch of its own, which is how the source projects them (``all_world2pix`` with its
+	defaults; the stopping test is per batch and frame).  Returns ``(catalog_px, targets_px)``, each ``None`` when that dict needs no
+	projection, else float64 ``(files, points, 2)`` of 0-based ``(x, y)`` relative to the stamp: the caller adds the stamp's place on the
+	CCD.  At most ``max_points`` positions are formed per call of the entry (``max_points // points`` files, never more than 65 535).
+	A point that does not converge raises :class:`photometry_amd.wcs.NoConvergence` naming the file, as the source would.
+	"""
+	from . import wcs as W
+	need_c, need_t = _needs_projection(catalog), _needs_projection(targets)
+	if not (need_c or need_t):
+		return None, None
+	for ld in loaded:
+		if not ld.wcs_cards:
+			raise ValueError(f"{ld.path}: the catalogue is in ra / dec and the APERTURE header has no WCS to project it through")
+	params = W.pack([W.TanSipWCS.from_header(ld.wcs_cards) for ld in loaded])
+	empty = np.zeros((0, 2))
+	pc = np.column_stack((catalog['ra'], catalog['dec'])).astype('float64') if need_c else empty
+	pt = np.column_stack((targets['ra'], targets['dec'])).astype('float64') if need_t else empty
+	nc, nt = len(pc), len(pt)
+	n = nc + nt
+	pts = np.ascontiguousarray(np.concatenate((pc, pt)))
+	offsets = np.concatenate(([0], nc + np.arange(nt + 1))).astype('int64')
+	d_radec = ctx.array(pts if n else np.zeros((1, 2)))
+	d_cos = ctx.empty((max(n, 1), 3), 'float64')
+	ctx._check(ctx.lib.tp_wcs_radec(ctx.handle, n, d_radec.ptr, d_cos.ptr))
+	F = len(loaded)
+	out = np.empty((F, n, 2))
+	step = max(1, min(65535, int(max_points) // max(n, 1)))
+	for a in range(0, F, step):
+		f = min(step, F - a)
+		d_params = ctx.array(params[a:a + f])
+		pix, status, iters = W.world2pix_frames(ctx, d_params, f, d_cos, n, offsets, 0, 1, 1e-4, 20)
+		bad = np.flatnonzero(np.any(status & (W.DIVERGENT | W.SLOW), axis=1))
+		if len(bad):
+			k = int(bad[0])
+			div, slow = np.flatnonzero(status[k] & W.DIVERGENT), np.flatnonzero(status[k] & W.SLOW)
+			raise W.NoConvergence(f"{loaded[a + k].path}: 'WCS.all_world2pix' failed to converge to the requested accuracy after {int(iters[k].max()):d} iterations.",
+				best_solution=pix[k], divergent=div if len(div) else None, slow_conv=slow if len(slow) else None, niter=int(iters[k].max()))
+		out[a:a + f] = pix
+	return (out[:, :nc] if need_c else None), (out[:, nc:] if need_t else None)
+
+
+def main_targets(files, ticids, targets=None):
+	"""
+	The ``starid`` of the main target of every file of a batched run: the file's ``TICID``, unless ``targets`` has a ``'file'`` column
+	with entries that name the file's path -- then the ``j``-th time the path appears in ``files`` it takes the ``starid`` of its
+	``j``-th entry (the reference's ``tpf:starid``: a file is listed once per extra target).  ``ValueError`` for a file listed more often
+	than it has entries, or without entries and without a ``TICID``.
+	"""
+	entries = {}
+	if targets is not None and 'file' in targets:
+		for k, name in enumerate(targets['file']):
+			if name is not None and str(name) != '':
+				entries.setdefault(str(name), []).append(int(np.asarray(targets['starid'])[k]))
+	seen, out = {}, []
+	for path, ticid in zip(files, ticids):
+		path = str(path)
+		if path in entries:
+			j = seen.get(path, 0)
+			seen[path] = j + 1
+			if j >= len(entries[path]):
+				raise ValueError(f"{path}: listed {j + 1} times, but targets names it {len(entries[path])} times")
+			out.append(entries[path][j])
+		elif ticid is None:
+			raise ValueError(f"{path}: the primary header has no TICID and targets names no target for the file")
+		else:
+			out.append(int(ticid))
+	return out
+
+
+def _check_aperture_units(infos):
+	for h in infos:
+		if h.aperture.bitpix != 32:
+			raise ValueError(f"{h.path}: the APERTURE image has BITPIX {h.aperture.bitpix}, not 32")
+		for key in ('CRVAL1P', 'CRVAL2P'):
+			if key not in h.aperture.header:
+				raise ValueError(f"{h.path}: the APERTURE header lacks the {key} card")
 
 
 def _host_side(h, buf):
