@@ -1004,6 +1004,32 @@ int tp_tpf_unpack(tp_ctx* ctx, const void* d_table, int64_t row_bytes, int64_t n
 int tp_stamp_flag_series(tp_ctx* ctx, const uint8_t* d_flags, int32_t n_frames, int32_t frame_rows, int32_t frame_cols, int64_t frame_stride,
 	int32_t row0, int32_t col0, int32_t n_targets, const int64_t* h_stamps, uint32_t flag_mask, int32_t out_value, int32_t* d_out, int64_t out_pitch);
 
+/* ---- batched DEFLATE (csrc/deflate.hip; the rules in csrc/deflate_rules.h) -----------------------------------------------------------
+ * RFC 1951 on the device, for the gzip members of the light-curve files.  The n_streams streams of a call lie in d_in: stream s is
+ * d_in[off[s], off[s + 1]) with off = h_stream_offsets (HOST, n_streams + 1 values that do not fall).  A stream is cut into chunks of
+ * tp_deflate_chunk_bytes() input bytes, the last one shorter, a stream of 0 bytes has none; the chunks of a call are numbered in call
+ * order.  Every chunk has a window of its own and becomes a byte-aligned run of complete blocks without BFINAL (dynamic, fixed or
+ * stored, whichever is smallest; a coded block is followed by an empty stored block), so the outputs of a stream's chunks,
+ * concatenated, followed by the two bytes 03 00, are a raw deflate stream of the stream's bytes.
+ * tp_deflate: d_out receives the outputs of all chunks back to back; d_chunk_end[c] (uint64) is the offset in d_out at which chunk c
+ *   ends, d_chunk_crc[c] the CRC-32 (gzip polynomial) of its input bytes.  Bytes of d_out behind the last end are never written.  The
+ *   output is a function of the input bytes alone: the same in every run.  d_work: scratch of tp_deflate_work_bytes(off, n_streams)
+ *   bytes, in use until the call's work on the stream is over.  Alignments: d_in and d_out none, d_chunk_end 8, d_chunk_crc 4, d_work 16.
+ *   TP_ERR_INVALID, checked on the host before anything is queued, nothing written: a null pointer with work to do, offsets that
+ *   fall, n_streams < 1, 2^34 bytes or more in all, out_capacity below the sum of tp_deflate_bound over the streams, work_bytes
+ *   below tp_deflate_work_bytes, a misaligned pointer.  A call without a byte of input queues nothing and reads no pointer.
+ *   Asynchronous on the context's stream; three launches per call (encode, running ends, pack).
+ * tp_deflate_bound(nbytes): the most output bytes of a stream of nbytes bytes: nbytes + 5 per chunk (the stored form).
+ * tp_deflate_work_bytes: the scratch of a call, 0 for arguments tp_deflate refuses.  tp_deflate_chunk_bytes: the chunk length.
+ * tp_crc32_combine: crc(A || B) from crc(A), crc(B) and len(B), so that a stream's CRC follows from its chunks'.
+ * The last four are host-only and need no context.                                                                               */
+int tp_deflate(tp_ctx* ctx, const void* d_in, const uint64_t* h_stream_offsets, int64_t n_streams, void* d_out, uint64_t out_capacity,
+	uint64_t* d_chunk_end, uint32_t* d_chunk_crc, void* d_work, uint64_t work_bytes);
+uint64_t tp_deflate_bound(uint64_t nbytes);
+uint64_t tp_deflate_work_bytes(const uint64_t* h_stream_offsets, int64_t n_streams);
+uint64_t tp_deflate_chunk_bytes(void);
+uint32_t tp_crc32_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b);
+
 /* ---- synthetic data (bench / test utility, not part of the reference path) -----------------
  * Fill images / images_err / backgrounds cubes on the device from scene parameters, following
  * the data model of simulation/simulateFITS.py:338-405 (see photometry_amd/simulate.py).

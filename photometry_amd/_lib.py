@@ -207,6 +207,11 @@ SIGNATURES = {
 	'tp_fits_datasum': (c_int, [c_void_p, _p, c_uint64, _p]),
 	'tp_tpf_unpack': (c_int, [c_void_p, _p, c_int64, c_int64, _p, c_int64, c_int32, _p, c_int64, _p, c_int64]),
 	'tp_stamp_flag_series': (c_int, [c_void_p, _p, c_int32, c_int32, c_int32, c_int64, c_int32, c_int32, c_int32, _p, c_uint32, c_int32, _p, c_int64]),
+	'tp_deflate': (c_int, [c_void_p, _p, _p, c_int64, _p, c_uint64, _p, _p, _p, c_uint64]),
+	'tp_deflate_bound': (c_uint64, [c_uint64]),
+	'tp_deflate_work_bytes': (c_uint64, [_p, c_int64]),
+	'tp_deflate_chunk_bytes': (c_uint64, []),
+	'tp_crc32_combine': (c_uint32, [c_uint32, c_uint32, c_uint64]),
 	'tp_synth_fill': (c_int, [c_void_p, _desc_p, c_int32, _p, _p, _p, _p, _p, c_double, c_double, c_uint64, _p, _p, _p, _p]),
 }
 

@@ -76,6 +76,9 @@ static const char* const kKernelNames[TPK_COUNT] = {
 	"tp_fits_fold_kernel",
 	"tp_tpf_unpack_kernel",
 	"tp_stamp_flags_kernel",
+	"tp_deflate_kernel",
+	"tp_deflate_scan_kernel",
+	"tp_deflate_pack_kernel",
 };
 
 extern "C" {

@@ -74,6 +74,9 @@ enum tp_kernel_id {
 	TPK_FITS_FOLD,
 	TPK_TPF_UNPACK,
 	TPK_STAMP_FLAGS,
+	TPK_DEFLATE,
+	TPK_DEFLATE_SCAN,
+	TPK_DEFLATE_PACK,
 	TPK_COUNT
 };
 

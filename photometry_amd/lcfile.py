@@ -10,8 +10,9 @@ paths that produce one:
   (``FrameStack.stamp_flag_series``, csrc/stampflags.hip), the images cropped from the region's, bytes and gzip on a thread pool;
 * :class:`FileInfo` -- what such a batch cannot know from its arguments (sector, camera, CCD, the input file's header, ...).
 
-Building the bytes and compressing them is host work: a file is 96 bytes per cadence against the 40 + 16 that cross the link as
-light curve and ``QUALITY``, and gzip dominates it.
+Building the bytes is host work: a file is 96 bytes per cadence against the 40 + 16 that cross the link as light curve and
+``QUALITY``.  Compressing them is host work too by default (``compress='zlib'``) and dominates it (DESIGN.md section 17);
+``compress='device'`` hands the bytes of a window of files to the device's DEFLATE encoder instead (``deflate.gzip_many``, section 19).
 """
 
 import datetime
@@ -29,6 +30,77 @@ CORRECTOR_BACKGROUND_SHENANIGANS = 256
 PROCVER = 'photometry_amd-0.2'
 #: the most threads :func:`save_lightcurves` writes files with
 MAX_WORKERS = 16
+#: what ``compress=`` takes: gzip on the workers (the default: the bytes ``gzip.open`` writes), or DEFLATE on the device
+COMPRESS = ('zlib', 'device')
+#: files whose bytes are held at a time with ``compress='device'``: built, compressed in batches, written, then the next window
+DEVICE_WINDOW = 256
+
+
+def _add_timings(timings, spent):
+	for k, v in spent.items():
+		if isinstance(v, dict):
+			_add_timings(timings.setdefault(k, {}), v)
+		else:
+			timings[k] = timings.get(k, 0.0) + v
+
+
+def _write_files(build, wanted, workers, compress, compresslevel, ctx, spent):
+	"""
+	The files of the targets ``wanted``: ``build(i) -> (path, hdus, seconds)`` on ``workers`` threads, then the gzip member.
+	``'zlib'``: the worker that built the bytes compresses and writes them (``fitsio.write``).  ``'device'``: per window of
+	:data:`DEVICE_WINDOW` files the workers build the bytes, the calling thread -- the owner of ``ctx`` -- compresses them in batches
+	(``deflate.gzip_many``), and the workers write the members.  Returns the paths in the order of ``wanted``; adds the seconds to
+	``spent['build']`` and ``spent['gzip']`` (``'device'``: the wall time of the device path, its parts as ``deflate.gzip_many`` names
+	them in ``spent['gzip_parts']``, and ``spent['write']`` for the files).
+	"""
+	import time as _clock
+	workers = min(MAX_WORKERS, os.cpu_count() or 1) if workers is None else max(1, min(MAX_WORKERS, int(workers)))
+	wanted = [int(i) for i in wanted]
+	serial = workers == 1 or len(wanted) <= 1
+
+	def zlib_one(i):
+		path, hdus, t_build = build(i)
+		tb = _clock.perf_counter()
+		fitsio.write(path, hdus, compresslevel=compresslevel)
+		return path, t_build, _clock.perf_counter() - tb
+
+	def build_one(i):
+		path, hdus, t_build = build(i)
+		return path, b''.join(hdus), t_build
+
+	def write_one(job):
+		tb = _clock.perf_counter()
+		with open(job[0], 'wb') as fh:
+			fh.write(job[1])
+		return _clock.perf_counter() - tb
+
+	if compress == 'zlib':
+		if serial:
+			done = [zlib_one(i) for i in wanted]
+		else:
+			with ThreadPoolExecutor(max_workers=workers) as pool:
+				done = list(pool.map(zlib_one, wanted))
+		for _path, t_build, t_gzip in done:
+			spent['build'] += t_build
+			spent['gzip'] += t_gzip
+		return [d[0] for d in done]
+	from . import deflate
+	paths = []
+	pool = None if serial else ThreadPoolExecutor(max_workers=workers)
+	try:
+		run = (lambda f, jobs: [f(j) for j in jobs]) if serial else (lambda f, jobs: list(pool.map(f, jobs)))
+		for a in range(0, len(wanted), DEVICE_WINDOW):
+			built = run(build_one, wanted[a:a + DEVICE_WINDOW])
+			spent['build'] += sum(b[2] for b in built)
+			tb = _clock.perf_counter()
+			members = deflate.gzip_many(ctx, [b[1] for b in built], parts=spent.setdefault('gzip_parts', {}))
+			spent['gzip'] += _clock.perf_counter() - tb
+			spent['write'] = spent.get('write', 0.0) + sum(run(write_one, [(b[0], m) for b, m in zip(built, members)]))
+			paths.extend(b[0] for b in built)
+	finally:
+		if pool is not None:
+			pool.shutdown()
+	return paths
 
 
 def weightmap_hdu(weightmap, shape, cards=()):
@@ -265,15 +337,21 @@ def _crop(image, stamp, row0, col0):
 
 
 def save_lightcurves(results, stack, output_folder, info, time, quality, version, timecorr=None, cadenceno=None, targets=None, workers=None,
-	compresslevel=9, timings=None):
+	compresslevel=9, timings=None, compress='zlib'):
 	"""
 	Write the light-curve file of every target of ``results`` (a ``tessphot.BatchResults`` over ``stack``) whose final status is OK
 	or WARNING -- the rule of ``run_plugin`` (tessphot.py:52-53) --, as the per-target run would: same name, same folder,
 	``_details['filepath_lightcurve']``.  Returns the list of paths (``None`` where no file was written), also kept as
 	``results.filepaths``.  See ``BatchResults.save_lightcurves`` for the arguments; ``timings``: a dict that receives the seconds
 	spent in ``quality`` (launch + download), ``build`` (bytes of the HDUs, summed over the workers) and ``gzip`` (likewise).
+	``compress``: ``'zlib'`` (the default: gzip at ``compresslevel`` on the workers, the bytes ``gzip.open`` writes) or ``'device'``: the
+	workers build the bytes, the calling thread compresses them on the stack's device (``deflate.gzip_many``) and the workers write the
+	members -- the same content in other compressed bytes, which depend on the content alone; ``compresslevel`` is ignored, and
+	``timings['gzip']`` is the wall time of the device path (``timings['write']``: writing the files, summed over the workers).
 	"""
 	import time as _clock
+	if compress not in COMPRESS:
+		raise ValueError(f"compress must be one of {COMPRESS}, not {compress!r}")
 	if version is None:
 		raise ValueError("VERSION has not been set")
 	if targets is None:
@@ -333,40 +411,34 @@ def save_lightcurves(results, stack, output_folder, info, time, quality, version
 		hdus = lightcurve_hdus(target, int(results.starid[i]), info.sector, info.camera, info.ccd, info.cadence, info.data_rel, version, r.method, info.ticver,
 			info.header, info.num_frm, info.n_readout, headers, lc, flag_series[i], sumimage, aperture, image_cards(stamp, info.wcs_header), weightmap=r.halo_weightmap)
 		path = os.path.join(output_folder, lightcurve_filename(results.starid[i], info.sector, info.camera, info.ccd, info.cadence, info.data_rel, version))
-		tb = _clock.perf_counter()
-		fitsio.write(path, hdus, compresslevel=compresslevel)
-		tc = _clock.perf_counter()
-		return path, tb - ta, tc - tb
+		return path, hdus, _clock.perf_counter() - ta
 
-	workers = min(MAX_WORKERS, os.cpu_count() or 1) if workers is None else max(1, min(MAX_WORKERS, int(workers)))
 	paths = [None] * n
-	if workers == 1 or len(wanted) <= 1:
-		done = [one(int(i)) for i in wanted]
-	else:
-		with ThreadPoolExecutor(max_workers=workers) as pool:
-			done = list(pool.map(one, [int(i) for i in wanted]))
-	for i, (path, t_build, t_gzip) in zip(wanted, done):
+	for i, path in zip(wanted, _write_files(one, wanted, workers, compress, compresslevel, getattr(stack, 'ctx', None), spent)):
 		paths[int(i)] = path
-		spent['build'] += t_build
-		spent['gzip'] += t_gzip
 	if timings is not None:
-		for k, v in spent.items():
-			timings[k] = timings.get(k, 0.0) + v
+		_add_timings(timings, spent)
 	results.filepaths = paths
 	results._filepath_rel = {int(i): relative_filepath(paths[int(i)], output_folder, output_folder) for i in wanted}
 	return paths
 
 
-def save_tpf_lightcurves(results, output_folder, version, workers=None, compresslevel=9, timings=None):
+def save_tpf_lightcurves(results, output_folder, version, workers=None, compresslevel=9, timings=None, compress='zlib', ctx=None):
 	"""
 	The light-curve files of a ``tessphot.TpfBatchResults`` (a chunk of ``tessphot_tpfs``): for every target whose final status is OK or
 	WARNING the file ``tessphot('aperture', starid, TpfStampSource(...), output_folder, datasource='tpf')`` writes.  Every file has a
 	:class:`FileInfo` of its own, from its headers as :meth:`FileInfo.from_source` takes it from the ``TpfStampSource``; ``TIME`` ..
 	``PIXEL_QUALITY`` and ``POS_CORR1/2`` are the file's columns, ``QUALITY`` is all zero (a target pixel file brings no pixel flags),
 	the ``APERTURE`` image is the file's without SPOC's mask and centroid flags plus this run's, the image cards are the stamp's
-	limits.  Threads, ``compresslevel``, ``timings`` (``build`` / ``gzip``) and the return value as :func:`save_lightcurves`.
+	limits.  Threads, ``compresslevel``, ``timings`` (``build`` / ``gzip``), ``compress`` and the return value as :func:`save_lightcurves`;
+	``compress='device'`` runs on ``ctx`` (default: the context the results were computed on), whose owner the calling thread must be.
 	"""
 	import time as _clock
+	if compress not in COMPRESS:
+		raise ValueError(f"compress must be one of {COMPRESS}, not {compress!r}")
+	ctx = getattr(results, 'ctx', None) if ctx is None else ctx
+	if compress == 'device' and ctx is None:
+		raise ValueError("compress='device' needs the context of the batch (ctx=)")
 	if version is None:
 		raise ValueError("VERSION has not been set")
 	n = len(results)
@@ -393,23 +465,14 @@ def save_tpf_lightcurves(results, output_folder, version, workers=None, compress
 		hdus = lightcurve_hdus({'tmag': float(results.tmag[i])}, int(results.starid[i]), info.sector, info.camera, info.ccd, info.cadence, info.data_rel, version, r.method,
 			info.ticver, info.header, info.num_frm, info.n_readout, headers, r.lightcurve, np.zeros(T, dtype='int32'), results.sumimage(i), aperture, image_cards(stamp))
 		path = os.path.join(output_folder, lightcurve_filename(results.starid[i], info.sector, info.camera, info.ccd, info.cadence, info.data_rel, version))
-		tb = _clock.perf_counter()
-		fitsio.write(path, hdus, compresslevel=compresslevel)
-		tc = _clock.perf_counter()
-		return path, tb - ta, tc - tb
+		return path, hdus, _clock.perf_counter() - ta
 
-	workers = min(MAX_WORKERS, os.cpu_count() or 1) if workers is None else max(1, min(MAX_WORKERS, int(workers)))
+	spent = {'build': 0.0, 'gzip': 0.0}
 	paths = [None] * n
-	if workers == 1 or len(wanted) <= 1:
-		done = [one(int(i)) for i in wanted]
-	else:
-		with ThreadPoolExecutor(max_workers=workers) as pool:
-			done = list(pool.map(one, [int(i) for i in wanted]))
-	for i, (path, t_build, t_gzip) in zip(wanted, done):
+	for i, path in zip(wanted, _write_files(one, wanted, workers, compress, compresslevel, ctx, spent)):
 		paths[int(i)] = path
-		if timings is not None:
-			timings['build'] = timings.get('build', 0.0) + t_build
-			timings['gzip'] = timings.get('gzip', 0.0) + t_gzip
+	if timings is not None:
+		_add_timings(timings, spent)
 	results.filepaths = paths
 	results._filepath_rel = {int(i): relative_filepath(paths[int(i)], output_folder, output_folder) for i in wanted}
 	return paths

@@ -215,7 +215,7 @@ class BatchResults(object):
 	def __len__(self):
 		return len(self.frames)
 
-	def save_lightcurves(self, output_folder, info, time, quality, version, *, timecorr=None, cadenceno=None, targets=None, workers=None, compresslevel=9):
+	def save_lightcurves(self, output_folder, info, time, quality, version, *, timecorr=None, cadenceno=None, targets=None, workers=None, compresslevel=9, compress='zlib'):
 		"""
 		Write ``tess…-tasoc_lc.fits.gz`` for every target whose final status is OK or WARNING (the rule of :func:`run_plugin`): the file
 		``tessphot('aperture', ...)`` -- or, for a target switched to Halo photometry, ``tessphot(None, ...)`` -- writes for it, into
@@ -225,14 +225,16 @@ class BatchResults(object):
 		one the entry was called with), which may carry the catalogue columns ``ra_J2000, decl_J2000, pm_ra, pm_decl, teff``.
 		``QUALITY`` comes from the stack's pixel flags over the final stamps of the whole batch in one launch (all zero for a stack
 		without flags).  ``workers`` threads (default ``min(16, os.cpu_count())``, never more than 16) build and compress the files;
-		``compresslevel`` is gzip's (9: what the per-target plugin writes with).  Returns the paths, ``None`` where no file was written
+		``compresslevel`` is gzip's (9: what the per-target plugin writes with).  ``compress='device'``: the workers build the bytes, the
+		calling thread compresses them on the stack's device and the workers write the members (``lcfile.save_lightcurves``; the same
+		content, other compressed bytes; ``compresslevel`` is ignored).  Returns the paths, ``None`` where no file was written
 		(also ``self.filepaths``); ``results[i]._details['filepath_lightcurve']`` is set as the plugin sets it.
 		"""
 		from . import lcfile
 		if self.stack is None:
 			raise ValueError("these results do not know their frame stack: run the batch through tessphot_frames")
 		return lcfile.save_lightcurves(self, self.stack, output_folder, info, time, quality, version, timecorr=timecorr, cadenceno=cadenceno,
-			targets=self.targets if targets is None else targets, workers=workers, compresslevel=compresslevel)
+			targets=self.targets if targets is None else targets, workers=workers, compresslevel=compresslevel, compress=compress)
 
 	def edge_flux_column(self):
 		"""``details['edge_flux']`` of every target as a column (NaN: none): the flux on the stuck edge of the haloswitch quick break,
@@ -376,7 +378,7 @@ def _pos_corr(ctx, movement, targets, time, timecorr):
 	return movement.jitter_many(t, targets['column'], targets['row']).to_host()
 
 
-def _finish_batch(ctx, out, stack, targets, time, quality, timecorr, cadenceno, movement, output_folder, fileinfo, version):
+def _finish_batch(ctx, out, stack, targets, time, quality, timecorr, cadenceno, movement, output_folder, fileinfo, version, compress='zlib'):
 	"""What both batched entries do with a batch after the method switch: ``pos_corr``, the stack and targets, the files when asked for."""
 	if movement is not None:
 		out.pos_corr = _pos_corr(ctx, movement, targets, time, timecorr)
@@ -384,12 +386,12 @@ def _finish_batch(ctx, out, stack, targets, time, quality, timecorr, cadenceno, 
 	if output_folder is not None:
 		if fileinfo is None:
 			raise ValueError("output_folder needs fileinfo (a photometry_amd.lcfile.FileInfo)")
-		out.save_lightcurves(output_folder, fileinfo, time, quality, version, timecorr=timecorr, cadenceno=cadenceno)
+		out.save_lightcurves(output_folder, fileinfo, time, quality, version, timecorr=timecorr, cadenceno=cadenceno, compress=compress)
 	return out
 
 
 def tessphot_frames(ctx, stack, targets, catalog, time, quality, settings=None, sector=None, timecorr=None, cadenceno=None, movement=None,
-	output_folder=None, fileinfo=None, version=None):
+	output_folder=None, fileinfo=None, version=None, compress='zlib'):
 	"""
 	Aperture photometry of every target of a CCD region resident in HBM (:class:`photometry_amd.pipeline.FrameStack`), stamp
 	resizes included: what ``tessphot('aperture', ...)`` returns per target, for the whole batch in a few device passes.
@@ -400,24 +402,25 @@ def tessphot_frames(ctx, stack, targets, catalog, time, quality, settings=None, 
 	``movement``: a :class:`~photometry_amd.motion.MovementKernel` with a loaded series: ``BatchResults.pos_corr`` and every light
 	curve's ``'pos_corr'`` are then its jitter at the targets' positions at ``time - timecorr``, as the plugins write it.
 	``output_folder`` with ``fileinfo`` (a :class:`~photometry_amd.lcfile.FileInfo`) and ``version``: the light-curve files of the batch
-	are written as well (:meth:`BatchResults.save_lightcurves`), as ``run_plugin`` writes them per target.
+	are written as well (:meth:`BatchResults.save_lightcurves`), as ``run_plugin`` writes them per target; ``compress``: ``'zlib'`` or
+	``'device'``, as there.
 	Returns a :class:`BatchResults`: columns for the whole batch, one :class:`BatchResult` per target on demand (``results[i]``).
 	"""
 	from . import pipeline
 	res = pipeline.aperture_frames(ctx, stack, targets, catalog, time, quality, settings=settings)
 	out = _halo_switch_frames(ctx, stack, BatchResults(res, targets['starid']), targets, catalog, time, quality, settings, sector, timecorr, cadenceno)
-	return _finish_batch(ctx, out, stack, targets, time, quality, timecorr, cadenceno, movement, output_folder, fileinfo, version)
+	return _finish_batch(ctx, out, stack, targets, time, quality, timecorr, cadenceno, movement, output_folder, fileinfo, version, compress)
 
 
 def tessphot_frames_pipelined(ctx, stack, batches, catalog, time, quality, settings=None, in_flight=4, sector=None, timecorr=None, cadenceno=None,
-	movement=None, output_folder=None, fileinfo=None, version=None):
+	movement=None, output_folder=None, fileinfo=None, version=None, compress='zlib'):
 	"""
 	:func:`tessphot_frames` over consecutive batches of targets of one CCD region -- what a run over a whole CCD does, a few
 	thousand targets per call -- with ``in_flight`` batches on the device at a time (``pipeline.aperture_frames_pipelined``: the
 	first round of a batch runs under the latency-bound resize rounds of the one before it).  ``batches``: an iterable of
 	``targets`` dicts; yields one :class:`BatchResults` per batch, in order, equal to what a call of its own returns (the switch to
 	Halo photometry included, applied to each batch before it is yielded; ``movement`` as there; with ``output_folder`` / ``fileinfo`` /
-	``version`` the files of each batch are written as it is collected).
+	``version`` the files of each batch are written as it is collected, ``compress`` as there).
 	"""
 	from . import pipeline
 	batches = list(batches) if not hasattr(batches, '__next__') else batches
@@ -428,7 +431,7 @@ def tessphot_frames_pipelined(ctx, stack, batches, catalog, time, quality, setti
 			yield t
 	for k, res in enumerate(pipeline.aperture_frames_pipelined(ctx, stack, feed(), catalog, time, quality, settings=settings, in_flight=in_flight)):
 		out = _halo_switch_frames(ctx, stack, BatchResults(res, seen[k]['starid']), seen[k], catalog, time, quality, settings, sector, timecorr, cadenceno)
-		yield _finish_batch(ctx, out, stack, seen[k], time, quality, timecorr, cadenceno, movement, output_folder, fileinfo, version)
+		yield _finish_batch(ctx, out, stack, seen[k], time, quality, timecorr, cadenceno, movement, output_folder, fileinfo, version, compress)
 
 
 def tessphot_batch(ctx, scene, cubes='host'):
@@ -503,11 +506,14 @@ class TpfBatchResults(BatchResults):
 		self.loaded = list(loaded)
 		self._apertures = apertures
 		self.filepaths = [None] * len(self.paths)
+		#: the context the chunk was computed on (set by :func:`tessphot_tpfs`): where ``compress='device'`` runs
+		self.ctx = None
 
-	def save_lightcurves(self, output_folder, version, workers=None, compresslevel=9):
-		"""Write the light-curve file of every OK / WARNING target as the per-file plugin call does (``lcfile.save_tpf_lightcurves``)."""
+	def save_lightcurves(self, output_folder, version, workers=None, compresslevel=9, compress='zlib'):
+		"""Write the light-curve file of every OK / WARNING target as the per-file plugin call does (``lcfile.save_tpf_lightcurves``);
+		``compress='device'`` compresses on the context of the batch, by the calling thread."""
 		from . import lcfile
-		return lcfile.save_tpf_lightcurves(self, output_folder, version, workers=workers, compresslevel=compresslevel)
+		return lcfile.save_tpf_lightcurves(self, output_folder, version, workers=workers, compresslevel=compresslevel, compress=compress, ctx=self.ctx)
 
 	def aperture_image(self, i):
 		"""The APERTURE image of file ``i`` without SPOC's mask and centroid flags: ``BasePhotometry.aperture`` of a ``tpf`` run."""
@@ -634,7 +640,7 @@ def _tpf_chunk(ctx, files, headers, starid, catalog, targets, verify):
 
 
 def tessphot_tpfs(ctx, files, catalog, targets=None, settings=None, output_folder=None, version=None, chunk_files=None, verify=True,
-	workers=None, compresslevel=9):
+	workers=None, compresslevel=9, compress='zlib'):
 	"""
 	Aperture photometry of many target pixel files: what ``tessphot('aperture', starid, tpf.TpfStampSource(loaded, catalog,
 	targets=targets), output_folder, datasource='tpf', version=version)`` returns and writes per file, with one pass of the fused
@@ -650,7 +656,8 @@ def tessphot_tpfs(ctx, files, catalog, targets=None, settings=None, output_folde
 	the device memory that is free when the run starts, at most :data:`TPF_CHUNK_MAX` (:func:`tpf_chunk_files`).  The cubes of a chunk
 	are freed before the next chunk is loaded.
 	``output_folder`` with ``version``: the ``tess…-tasoc_lc.fits.gz`` of every OK / WARNING target is written on ``workers`` threads (at
-	most 16) with gzip's ``compresslevel``; ``QUALITY`` is all zero, what the plugin writes for a source without pixel flags.
+	most 16) with gzip's ``compresslevel`` -- or, with ``compress='device'``, compressed on the device by the calling thread while the
+	workers build the bytes and write the members (``lcfile.save_tpf_lightcurves``) --; ``QUALITY`` is all zero, what the plugin writes for a source without pixel flags.
 	``verify``: the ``DATASUM`` check of ``tpf.load_tpfs``.
 	This is ``tessphot('aperture', ...)``: with ``[halo] enabled`` in the settings nothing is switched to Halo photometry, which is logged.
 	"""
@@ -661,6 +668,8 @@ def tessphot_tpfs(ctx, files, catalog, targets=None, settings=None, output_folde
 		raise ValueError("tessphot_tpfs: no files")
 	if output_folder is not None and version is None:
 		raise ValueError("VERSION has not been set")
+	if compress not in ('zlib', 'device'):
+		raise ValueError(f"compress must be one of ('zlib', 'device'), not {compress!r}")
 	settings = load_settings() if settings is None else settings
 	if halo.enabled(settings):
 		logger.info("Halo photometry is enabled in the settings, but batches of target pixel files do not switch methods: aperture results are kept.")
@@ -672,6 +681,7 @@ def tessphot_tpfs(ctx, files, catalog, targets=None, settings=None, output_folde
 	for a in range(0, len(files), chunk_files):
 		b = min(a + chunk_files, len(files))
 		out = _tpf_chunk(ctx, files[a:b], headers[a:b], starid[a:b], catalog, targets, verify)
+		out.ctx = ctx
 		if output_folder is not None:
-			out.save_lightcurves(output_folder, version, workers=workers, compresslevel=compresslevel)
+			out.save_lightcurves(output_folder, version, workers=workers, compresslevel=compresslevel, compress=compress)
 		yield out

@@ -59,6 +59,9 @@ def main():
 	ap.add_argument('--plugin-targets', type=int, default=32)
 	ap.add_argument('--dir', default=None, help='where the files go (default: a temporary directory, removed afterwards)')
 	ap.add_argument('--out', default=None)
+	ap.add_argument('--compress', choices=('zlib', 'device'), nargs='+', default=['zlib'], help="how the files are compressed; 'device': one run per worker count")
+	ap.add_argument('--compresslevel', type=int, nargs='+', default=[9, 1], help="gzip's levels with --compress zlib")
+	ap.add_argument('--skip-baselines', action='store_true', help='the files alone: no flag-series timing on the host, no per-target plugin')
 	a = ap.parse_args()
 	import numpy as np
 	from photometry_amd import pipeline, tessphot_frames
@@ -100,35 +103,47 @@ def main():
 			kernel_ms.append(ctx.profile_report()['tp_stamp_flags_kernel'][1])
 		ctx.profile(False)
 		host_ms = []
-		for _ in range(a.repeats):
+		for _ in range(0 if a.skip_baselines else a.repeats):
 			t0 = time.perf_counter()
 			ref = np.zeros((N, T), dtype='int32')
 			for i, (r1, r2, c1, c2) in enumerate(stamps):
 				if r1 >= 0:
 					ref[i, np.any(flags[:, r1:r2, c1 - 44:c2 - 44] & 4, axis=(1, 2))] = CORRECTOR_BACKGROUND_SHENANIGANS
 			host_ms.append((time.perf_counter() - t0) * 1e3)
-		emit({'step': 'flags', 'targets': N, 'cadences': T, 'stack_MB': flags.nbytes / 1e6, 'kernel_ms': kernel_ms, 'kernel_ms_best': min(kernel_ms), 'call_ms': call_ms,
-			'call_ms_best': min(call_ms), 'numpy_one_core_ms': host_ms, 'numpy_one_core_ms_best': min(host_ms), 'equal': bool(np.array_equal(series, ref)),
-			'flagged_pairs': int((series != 0).sum())})
+		if not a.skip_baselines:
+			emit({'step': 'flags', 'targets': N, 'cadences': T, 'stack_MB': flags.nbytes / 1e6, 'kernel_ms': kernel_ms, 'kernel_ms_best': min(kernel_ms), 'call_ms': call_ms,
+				'call_ms_best': min(call_ms), 'numpy_one_core_ms': host_ms, 'numpy_one_core_ms_best': min(host_ms), 'equal': bool(np.array_equal(series, ref)),
+				'flagged_pairs': int((series != 0).sum())})
 
 		# ---- the files ----
 		info = FileInfo(14, 2, 3)
-		save_lightcurves(res, stack, os.path.join(root, 'warm'), info, tstamp, quality, 6, targets=targets, workers=16, compresslevel=1)      # warm-up
+		save_lightcurves(res, stack, os.path.join(root, 'warm'), info, tstamp, quality, 6, targets=targets, workers=16, compresslevel=1, compress=a.compress[-1])      # warm-up
 		n_files = int(wanted.sum())
-		for workers, level in ((1, 9), (16, 9), (1, 1), (16, 1)):
+		for compress, workers, level in [(c, w, l) for c in a.compress for l in (a.compresslevel if c == 'zlib' else a.compresslevel[:1]) for w in (1, 16)]:
 			runs = []
 			for k in range(a.repeats):
 				timings = {}
 				t0 = time.perf_counter()
 				paths = save_lightcurves(res, stack, os.path.join(root, f'w{workers}l{level}'), info, tstamp, quality, 6, targets=targets, workers=workers,
-					compresslevel=level, timings=timings)
-				runs.append({'wall_s': time.perf_counter() - t0, 'quality_s': timings['quality'], 'build_s': timings['build'], 'gzip_s': timings['gzip']})
+					compresslevel=level, timings=timings, compress=compress)
+				runs.append({'wall_s': time.perf_counter() - t0, 'quality_s': timings['quality'], 'build_s': timings['build'], 'gzip_s': timings['gzip'],
+					'write_s': timings.get('write'), 'gzip_parts_s': timings.get('gzip_parts')})
 			best = min(runs, key=lambda r: r['wall_s'])
 			size = sum(os.path.getsize(p) for p in paths if p is not None)
-			emit({'step': 'files', 'workers': workers, 'compresslevel': level, 'files': n_files, 'runs': runs, 'files_per_s': n_files / best['wall_s'],
+			deflate_kernels = None
+			if compress == 'device':                                          # once more under the kernel profile
+				ctx.profile(True)
+				ctx.profile_reset()
+				save_lightcurves(res, stack, os.path.join(root, f'w{workers}l{level}'), info, tstamp, quality, 6, targets=targets, workers=workers, compress='device')
+				ctx.sync()
+				deflate_kernels = {k: v for k, v in ctx.profile_report().items() if 'deflate' in k}
+				ctx.profile(False)
+			emit({'step': 'files', 'workers': workers, 'compress': compress, 'deflate_kernels': deflate_kernels, 'compresslevel': level if compress == 'zlib' else None, 'files': n_files, 'runs': runs, 'files_per_s': n_files / best['wall_s'],
 				'gzip_share_of_worker_time': best['gzip_s'] / (best['gzip_s'] + best['build_s']), 'quality_share_of_wall': best['quality_s'] / best['wall_s'],
 				'MB_written': size / 1e6})
 
+		if a.skip_baselines:
+			return
 		# ---- the per-target plugin ----
 		src = MemoryStampSource({k: np.moveaxis(v, 0, 2) for k, v in dict(frames, pixel_flags=flags).items()}, 0, 44, tstamp, np.zeros(T), np.arange(T), quality, cat,
 			targets=targets, sector=14, camera=2, ccd=3)
