@@ -17,7 +17,6 @@ releases for FFIs (``fixes.time_offset``: the adapter's job, see plugins.py; ``t
 types).  Target pixel files have a loader of their own, ``photometry_amd.tpf``.
 """
 
-import gzip
 import logging
 import os
 import re
@@ -26,6 +25,8 @@ from collections import namedtuple
 import numpy as np
 from . import fitsio
 from . import wcs as wcsmod
+from .device import round_up
+from .staging import StagedUpload, check_datasum
 
 #: the science region of a TESS FFI (io.py:47-48) and the shape that marks one (io.py:46)
 TESS_SHAPE = (2078, 2136)
@@ -58,10 +59,6 @@ class LoadedFFIs(object):
 			if a is not None:
 				a.free()
 			self.__dict__[name] = None
-
-
-def _round_up(n, m):
-	return (int(n) + m - 1) // m * m
 
 
 #--------------------------------------------------------------------------------------------------
@@ -120,22 +117,10 @@ def read_ffi_header(path):
 	``wcs_cards``: the raw 80-column cards of the HDU that holds the WCS, as one string: HDU 1 for every file (io.py:42).
 	"""
 	path = str(path)
-	opener = gzip.open if path.endswith('.gz') else open
 	hdus = []
-	with opener(path, 'rb') as fh:
-		pos = 0
-		while len(hdus) < 3:
-			try:
-				header, cards = fitsio.read_header_blocks(lambda: fh.read(fitsio.BLOCK))
-			except EOFError:
-				break
-			pos += _round_up(len(cards) * 80, fitsio.BLOCK)
-			shape, nbytes = fitsio.data_unit_bytes(header)
-			datasum = header.get('DATASUM')
-			hdus.append((header, cards, DataUnit(len(hdus), pos, header.get('BITPIX'), tuple(int(n) for n in shape), _round_up(nbytes, fitsio.BLOCK),
-				None if datasum is None else int(str(datasum).strip()))))
-			pos += _round_up(nbytes, fitsio.BLOCK)
-			fh.seek(pos)
+	for n, u in enumerate(fitsio.scan_hdus(path, 3)):
+		datasum = u.header.get('DATASUM')
+		hdus.append((u.header, u.cards, DataUnit(n, u.offset, u.header.get('BITPIX'), u.shape, u.nbytes, None if datasum is None else int(str(datasum).strip()))))
 	if len(hdus) < 2:
 		raise ValueError(f"{path}: an FFI has a primary HDU and at least one extension")
 	hdr0, hdr1 = hdus[0][0], hdus[1][0]
@@ -163,20 +148,6 @@ def wcs_header_string(cards):
 
 
 #--------------------------------------------------------------------------------------------------
-def _read_into(path, buf, start, nbytes):
-	"""``nbytes`` of the (decompressed) file from byte ``start`` into the uint8 array ``buf``, without an intermediate copy."""
-	opener = gzip.open if path.endswith('.gz') else open
-	view = memoryview(buf)[:nbytes]
-	with opener(path, 'rb') as fh:
-		fh.seek(start)
-		got = 0
-		while got < nbytes:
-			n = fh.readinto(view[got:])
-			if not n:
-				raise ValueError(f"{path}: the file ends inside a data unit ({start + got} of {start + nbytes} bytes)")
-			got += n
-
-
 def load_ffis(ctx, files, verify=True):
 	"""
 	Load the FFIs ``files`` (in the order given) into two float32 stacks on the device.  Returns a :class:`LoadedFFIs` with
@@ -192,13 +163,12 @@ def load_ffis(ctx, files, verify=True):
 	``BACKAPP`` card; ``files``; ``stats``: seconds the host spent reading and waiting.
 
 	Every header is read and every file's geometry held to the first one's before anything is allocated (``ValueError`` naming the
-	file).  The files then stream through two page-locked staging buffers on a second context, the scheme of
-	``frameio.upload_group``: while file ``i`` transfers and unpacks, file ``i + 1`` is read (``readinto``; a ``.gz`` is
-	decompressed) straight into the other buffer.  ``verify``: the word sum of every data unit that has a ``DATASUM`` card is formed
-	on the device and compared once all files are in; a mismatch raises :class:`ChecksumError` naming file and HDU.  After any
-	exception the staging buffers, events and both stacks are gone.
+	file).  The files then stream through two page-locked staging buffers on a second context (``staging.StagedUpload``): while
+	file ``i`` transfers and unpacks, file ``i + 1`` is read (``readinto``; a ``.gz`` is decompressed) straight into the other
+	buffer.  ``verify``: the word sum of every data unit that has a ``DATASUM`` card is formed on the device and compared once all
+	files are in; a mismatch raises :class:`ChecksumError` naming file and HDU.  After any exception the staging buffers, events
+	and both stacks are gone, the stacks only once nothing queued can write into them any more.
 	"""
-	from .device import Context
 	logger = logging.getLogger(__name__)
 	files = [str(f) for f in files]
 	if not files:
@@ -255,72 +225,34 @@ def load_ffis(ctx, files, verify=True):
 
 	# from the first byte of the image unit to the last of the uncertainty unit: what is read from a file
 	span = [(h.image.offset, h.uncert.offset + h.uncert.nbytes - h.image.offset) for h in infos]
-	stage_bytes = max(n for _, n in span)
-	half = _round_up(max(h.image.nbytes for h in infos), 256)           # every unit starts on a 256-byte boundary in device memory
-	slot_bytes = half + _round_up(max(h.uncert.nbytes for h in infos), 256)
-	up = None
-	stage, done, d_slots, d_sums = [], [], None, None
-	stats = {'read_s': 0.0, 'wait_s': 0.0, 'bytes': int(sum(n for _, n in span))}
+	half = round_up(max(h.image.nbytes for h in infos), 256)            # every unit starts on a 256-byte boundary in device memory
+	slot_bytes = half + round_up(max(h.uncert.nbytes for h in infos), 256)
 	tic = _time.perf_counter()
 	try:
 		out.raw = ctx.empty((T, R, C), 'float32')
 		out.raw_err = ctx.empty((T, R, C), 'float32')
-		d_slots = ctx.empty((2, slot_bytes), 'uint8')
-		d_sums = ctx.zeros((T, 2), 'uint64')
-		ctx.sync()
-		up = Context(ctx.device, high_priority=False)
-		lib = up.lib
-		stage = [ctx.pinned((stage_bytes,), 'uint8') for _ in range(2)]
-		done = [up.event(), up.event()]
-		for i, h in enumerate(infos):
-			s = i % 2
-			if i >= 2:
-				t0 = _time.perf_counter()
-				up.event_sync(done[s])                                  # the transfers that last read this staging buffer are over
-				stats['wait_s'] += _time.perf_counter() - t0
-			t0 = _time.perf_counter()
-			_read_into(h.path, stage[s].array, span[i][0], span[i][1])  # page cache / disk -> pinned memory, while file i-1 is in flight
-			stats['read_s'] += _time.perf_counter() - t0
-			units = ((h.image, out.raw, 0), (h.uncert, out.raw_err, half))
-			for unit, dst, off in units:
-				d_unit = d_slots.ptr + s * slot_bytes + off
-				up._check(lib.tp_upload_cube_async(up.handle, d_unit, unit.nbytes // 4, stage[s].ptr + unit.offset - span[i][0], unit.nbytes // 4, 1, unit.nbytes // 4))
-			up.record(done[s])
-			for j, (unit, dst, off) in enumerate(units):
-				d_unit = d_slots.ptr + s * slot_bytes + off
-				if verify and unit.datasum is not None:
-					up._check(lib.tp_fits_datasum(up.handle, d_unit, unit.nbytes, d_sums.ptr + 8 * (2 * i + j)))
-				up._check(lib.tp_fits_unpack(up.handle, d_unit, unit.bitpix, unit.shape[1], unit.shape[0], row0, col0, R, C, dst.ptr + i * R * C * 4, C))
-		t0 = _time.perf_counter()
-		up.sync()
-		stats['wait_s'] += _time.perf_counter() - t0
+		with StagedUpload(ctx, max(n for _, n in span), slot_bytes, 2 * T if verify else 0) as st:
+			up = st.up
+			for i, h in enumerate(infos):
+				st.take()
+				st.read(h.path, *span[i])
+				units = ((h.image, out.raw, st.slot), (h.uncert, out.raw_err, st.slot + half))
+				for unit, _, d_unit in units:
+					st.upload(d_unit, unit.nbytes, unit.offset - span[i][0])
+				st.record()
+				for j, (unit, dst, d_unit) in enumerate(units):
+					if verify and unit.datasum is not None:
+						st.datasum(d_unit, unit.nbytes, 2 * i + j)
+					up._check(up.lib.tp_fits_unpack(up.handle, d_unit, unit.bitpix, unit.shape[1], unit.shape[0], row0, col0, R, C, dst.ptr + i * R * C * 4, C))
+			sums = st.finish()
 		if verify:
-			sums = d_sums.to_host()
 			for i, h in enumerate(infos):
 				for j, unit in enumerate((h.image, h.uncert)):
-					if unit.datasum is not None and int(sums[i, j]) != unit.datasum:
-						raise ChecksumError(f"{h.path}: HDU {unit.hdu}: the data unit sums to {int(sums[i, j])}, its DATASUM card says {unit.datasum}")
+					check_datasum(h.path, unit.hdu, sums[2 * i + j], unit.datasum)
 	except BaseException:
-		out.free()
+		out.free()                                                      # (the transfer context has been synced: nothing can write into the stacks any more)
 		raise
-	finally:
-		# staging buffers, events and the transfer context go whatever happened
-		if up is not None and getattr(up, 'handle', None) is not None:
-			try:
-				up.sync()
-			except Exception: # noqa: B902
-				pass
-			for e in done:
-				up.lib.tp_event_destroy(up.handle, e)
-		for p in stage:
-			p.free()
-		for d in (d_slots, d_sums):
-			if d is not None:
-				d.free()
-		if up is not None:
-			up.close()
-	stats['total_s'] = _time.perf_counter() - tic
-	out.stats = stats
+	out.stats = dict(st.stats, bytes=int(sum(n for _, n in span)), total_s=_time.perf_counter() - tic)
 	return out
 
 

@@ -13,6 +13,7 @@ same subset and is used by the tests for round trips.
 import gzip
 import io
 import re
+from collections import namedtuple
 import numpy as np
 
 BLOCK = 2880
@@ -60,6 +61,11 @@ def _header_bytes(cards):
 
 def _pad(data, fill=b'\0'):
 	return data + fill * ((-len(data)) % BLOCK)
+
+
+def _padded(n):
+	"""``n`` bytes rounded up to whole blocks."""
+	return int(n) + (-int(n)) % BLOCK
 
 
 def _sum32(data, start=0):
@@ -246,10 +252,39 @@ def data_unit_bytes(header):
 	return shape, nbytes
 
 
+#: one HDU as :func:`scan_hdus` sees it: header, raw cards, byte offset of the data unit, its bytes with the padding, its shape
+HDU = namedtuple('HDU', 'header cards offset nbytes shape')
+
+
+def opener(path):
+	"""``gzip.open`` for a ``.gz`` file, else ``open``."""
+	return gzip.open if str(path).endswith('.gz') else open
+
+
+def scan_hdus(path, most):
+	"""
+	The first ``most`` HDUs of a plain or ``.gz`` file as :class:`HDU` s, reading header blocks only: the data units (``PCOUNT`` bytes
+	included) are skipped with ``seek``, and a file cut short behind a header ends the list quietly.
+	"""
+	hdus, pos = [], 0
+	with opener(path)(path, 'rb') as fh:
+		while len(hdus) < most:
+			try:
+				header, cards = read_header_blocks(lambda: fh.read(BLOCK))
+			except EOFError:
+				break
+			pos += _padded(len(cards) * 80)
+			shape, nbytes = data_unit_bytes(header)
+			nbytes = _padded(nbytes + int(header.get('PCOUNT', 0) or 0))
+			hdus.append(HDU(header, cards, pos, nbytes, tuple(int(n) for n in shape)))
+			pos += nbytes
+			fh.seek(pos)
+	return hdus
+
+
 def read(path):
 	"""Returns a list of ``(header dict, data)``; data is None, an ndarray (image) or a dict of column arrays (table)."""
-	opener = gzip.open if str(path).endswith('.gz') else open
-	with opener(path, 'rb') as fh:
+	with opener(path)(path, 'rb') as fh:
 		blob = fh.read()
 	out = []
 	pos = 0
@@ -262,8 +297,7 @@ def read(path):
 	while pos < len(blob):
 		header, raw_cards = read_header_blocks(next_block)
 		naxis = header.get('NAXIS', 0)
-		shape = [header[f'NAXIS{i}'] for i in range(naxis, 0, -1)]
-		nbytes = (abs(header.get('BITPIX', 8)) // 8) * int(np.prod(shape)) if naxis else 0
+		shape, nbytes = data_unit_bytes(header)
 		data = None
 		raw = blob[pos:pos + nbytes]
 		if header.get('XTENSION') == 'BINTABLE':

@@ -120,49 +120,28 @@ def open_group(path, name, meta=None):
 def upload_group(ctx, mm, frames_per_chunk=None, up=None):
 	"""
 	Stream a memory-mapped group into a new DeviceArray ``(T, R, C)``: two pinned staging buffers, the host copy of the next
-	chunk overlapping the transfer of the current one (``tp_upload_cube_async`` on a second stream).
+	chunk overlapping the transfer of the current one (``staging.StagedUpload``; ``up``: a transfer context to borrow).
 	"""
-	from .device import Context
+	from .staging import StagedUpload
 	T, R, C = mm.shape
-	item = mm.dtype.itemsize
+	frame = R * C * mm.dtype.itemsize
 	if frames_per_chunk is None:
-		frames_per_chunk = max(1, min(T, (256 << 20) // max(R * C * item, 1)))   # about 256 MiB per chunk
-	if (R * C * item) % 4:
+		frames_per_chunk = max(1, min(T, (256 << 20) // max(frame, 1)))   # about 256 MiB per chunk
+	if frame % 4:
 		raise ValueError('frame size must be a multiple of 4 bytes')   # before anything is allocated
-	own = up is None
 	dst = ctx.empty((T, R, C), mm.dtype)
-	stage, done = [], []
 	try:
-		if own:
-			up = Context(ctx.device, high_priority=False)
-		stage = [ctx.pinned((frames_per_chunk, R, C), mm.dtype) for _ in range(2)]
-		done = [up.event(), up.event()]
-		for i, k0 in enumerate(range(0, T, frames_per_chunk)):
-			s = i % 2
-			n = min(frames_per_chunk, T - k0)
-			if i >= 2:
-				up.event_sync(done[s])                                 # the transfer that last read this staging buffer is over
-			stage[s].array[:n] = mm[k0:k0 + n]                         # page cache / disk -> pinned memory, while chunk i-1 is in flight
-			nbytes = n * R * C * item
-			up._check(up.lib.tp_upload_cube_async(up.handle, dst.ptr + k0 * R * C * item, nbytes // 4, stage[s].ptr, nbytes // 4, 1, nbytes // 4))
-			up.record(done[s])
-		up.sync()
+		with StagedUpload(ctx, frames_per_chunk * frame, up=up) as st:
+			for k0 in range(0, T, frames_per_chunk):
+				n = min(frames_per_chunk, T - k0)
+				st.take()
+				st.fill(lambda buf: np.copyto(buf[:n * frame].view(mm.dtype).reshape(n, R, C), mm[k0:k0 + n]))   # noqa: B023
+				st.upload(dst.ptr + k0 * frame, n * frame)
+				st.record()
+			st.finish()
 	except BaseException:
-		dst.free()
+		dst.free()                                                     # (the transfer context has been synced: nothing can write into it any more)
 		raise
-	finally:
-		# staging buffers, events and the transfer context go whatever happened
-		if up is not None and getattr(up, 'handle', None) is not None:
-			try:
-				up.sync()
-			except Exception: # noqa: B902
-				pass
-			for e in done:
-				up.lib.tp_event_destroy(up.handle, e)
-		for p in stage:
-			p.free()
-		if own and up is not None:
-			up.close()
 	return dst
 
 

@@ -25,16 +25,16 @@ reference (the catalogue comes in as a dict), tile-compressed files.
 """
 
 import ctypes
-import gzip
 import logging
 import os
 import re
-import time as _time
 from collections import namedtuple, defaultdict
 import numpy as np
 from . import fitsio
 from . import ffi
+from .device import DeviceCube, round_up
 from .source import MemoryStampSource
+from .staging import StagedUpload, check_datasum
 
 #: the columns of the PIXELS table the loader reads, and those among them that are images
 COLUMNS = ('TIME', 'TIMECORR', 'CADENCENO', 'FLUX', 'FLUX_ERR', 'FLUX_BKG', 'QUALITY', 'POS_CORR1', 'POS_CORR2')
@@ -115,13 +115,8 @@ def find_tpf_files(rootdir, starid=None, sector=None, camera=None, ccd=None, cad
 	return files
 
 
-def _opener(path):
-	return gzip.open if str(path).endswith('.gz') else open
-
-
 def _primary_header(path):
-	with _opener(path)(path, 'rb') as fh:
-		return fitsio.read_header_blocks(lambda: fh.read(fitsio.BLOCK))[0]
+	return fitsio.scan_hdus(path, 1)[0].header
 
 
 #--------------------------------------------------------------------------------------------------
@@ -157,20 +152,7 @@ def read_tpf_header(path):
 	the APERTURE image.
 	"""
 	path = str(path)
-	hdus = []
-	with _opener(path)(path, 'rb') as fh:
-		pos = 0
-		while len(hdus) < 3:
-			try:
-				header, cards = fitsio.read_header_blocks(lambda: fh.read(fitsio.BLOCK))
-			except EOFError:
-				break
-			pos += ffi._round_up(len(cards) * 80, fitsio.BLOCK)
-			shape, nbytes = fitsio.data_unit_bytes(header)
-			nbytes += int(header.get('PCOUNT', 0) or 0)
-			hdus.append((header, cards, pos, ffi._round_up(nbytes, fitsio.BLOCK), tuple(int(n) for n in shape)))
-			pos += ffi._round_up(nbytes, fitsio.BLOCK)
-			fh.seek(pos)
+	hdus = fitsio.scan_hdus(path, 3)
 	if len(hdus) < 3:
 		raise ValueError(f"{path}: a target pixel file has a primary HDU, the PIXELS table and the APERTURE image")
 	thdr, _, toff, tbytes, _ = hdus[1]
@@ -272,104 +254,82 @@ def load_tpfs(ctx, files, verify=True):
 	and waiting for this file, and its bytes.
 
 	Every header is read and checked (:func:`read_tpf_header`) before anything is allocated.  The files then stream through two
-	page-locked staging buffers on a second context, the scheme of ``ffi.load_ffis``: while file ``i`` transfers and unpacks, file
+	page-locked staging buffers on a second context (``staging.StagedUpload``): while file ``i`` transfers and unpacks, file
 	``i + 1`` is read (``readinto``; a ``.gz`` is decompressed) straight into the other buffer.  The scalar columns are read out of the
 	staging buffer on the host, so the size of the cubes is known without a device round trip.  ``verify``: the word sum of every
 	table that has a ``DATASUM`` card is formed on the device and compared once all files are in; a mismatch raises
 	``ffi.ChecksumError`` naming file and HDU.  After any exception the staging buffers, events and all cubes are gone.
 	"""
-	from .device import Context, DeviceCube
 	files = [str(f) for f in files]
 	if not files:
 		raise ValueError("load_tpfs: no files")
 	infos = [read_tpf_header(f) for f in files]
-	for h in infos:
-		if h.aperture.bitpix != 32:
-			raise ValueError(f"{h.path}: the APERTURE image has BITPIX {h.aperture.bitpix}, not 32")
-		for key in ('CRVAL1P', 'CRVAL2P'):
-			if key not in h.aperture.header:
-				raise ValueError(f"{h.path}: the APERTURE header lacks the {key} card")
-	# from the first byte of the table to the last of the APERTURE image: what is read from a file
-	span = [(h.table.offset, h.aperture.offset + h.aperture.nbytes - h.table.offset) for h in infos]
-	stage_bytes = max(n for _, n in span)
-	slot_bytes = ffi._round_up(max(h.table.nbytes for h in infos), 256)
+	_check_aperture_units(infos)
 	loaded = []
-	up = None
-	stage, done, d_slots, d_sums = [], [], None, None
+
+	def fresh_cubes(i, out):
+		"""A one-target cube per image column of file ``i``, its pitch from ``T``."""
+		H, W = out.aperture.shape
+		for name in out.cubes:
+			out.cubes[name] = DeviceCube(ctx, 1, len(out.time), H, W)
+		return [cube.ptr for cube in out.cubes.values()], out.cubes['images'].t_pitch
 	try:
-		d_slots = ctx.empty((2, slot_bytes), 'uint8')
-		d_sums = ctx.zeros((len(infos),), 'uint64')
-		ctx.sync()
-		up = Context(ctx.device, high_priority=False)
-		lib = up.lib
-		stage = [ctx.pinned((stage_bytes,), 'uint8') for _ in range(2)]
-		done = [up.event(), up.event()]
-		for i, h in enumerate(infos):
-			s = i % 2
-			tb = h.table
-			stats = {'read_s': 0.0, 'wait_s': 0.0, 'bytes': int(span[i][1])}
-			if i >= 2:
-				t0 = _time.perf_counter()
-				up.event_sync(done[s])                                   # the transfer that last read this staging buffer is over
-				stats['wait_s'] += _time.perf_counter() - t0
-			t0 = _time.perf_counter()
-			ffi._read_into(h.path, stage[s].array, span[i][0], span[i][1])   # page cache / disk -> pinned memory, while file i-1 is in flight
-			stats['read_s'] += _time.perf_counter() - t0
-			d_table = d_slots.ptr + s * slot_bytes
-			up._check(lib.tp_upload_cube_async(up.handle, d_table, tb.nbytes // 4, stage[s].ptr, tb.nbytes // 4, 1, tb.nbytes // 4))
-			up.record(done[s])
-			out = _host_side(h, stage[s].array)                          # (the host reads the staging buffer while the DMA does)
-			out.stats = stats
-			loaded.append(out)
-			H, W = out.aperture.shape
-			T = len(out.time)
-			if T == 0:
-				raise ValueError(f"{h.path}: no row of the PIXELS table has a finite TIME")
-			out.cubes = {name: None for name, _ in IMAGE_COLUMNS}
-			for name, _ in IMAGE_COLUMNS:
-				out.cubes[name] = DeviceCube(ctx, 1, T, H, W)
-			if verify and tb.datasum is not None:
-				up._check(lib.tp_fits_datasum(up.handle, d_table, tb.nbytes, d_sums.ptr + 8 * i))
-			rows = None if out.rows_dropped == 0 else np.ascontiguousarray(out._kept_rows, dtype='int32')
-			offsets = (ctypes.c_int64 * 3)(*[tb.columns[col].offset for _, col in IMAGE_COLUMNS])
-			outs = (ctypes.c_void_p * 3)(*[out.cubes[name].ptr for name, _ in IMAGE_COLUMNS])
-			up._check(lib.tp_tpf_unpack(up.handle, d_table, tb.row_bytes, tb.n_rows, None if rows is None else rows.ctypes.data, T, 3,
-				ctypes.addressof(offsets), H * W, ctypes.addressof(outs), out.cubes['images'].t_pitch))
-			del out._kept_rows
-		t0 = _time.perf_counter()
-		up.sync()
-		loaded[-1].stats['wait_s'] += _time.perf_counter() - t0
+		with _staging(ctx, infos, verify) as st:
+			_stream_files(st, infos, verify, loaded, fresh_cubes)
+			sums = st.finish()
 		if verify:
-			sums = d_sums.to_host()
-			for i, h in enumerate(infos):
-				if h.table.datasum is not None and int(sums[i]) != h.table.datasum:
-					raise ffi.ChecksumError(f"{h.path}: HDU {h.table.hdu}: the data unit sums to {int(sums[i])}, its DATASUM card says {h.table.datasum}")
+			for h, got in zip(infos, sums):
+				check_datasum(h.path, h.table.hdu, got, h.table.datasum)
 	except BaseException:
-		if up is not None and getattr(up, 'handle', None) is not None:
-			try:
-				up.sync()                                                # nothing may still write into a cube that goes back to the cache
-			except Exception: # noqa: B902
-				pass
 		for out in loaded:
-			out.free()
+			out.free()                                                   # (the transfer context has been synced: nothing can write into a cube any more)
 		raise
-	finally:
-		# staging buffers, events and the transfer context go whatever happened
-		if up is not None and getattr(up, 'handle', None) is not None:
-			try:
-				up.sync()
-			except Exception: # noqa: B902
-				pass
-			for e in done:
-				up.lib.tp_event_destroy(up.handle, e)
-		for p in stage:
-			p.free()
-		for d in (d_slots, d_sums):
-			if d is not None:
-				d.free()
-		if up is not None:
-			up.close()
 	return loaded
+
+
+def _span(h):
+	"""``(first byte, bytes)`` of what is read from a file: from the first byte of the table to the last of the APERTURE image."""
+	return h.table.offset, h.aperture.offset + h.aperture.nbytes - h.table.offset
+
+
+def _staging(ctx, infos, verify):
+	"""The :class:`~photometry_amd.staging.StagedUpload` of a run over ``infos``: a slot holds a table, sum ``i`` is that of file ``i``."""
+	return StagedUpload(ctx, max(_span(h)[1] for h in infos), round_up(max(h.table.nbytes for h in infos), 256), len(infos) if verify else 0)
+
+
+def _stream_files(st, infos, verify, loaded, place):
+	"""
+	The per-file body of :func:`load_tpfs` and :func:`load_tpf_groups`: every file of ``infos`` through the staging buffers of ``st``
+	(``staging``: while file ``i`` transfers and unpacks, file ``i + 1`` is read), its :class:`LoadedTPF` without cubes appended to
+	``loaded``, its table summed and its three image columns unpacked to where ``place(i, out)`` says: the device addresses of the
+	three columns of file ``i`` and their ``t_pitch``.
+	"""
+	up = st.up
+	for i, h in enumerate(infos):
+		tb = h.table
+		start, nbytes = _span(h)
+		st.stats = {'read_s': 0.0, 'wait_s': 0.0, 'bytes': int(nbytes)}
+		st.take()
+		st.read(h.path, start, nbytes)
+		st.upload(st.slot, tb.nbytes)
+		st.record()
+		out = _host_side(h, st.buf.array)                                # (the host reads the staging buffer while the DMA does)
+		out.stats = st.stats
+		out.cubes = {name: None for name, _ in IMAGE_COLUMNS}
+		loaded.append(out)
+		H, W = out.aperture.shape
+		T = len(out.time)
+		if T == 0:
+			raise ValueError(f"{h.path}: no row of the PIXELS table has a finite TIME")
+		dst, t_pitch = place(i, out)
+		if verify and tb.datasum is not None:
+			st.datasum(st.slot, tb.nbytes, i)
+		rows = None if out.rows_dropped == 0 else np.ascontiguousarray(out._kept_rows, dtype='int32')
+		offsets = (ctypes.c_int64 * 3)(*[tb.columns[col].offset for _, col in IMAGE_COLUMNS])
+		outs = (ctypes.c_void_p * 3)(*dst)
+		up._check(up.lib.tp_tpf_unpack(up.handle, st.slot, tb.row_bytes, tb.n_rows, None if rows is None else rows.ctypes.data, T, 3,
+			ctypes.addressof(offsets), H * W, ctypes.addressof(outs), t_pitch))
+		del out._kept_rows
 
 
 #--------------------------------------------------------------------------------------------------
@@ -486,7 +446,6 @@ def load_tpf_groups(ctx, files, verify=True, headers=None):
 	lies in two cubes.  ``verify``, :class:`ffi.ChecksumError` and the promise that after any exception everything is freed are those of
 	:func:`load_tpfs`.  ``headers``: the :class:`TPFHeader` of every file when the caller has read them already.
 	"""
-	from .device import Context, DeviceCube
 	files = [str(f) for f in files]
 	if not files:
 		raise ValueError("load_tpf_groups: no files")
@@ -496,85 +455,46 @@ def load_tpf_groups(ctx, files, verify=True, headers=None):
 	_check_aperture_units(infos)
 	shapes = [h.aperture.shape + (h.table.n_rows,) for h in infos]
 	keys, members = bucket_files(shapes)
-	place = {i: (b, j) for b, m in enumerate(members) for j, i in enumerate(m)}
-	span = [(h.table.offset, h.aperture.offset + h.aperture.nbytes - h.table.offset) for h in infos]
-	stage_bytes = max(n for _, n in span)
-	slot_bytes = ffi._round_up(max(h.table.nbytes for h in infos), 256)
+	slot_of = {i: (b, j) for b, m in enumerate(members) for j, i in enumerate(m)}
 	names = [name for name, _ in IMAGE_COLUMNS]
-	loaded, owned, out_groups = [], [], []
-	up = None
-	stage, done, d_slots, d_sums = [], [], None, None
+	loaded, owned, buckets, out_groups = [], [], [], []
+
+	def bucket_slot(i, out):
+		"""Slot ``j`` of the three cubes of file ``i``'s bucket, their pitch from ``NAXIS2``."""
+		b, j = slot_of[i]
+		H, W = out.aperture.shape
+		pitch = buckets[b][names[0]].t_pitch
+		return [buckets[b][name].ptr + j * H * W * pitch * 4 for name in names], pitch
 	try:
-		d_slots = ctx.empty((2, slot_bytes), 'uint8')
-		d_sums = ctx.zeros((len(infos),), 'uint64')
-		buckets = []
 		for (H, W, n_rows), m in zip(keys, members):
 			buckets.append({})
 			for name in names:
 				cube = DeviceCube(ctx, len(m), n_rows, H, W)
 				owned.append(cube)
 				buckets[-1][name] = cube
-		ctx.sync()
-		up = Context(ctx.device, high_priority=False)
-		lib = up.lib
-		stage = [ctx.pinned((stage_bytes,), 'uint8') for _ in range(2)]
-		done = [up.event(), up.event()]
-		for i, h in enumerate(infos):
-			s = i % 2
-			tb = h.table
-			stats = {'read_s': 0.0, 'wait_s': 0.0, 'bytes': int(span[i][1])}
-			if i >= 2:
-				t0 = _time.perf_counter()
-				up.event_sync(done[s])
-				stats['wait_s'] += _time.perf_counter() - t0
-			t0 = _time.perf_counter()
-			ffi._read_into(h.path, stage[s].array, span[i][0], span[i][1])
-			stats['read_s'] += _time.perf_counter() - t0
-			d_table = d_slots.ptr + s * slot_bytes
-			up._check(lib.tp_upload_cube_async(up.handle, d_table, tb.nbytes // 4, stage[s].ptr, tb.nbytes // 4, 1, tb.nbytes // 4))
-			up.record(done[s])
-			out = _host_side(h, stage[s].array)
-			out.stats = stats
-			out.cubes = {name: None for name in names}
-			loaded.append(out)
-			H, W = out.aperture.shape
-			T = len(out.time)
-			if T == 0:
-				raise ValueError(f"{h.path}: no row of the PIXELS table has a finite TIME")
-			if verify and tb.datasum is not None:
-				up._check(lib.tp_fits_datasum(up.handle, d_table, tb.nbytes, d_sums.ptr + 8 * i))
-			b, j = place[i]
-			pitch = buckets[b][names[0]].t_pitch
-			rows = None if out.rows_dropped == 0 else np.ascontiguousarray(out._kept_rows, dtype='int32')
-			offsets = (ctypes.c_int64 * 3)(*[tb.columns[col].offset for _, col in IMAGE_COLUMNS])
-			outs = (ctypes.c_void_p * 3)(*[buckets[b][name].ptr + j * H * W * pitch * 4 for name in names])
-			up._check(lib.tp_tpf_unpack(up.handle, d_table, tb.row_bytes, tb.n_rows, None if rows is None else rows.ctypes.data, T, 3,
-				ctypes.addressof(offsets), H * W, ctypes.addressof(outs), pitch))
-			del out._kept_rows
-		plan, index, moves = plan_groups(shapes, [len(ld.time) for ld in loaded])
-		cubes_of = []
-		for (H, W, T), b, own, members_g in plan:
-			if own:
-				cubes = {name: DeviceCube(ctx, len(members_g), T, H, W, t_pitch=buckets[b][name].t_pitch) for name in names}
-				owned.extend(cubes.values())
-			else:
-				cubes = buckets[b]
-			cubes_of.append(cubes)
-		if any(own for _, _, own, _ in plan):
-			ctx.sync()                                               # the cubes of the sub-groups exist before the other stream writes them
-		for b, src, g, slot in moves:
-			(H, W, _), _, _, _ = plan[g]
-			for name in names:
-				one = H * W * buckets[b][name].t_pitch * 4
-				up._check(lib.tp_memcpy_d2d(up.handle, cubes_of[g][name].ptr + slot * one, buckets[b][name].ptr + src * one, one))
-		t0 = _time.perf_counter()
-		up.sync()
-		loaded[-1].stats['wait_s'] += _time.perf_counter() - t0
+		with _staging(ctx, infos, verify) as st:
+			up = st.up
+			_stream_files(st, infos, verify, loaded, bucket_slot)
+			plan, index, moves = plan_groups(shapes, [len(ld.time) for ld in loaded])
+			cubes_of = []
+			for (H, W, T), b, own, members_g in plan:
+				if own:
+					cubes = {name: DeviceCube(ctx, len(members_g), T, H, W, t_pitch=buckets[b][name].t_pitch) for name in names}
+					owned.extend(cubes.values())
+				else:
+					cubes = buckets[b]
+				cubes_of.append(cubes)
+			if any(own for _, _, own, _ in plan):
+				ctx.sync()                                               # the cubes of the sub-groups exist before the other stream writes them
+			for b, src, g, slot in moves:
+				(H, W, _), _, _, _ = plan[g]
+				for name in names:
+					one = H * W * buckets[b][name].t_pitch * 4
+					up._check(up.lib.tp_memcpy_d2d(up.handle, cubes_of[g][name].ptr + slot * one, buckets[b][name].ptr + src * one, one))
+			sums = st.finish()
 		if verify:
-			sums = d_sums.to_host()
-			for i, h in enumerate(infos):
-				if h.table.datasum is not None and int(sums[i]) != h.table.datasum:
-					raise ffi.ChecksumError(f"{h.path}: HDU {h.table.hdu}: the data unit sums to {int(sums[i])}, its DATASUM card says {h.table.datasum}")
+			for h, got in zip(infos, sums):
+				check_datasum(h.path, h.table.hdu, got, h.table.datasum)
 		for g, ((H, W, T), b, own, members_g) in enumerate(plan):
 			n = len(members_g)
 			cubes = {}
@@ -586,29 +506,9 @@ def load_tpf_groups(ctx, files, verify=True, headers=None):
 				loaded[i].cubes = {name: cubes[name].slice0(slot, 1) for name in names}
 			out_groups.append(TpfGroup((H, W, T), cubes, [cubes_of[g][name] for name in names], [loaded[i] for i in members_g]))
 	except BaseException:
-		if up is not None and getattr(up, 'handle', None) is not None:
-			try:
-				up.sync()                                                # nothing may still write into a cube that goes back to the cache
-			except Exception: # noqa: B902
-				pass
 		for cube in owned:
-			cube.free()
+			cube.free()                                                  # (the transfer context has been synced: nothing can write into a cube any more)
 		raise
-	finally:
-		if up is not None and getattr(up, 'handle', None) is not None:
-			try:
-				up.sync()
-			except Exception: # noqa: B902
-				pass
-			for e in done:
-				up.lib.tp_event_destroy(up.handle, e)
-		for p in stage:
-			p.free()
-		for d in (d_slots, d_sums):
-			if d is not None:
-				d.free()
-		if up is not None:
-			up.close()
 	return out_groups, index
 
 
@@ -751,18 +651,17 @@ class TpfStampSource(MemoryStampSource):
 		H, W = loaded.aperture.shape
 		catalog = dict(catalog)
 		targets = None if targets is None else dict(targets)
-		need = lambda d: d is not None and 'row' not in d and 'column' not in d and 'ra' in d and 'dec' in d # noqa: E731
-		if wcs is None and loaded.wcs_cards and (need(catalog) or need(targets)):
+		if wcs is None and loaded.wcs_cards and (_needs_projection(catalog) or _needs_projection(targets)):
 			wcs = loaded.wcs_cards
 		if wcs is not None:
 			from .wcs import as_wcs
 			cube = (loaded.cubes or {}).get('images')
 			wcs = as_wcs(wcs, ctx=None if cube is None else cube.ctx)
-			if need(catalog):
+			if _needs_projection(catalog):
 				px = wcs.all_world2pix(np.column_stack((catalog['ra'], catalog['dec'])), 0)
 				catalog['column'] = (px[:, 0] + c0).astype('float32')
 				catalog['row'] = (px[:, 1] + r0).astype('float32')
-			if need(targets):
+			if _needs_projection(targets):
 				pos = np.array([wcs.all_world2pix(np.array([[r, d]], dtype='float64'), 0)[0]
 					for r, d in zip(np.asarray(targets['ra'], dtype='float64'), np.asarray(targets['dec'], dtype='float64'))]).reshape(-1, 2)
 				targets['column'], targets['row'] = pos[:, 0] + c0, pos[:, 1] + r0

@@ -9,6 +9,7 @@ import os
 import numpy as np
 import pytest
 import ffi_common as fc
+from alloc_common import count_allocations
 from photometry_amd import ffi, frameio, motion, prepare
 
 pytestmark = pytest.mark.gpu
@@ -92,20 +93,24 @@ def test_tess_vectors_headers_and_defaults(tess_set, tess_loaded):
 
 
 @pytest.mark.parametrize('hdu,row,col', [(1, 5, 10), (2, 2060, 100)])
-def test_a_flipped_byte_outside_the_science_window(ctx, tess_set, tmp_path, hdu, row, col):
+def test_a_flipped_byte_outside_the_science_window(ctx, tess_set, tmp_path, monkeypatch, hdu, row, col):
 	blob = bytearray(tess_set['blobs'][0])
 	h = ffi.read_ffi_header(tess_set['files'][0])
 	unit = h.image if hdu == 1 else h.uncert
 	blob[unit.offset + 4 * (row * 2136 + col) + 1] ^= 0x10
 	path = fc.write(tmp_path / NAMES[0], bytes(blob))
+	live = count_allocations(ctx, monkeypatch)                             # every allocation and release on ctx, device and page-locked
 	with pytest.raises(ffi.ChecksumError) as e:
 		ffi.load_ffis(ctx, [path])
 	assert path in str(e.value) and f'HDU {hdu}' in str(e.value) and f'HDU {3 - hdu}' not in str(e.value)
+	assert live == {'device': 0, 'host': 0}, live
 	loaded = ffi.load_ffis(ctx, [path], verify=False)                      # the same file loads unverified: the window is untouched
+	assert live == {'device': 2, 'host': 0}, live                          # the counter counts: the two stacks
 	img, unc = tess_set['bits'][0]
 	assert np.array_equal(loaded.raw.to_host()[0].view('uint32'), img[0:2048, 44:2092])
 	assert np.array_equal(loaded.raw_err.to_host()[0].view('uint32'), unc[0:2048, 44:2092])
 	loaded.free()
+	assert live == {'device': 0, 'host': 0}, live
 
 
 def test_tess_files_without_ffiindex(ctx, tess_set, tmp_path):

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 import ffi_common as fc
 import tpf_common as tc
+from alloc_common import count_allocations
 from photometry_amd import ffi, tpf
 
 pytestmark = pytest.mark.gpu
@@ -119,19 +120,7 @@ def test_a_flipped_byte_raises_and_frees_everything(ctx, seven, tmp_path, monkey
 	files = list(seven['files'])
 	files[4] = path
 	# every allocation and release on ctx, device and page-locked, counted at the C entries
-	live = {'device': 0, 'host': 0}
-	lib = ctx.lib
-	calls = {name: getattr(lib, name) for name in ('tp_malloc', 'tp_free', 'tp_host_alloc', 'tp_host_free')}
-
-	def counting(name, kind, step):
-		def call(handle, *args):
-			rc = calls[name](handle, *args)
-			if rc == 0 and handle == ctx.handle:
-				live[kind] += step
-			return rc
-		return call
-	for name, kind, step in (('tp_malloc', 'device', 1), ('tp_free', 'device', -1), ('tp_host_alloc', 'host', 1), ('tp_host_free', 'host', -1)):
-		monkeypatch.setattr(lib, name, counting(name, kind, step))
+	live = count_allocations(ctx, monkeypatch)
 	with pytest.raises(ffi.ChecksumError, match=r'flipped_tp\.fits: HDU 1'):
 		tpf.load_tpf_groups(ctx, files)
 	assert live == {'device': 0, 'host': 0}, live

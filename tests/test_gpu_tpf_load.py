@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import ffi_common as fc
 import tpf_common as tc
+from alloc_common import count_allocations
 from photometry_amd import ffi, tpf
 
 pytestmark = pytest.mark.gpu
@@ -96,18 +97,22 @@ def test_vectors_and_header_derived_attributes(three, loaded3):
 		assert ld.stats['bytes'] == info['aperture_offset'] + info['aperture_bytes'] - info['table_offset'] and ld.stats['read_s'] > 0
 
 
-def test_a_flipped_byte_outside_the_unpacked_columns(ctx, three, tmp_path):
+def test_a_flipped_byte_outside_the_unpacked_columns(ctx, three, tmp_path, monkeypatch):
 	blob, rec, ap, info = three['made'][0]
 	at = info['table_offset'] + 5 * info['row_bytes'] + info['columns']['RAW_CNTS'] + 7                       # inside RAW_CNTS of row 5
 	bad = bytearray(blob)
 	bad[at] ^= 0x10
 	path = fc.write(tmp_path / 'flipped_tp.fits', bytes(bad))
+	live = count_allocations(ctx, monkeypatch)                                # every allocation and release on ctx, device and page-locked
 	with pytest.raises(ffi.ChecksumError, match=r'flipped_tp\.fits: HDU 1'):
 		tpf.load_tpfs(ctx, [three['files'][1], path], verify=True)
+	assert live == {'device': 0, 'host': 0}, live
 	(ld,) = tpf.load_tpfs(ctx, [path], verify=False)
+	assert live == {'device': 3, 'host': 0}, live                             # the counter counts: the three cubes of the file
 	assert np.array_equal(ld.cubes['images'].to_host()[0].view('uint32'), tc.host_cube(rec, 'FLUX'))
 	ld.free()
 	assert all(c is None for c in ld.cubes.values())
+	assert live == {'device': 0, 'host': 0}, live
 
 
 def test_a_double_image_column_is_refused_before_any_allocation(ctx, three, tmp_path, monkeypatch):

@@ -56,7 +56,7 @@ def main():
 	ap.add_argument('--out', default=None)
 	a = ap.parse_args()
 	import numpy as np
-	from photometry_amd import ffi, frameio
+	from photometry_amd import ffi, frameio, staging
 	from photometry_amd.device import Context
 
 	def emit(res):
@@ -92,7 +92,7 @@ def main():
 		for _ in range(a.repeats):
 			t0 = time.perf_counter()
 			for h in infos:
-				ffi._read_into(h.path, stage.array, h.image.offset, span)
+				staging.read_into(h.path, stage.array, h.image.offset, span)
 			times.append(time.perf_counter() - t0)
 		emit({'step': 'read', 'ms_per_frame': min(times) / T * 1e3, 'GB_per_s': span * T / min(times) / 1e9, 'all_s': times})
 

@@ -61,7 +61,7 @@ def main():
 	ap.add_argument('--out', default=None)
 	a = ap.parse_args()
 	import numpy as np
-	from photometry_amd import ffi, tpf
+	from photometry_amd import staging, tpf
 	from photometry_amd.device import Context, DeviceCube
 
 	def emit(res):
@@ -100,7 +100,7 @@ def main():
 		for _ in range(a.repeats):
 			t0 = time.perf_counter()
 			for h in infos:
-				ffi._read_into(h.path, stage.array, h.table.offset, span)
+				staging.read_into(h.path, stage.array, h.table.offset, span)
 			times.append(time.perf_counter() - t0)
 		emit({'step': 'read', 'ms_per_file': min(times) / N * 1e3, 'GB_per_s': span * N / min(times) / 1e9, 'all_s': times})
 
