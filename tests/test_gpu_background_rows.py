@@ -8,7 +8,8 @@ row, the partial row), the frames of a wavefront and the blocks of a series (cad
 mask decides on (either side of the cutoff, both zeros, the infinities, NaN), frames with a masked value in every row, frames
 more than half and wholly masked, beside a target left clean.
 
-Asserted, for the 15 x 15 and 11 x 11 instances and the 16 x 16 one (the instance that tests every slot): the stamp background
+Asserted, for the 15 x 15 and 11 x 11 instances (also at the other pixel counts they serve: an empty partial row, a full one but
+for a pixel) and the 16 x 16 one (the instance that tests every slot): the stamp background
 of tp_background_stamp and of tp_background_sumimage bit for bit the oracle's (oracle/backgrounds.py, NaN positions included),
 the smoothed series bit for bit tp_smooth_time's, the sum image within 1e-12 of the oracle's chain from the raw cube (float64
 sums of the same float32 differences in another order: the bound of test_gpu_raw_chain.py).
@@ -25,7 +26,11 @@ VALUES = {
 	'9e4': np.float32(9e4),
 }
 MASKED = ('nan', 'pinf', 'ninf', 'minus1', 'above', '9e4')      # the others are kept: -0.0 is not < 0, the cutoff itself is not > cutoff
-SHAPES = [(2, 40, 15, 15), (2, 40, 11, 11), (2, 12, 16, 16)]  # a full block + a block of 8 frames: <28,*>, <15,*>; one short block: <-1,*>
+SHAPES = [(2, 40, 15, 15), (2, 40, 11, 11), (2, 12, 16, 16),  # a full block + a block of 8 frames: <28,*>, <15,*>; one short block: <-1,*>
+	# the other fill levels of the two tuned instances' partial row (they serve n_pix 224 .. 231 and 120 .. 127): 224 and 120 with no
+	# pixel in it, 228 (also the one-pass kernel's frame_stride += 8), 231 and 127 with seven
+	(2, 40, 14, 16), (2, 40, 12, 19), (2, 40, 7, 33), (2, 40, 15, 8), (2, 40, 1, 127)]
+CUTOFF_SHAPES = SHAPES[:2] + [(2, 40, 14, 16), (2, 40, 15, 8)]   # ... and the sizes at which the <-1> instances run without a partial row
 
 
 @pytest.fixture(scope='module')
@@ -61,7 +66,7 @@ def _places(shape):
 	P = H * W
 	jfull = P // 8
 	partial = list(range(8 * jfull, P)) or [P - 1]          # 16 x 16 has no partial row: its last pixel
-	pixels = [0, 7, 8, 8 * jfull - 1] + partial
+	pixels = [p for p in [0, 7, 8, 8 * jfull - 1] + partial if 0 <= p < P]      # stamps of fewer than nine pixels lack some of them
 	cadences = [c for c in (0, 7, 8, 31, 32, 39) if c < T] + ([T - 1] if T < 40 else [])
 	return P, pixels, cadences
 
@@ -150,7 +155,7 @@ def test_random_nan_rows(ctx):
 	_check(ctx, raw, err, q)
 
 
-@pytest.mark.parametrize("shape", SHAPES[:2], ids=lambda s: f"{s[2]}x{s[3]}")
+@pytest.mark.parametrize("shape", CUTOFF_SHAPES, ids=lambda s: f"{s[2]}x{s[3]}")
 @pytest.mark.parametrize("cutoff", [-1.0, -0.0, float('nan')])
 def test_cutoff_without_an_order(ctx, shape, cutoff):
 	"""A negative or NaN cutoff masks every pixel (-0.0: all but the zeros): the integer pre-test of a row does not apply and the
