@@ -163,7 +163,7 @@ int tp_sumimage(tp_ctx* ctx, const tp_cube_desc* desc, const float* d_images,
  *   d_flags int32: bit0 minimum aperture used, bits1-4 mask touches stamp edge (row 0, last row,
  *   column 0, last column), bit5 K2P2NoStars, bit6 no mask passed the size filter,
  *   bits 8+ error kind (1 no flux, 2 zero KDE bandwidth, 3 no watershed peak, 4 target outside
- *   stamp, 5 too many masks, 6 no catalog star in mask);
+ *   stamp, 5 too many masks, 6 no catalog star in mask, 7 empty KDE sample: every positive flux >= 70000);
  *   d_contamination float64 (AP_CONT, NaN if undefined); d_diag optional float64 [n_targets][8] =
  *   (CUT, MODE, MAD1, KDE bandwidth, FFT-grid mode guess, n positive pixels, min|S-CUT|, n masks);
  *   d_cat_in_mask optional uint8 [n_catalog]: star falls inside the final mask (skip_targets).   */

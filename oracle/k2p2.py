@@ -197,7 +197,7 @@ def watershed(image, markers, mask):
 #--------------------------------------------------------------------------------------------------
 # A4: watershed segmentation of each cluster
 #--------------------------------------------------------------------------------------------------
-def k2p2WS(flux0, labels_grid, core, saturated_masks=None, ws_thres=0, ws_footprint=3, ws_blur=0.5, catalog=None):
+def k2p2WS(flux0, labels_grid, core, saturated_masks=None, ws_thres=0, ws_footprint=3, ws_blur=0.5, catalog=None, trace=None):
 	"""
 	``k2p2WS`` (k2p2v2.py:89-288) with ``ws_alg='flux'``, on grid arrays.
 
@@ -207,6 +207,8 @@ def k2p2WS(flux0, labels_grid, core, saturated_masks=None, ws_thres=0, ws_footpr
 		core: core flags.
 		saturated_masks: ``None`` or dict label -> bool image (k2p2v2.py:486-492).
 		catalog: ``(n, 3)`` array of (column, row, tmag) or ``None``.
+		trace: ``None`` or a list that receives one dict per cluster (``lab``, ``Z``, ``distance``, ``peaks``, ``markers`` and, where
+			the flood ran, ``labels_ws``): what the tests' case builders assert about their inputs.  No effect on the result.
 
 	Returns the new label grid (``-2`` outside ``idx``, ``-1`` noise).
 	"""
@@ -249,11 +251,15 @@ def k2p2WS(flux0, labels_grid, core, saturated_masks=None, ws_thres=0, ws_footpr
 					local_maxi[imax] = True
 
 		markers = ndimage.label(local_maxi)[0]
+		if trace is not None:
+			trace.append({'lab': lab, 'Z': Z, 'distance': distance, 'peaks': local_maxi_loc, 'markers': markers})
 
 		if np.all(local_maxi == 0):
 			Labels[class_member] = -1
 		else:
 			labels_ws = watershed(-distance0, markers, mask=Z)
+			if trace is not None:
+				trace[-1]['labels_ws'] = labels_ws
 			no_labels = len(set(labels_ws.flatten().tolist()))
 			Labels[class_member] = -1
 			idx = (labels_ws == 1) & (Z != 0)
@@ -344,8 +350,10 @@ def k2p2FixFromSum(SumImage, thresh=1, min_no_pixels_in_mask=8, min_for_cluster=
 			saturated_masks = {lab: smask[u] for u, lab in enumerate(dummy_labels)}
 		else:
 			saturated_masks = None
+		if full_output:
+			info['ws'] = []      # (the per-cluster trace is kept for a caller that asks for the intermediate images only)
 		labels = k2p2WS(SumImage, labels_ini, core, saturated_masks=saturated_masks,
-			ws_thres=ws_thres, ws_footprint=ws_footprint, ws_blur=ws_blur, catalog=catalog)
+			ws_thres=ws_thres, ws_footprint=ws_footprint, ws_blur=ws_blur, catalog=catalog, trace=info.get('ws'))
 	else:
 		labels = labels_ini
 	info['labels'] = labels

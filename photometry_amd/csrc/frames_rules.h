@@ -258,7 +258,7 @@ inline Decision decide_target(const Attempt& t)
 	if (fl & 32) d.log(1);
 	if (fl & 1) d.log((fl & (32 | 64)) ? 2 : 3);
 	if (kind == 5) { d.log(4); return d.end(Decision::ERROR, kStatusError); }
-	if (kind >= 1 && kind <= 4) { d.log(5); d.kind = kind; return d.end(Decision::ERROR, kStatusError); }   // an uncaught exception upstream
+	if ((kind >= 1 && kind <= 4) || kind == 7) { d.log(5); d.kind = kind; return d.end(Decision::ERROR, kStatusError); }   // an uncaught exception upstream (plugins._MASK_EXCEPTIONS)
 	if (fl & kEdgeBits) {
 		const int64_t* before = t.stamp;
 		int64_t* after = d.stamp;

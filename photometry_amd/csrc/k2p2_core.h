@@ -66,6 +66,7 @@ enum : int32_t {
 	ERR_TARGET_OUTSIDE = 4,     // IndexError at photometry.py:107
 	ERR_TOO_MANY_MASKS = 5,     // photometry.py:114-116
 	ERR_NO_TARGETS_IN_MASK = 6, // photometry.py:227-230
+	ERR_EMPTY_SAMPLE = 7,       // statsmodels bw_scott on an empty sample: ZeroDivisionError, 0 ** (-0.2) (every positive flux >= 70000)
 };
 
 struct Params {
@@ -547,6 +548,7 @@ inline TP_DEV int threshold(Shared& k, const Params& prm, const Target& t, doubl
 	nc = sum_ired(k);
 	TP_SYNC();
 	if (t.diag) { TP_SERIAL { t.diag[5] = (double)nflux; } }
+	if (nc == 0) return ERR_EMPTY_SAMPLE;   // bw_scott's n ** (-0.2) with n = 0 raises (bandwidths.py); the plugin does not catch it
 
 	// --- bw_scott: 1.059 * min(std(ddof=1), IQR/1.349) * n^-0.2   (bandwidths.py)
 	double bw;
@@ -561,14 +563,11 @@ inline TP_DEV int threshold(Shared& k, const Params& prm, const Target& t, doubl
 		TP_SYNC();
 		const double std_dev = sqrt(var);
 		double A = std_dev;
-		if (nc > 0) {
-			const double IQR = (score_at_percentile(k.srt, nc, 75.0) - score_at_percentile(k.srt, nc, 25.0)) / 1.349;
-			if (IQR > 0) A = (std_dev < IQR || tp_isnan(std_dev)) ? std_dev : IQR; // np.minimum propagates NaN
-		}
+		const double IQR = (score_at_percentile(k.srt, nc, 75.0) - score_at_percentile(k.srt, nc, 25.0)) / 1.349;
+		if (IQR > 0) A = (std_dev < IQR || tp_isnan(std_dev)) ? std_dev : IQR; // np.minimum propagates NaN
 		// n ** (-0.2) via exp/log would not be bit-stable; use pow from the toolchain only here
 		bw = 1.059 * A * pow((double)nc, -0.2);
 	}
-	if (nc == 0) bw = tp_nan();
 	TP_K2P2_CLOCK(k, 13);
 	if (bw == 0.0) return ERR_BANDWIDTH_ZERO;
 
@@ -577,7 +576,7 @@ inline TP_DEV int threshold(Shared& k, const Params& prm, const Target& t, doubl
 	{
 		const int M = kGrid;
 		const double a = k.srt[0] - 3.0 * bw;
-		const double b = ((nc > 0) ? k.srt[nc - 1] : tp_nan()) + 3.0 * bw;
+		const double b = k.srt[nc - 1] + 3.0 * bw;
 		const double delta = (b - a) / (double)(M - 1);   // np.linspace retstep
 		const double RANGE = b - a;
 		double* binned = k.grid; double* dens = k.grid; double* fre = k.grid; double* fim = k.grid + M; // the transforms work in place: dens overwrites binned
@@ -1020,10 +1019,12 @@ inline TP_DEV void gaussian_blur(Shared& k, const Params& prm, const double* in,
 
 // skimage.segmentation.watershed(-Z, markers, mask=Z) (connectivity 1, no compactness / lines):
 // priority flood, a neighbour is labelled when it is pushed, pops in (value, age) order.
-// in: k.mark (markers); out: k.wsout.  The image values -Z[p] of a cluster are distinct floats, so the
-// pop order is the order of the values: every in-mask pixel gets its RANK (brightest = 0; computed in
-// parallel, exact ties broken by pixel index instead of push age), and the heap becomes a bit set of
-// ranks with a two-level find-first-set -- O(1) per push / pop instead of LDS heap sifts.
+// in: k.mark (markers); out: k.wsout.  Where the image values -Z[p] of a cluster are distinct floats -- ordinary
+// photometry -- the pop order is the order of the values: every in-mask pixel gets its RANK (brightest = 0; computed
+// in parallel), and the heap becomes a bit set of ranks with a two-level find-first-set -- O(1) per push / pop instead
+// of LDS heap sifts.  A cluster that holds EQUAL values (a saturated plateau, clipped or quantised data) pops them in
+// push order, by age, which no rank fixed in advance can state: such a cluster is found after the ranking (two
+// neighbours in rank order are equal) and takes the flood by LEVELS below (one FIFO per distinct value).
 inline TP_DEV void watershed(Shared& k, int nmark) {
 	const int P = k.P, H = k.H, W = k.W;
 	// How many marker labels survive `markers *= mask`?  With a single one the flood is simply "every in-mask
@@ -1086,6 +1087,81 @@ inline TP_DEV void watershed(Shared& k, int nmark) {
 	const int nwords = (P + 31) / 32;
 	TP_PAR_FOR(w, nwords) words[w] = 0u;
 	TP_SYNC();
+	// equal values in the cluster?  (then two neighbours in rank order are equal)
+	TP_LANE_LOOP(l) {
+		int e = 0;
+		for (int r = l; r + 1 < nz; r += 64) e |= (k.Z[ord[r]] == k.Z[ord[r + 1]]) ? 1 : 0;
+		k.ired[l] = e;
+	}
+	TP_SYNC();
+	const int ties = or_ired(k);
+	TP_SYNC();
+	if (ties) {
+		// The flood by levels.  The LEVEL of a pixel is the number of strictly larger values in the cluster: the rank of the first
+		// pixel of its run of equal values, so the ranks L .. L + n - 1 of a run of n are slots of `ord` that belong to level L alone --
+		// its FIFO: a push writes ord[L + tail[L]++], a pop reads ord[L + head[L]++], and the age counter of the reference grows with
+		// every push, so first in, first out IS (value, age) order.  The markers all have age 0 and enter in raster order, as the
+		// reference's heap settles them (by pixel index).  The bit set ranges over levels (bit L set <=> the FIFO of L is not empty); its
+		// lowest set bit is found by the scan of the large-cluster path below, whatever the cluster's size: equal values are rare.
+		// Scratch: the two counters per level are int32 in k.dist (P doubles, 2 nz <= 2 P counters; its compacted values are no longer
+		// read: the runs are compared through k.Z) -- nothing of the threshold phase is live here, and k.tmp keeps the compacted pixels.
+		int32_t* head = (int32_t*)k.dist;
+		int32_t* tail = head + nz;
+		// (a lane owns a contiguous chunk of ranks: it walks back to the start of the run its first rank lies in, once, and carries the
+		// level forward -- linear in the cluster's size however long a plateau's run of equal values is)
+		const int rchunk = (nz + 63) / 64;
+		TP_LANE_LOOP(l) {
+			const int r0 = l * rchunk;
+			if (r0 < nz) {
+				double zprev = k.Z[ord[r0]];
+				int L = r0;
+				while (L > 0 && k.Z[ord[L - 1]] == zprev) --L;
+				for (int r = r0; r < r0 + rchunk && r < nz; ++r) {
+					const int px = ord[r];
+					const double z = k.Z[px];
+					if (z != zprev) { L = r; zprev = z; }
+					rank[px] = (lab_t)L;
+					head[r] = 0; tail[r] = 0;
+				}
+			}
+		}
+		TP_SYNC();
+		TP_SERIAL {
+			const int nzw = (nz + 31) >> 5;
+			for (int c = 0; c < nz; ++c) {
+				const int p = cp[c];
+				if (k.wsout[p] == 0) continue;
+				const int L = rank[p];
+				ord[L + tail[L]] = p; tail[L] += 1;
+				words[L >> 5] |= (1u << (L & 31));
+			}
+			int wscan = 0;
+			while (true) {
+				while (wscan < nzw && words[wscan] == 0u) ++wscan;
+				if (wscan >= nzw) break;
+				const int L = wscan * 32 + __builtin_ctz(words[wscan]);
+				const int px = ord[L + head[L]];
+				head[L] += 1;
+				if (head[L] == tail[L]) words[wscan] &= ~(1u << (L & 31));
+				const int lbl = k.wsout[px];
+				const int r = row_of(k, px), c = px - r * W;
+				const int nbr[4] = {r - 1, r, r, r + 1};      // the reference's order of the neighbours: -W, -1, +1, +W
+				const int nbc[4] = {c, c - 1, c + 1, c};
+				for (int q = 0; q < 4; ++q) {
+					if (nbr[q] < 0 || nbr[q] >= H || nbc[q] < 0 || nbc[q] >= W) continue;
+					const int nb = nbr[q] * W + nbc[q];
+					if (k.Z[nb] == 0.0 || k.wsout[nb] != 0) continue;      // not in mask / labelled already
+					k.wsout[nb] = lbl;
+					const int Ln = rank[nb];
+					ord[Ln + tail[Ln]] = nb; tail[Ln] += 1;
+					words[Ln >> 5] |= (1u << (Ln & 31));
+					if ((Ln >> 5) < wscan) wscan = Ln >> 5;
+				}
+			}
+		}
+		TP_SYNC();
+		return;
+	}
 	// seeds: the ranks of the marker pixels (parallel, the bit set is an OR)
 	TP_PAR_FOR(p, P) if (k.wsout[p] != 0) { const int r = rank[p]; TP_ATOMIC_OR(&words[r >> 5], 1u << (r & 31)); }
 	TP_SYNC();

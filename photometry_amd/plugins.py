@@ -575,7 +575,8 @@ K2P2_HEADERS = (('KP_THRES', 'thresh', 'K2P2 sum-image threshold'), ('KP_MIPIX',
 
 #: error kinds of the device flags (include/tessphot_hip.h) that are uncaught exceptions in the reference's plugin
 _MASK_EXCEPTIONS = {1: "K2P2NoFlux: No measured flux in sum-image", 2: "Selected KDE bandwidth is 0. Cannot estimate density.",
-	3: "attempt to get argmin of an empty sequence", 4: "index out of bounds for the target pixel"}
+	3: "attempt to get argmin of an empty sequence", 4: "index out of bounds for the target pixel",
+	7: "0.0 cannot be raised to a negative power"}
 
 
 def mask_outcome(flags, logger):

@@ -7,6 +7,9 @@
 #include <cmath>
 #include <cstring>
 
+// bytes of work arrays per target: what decides between the LDS-resident kernel (up to 160 KiB) and the one on HBM scratch
+extern "C" long long hostsim_k2p2_shared_bytes(int n_pixels) { return (long long)k2p2::shared_bytes(n_pixels); }
+
 extern "C" int hostsim_k2p2(int n_targets, int H, int W, const double* sumimage,
 	const int64_t* cat_offsets, const float* cat_column_stamp, const float* cat_row_stamp, const float* cat_tmag,
 	const float* cat_column, const float* cat_row, const int64_t* cat_starid,

@@ -284,10 +284,10 @@ def test_decision_equals_the_plugin_flag_bits_and_kinds(driver):
 	cases = []
 	mask, sumimage = _image(4)
 	k = 0
-	for edges, bits, kind in itertools.product(range(0, 32, 2), itertools.product((0, 1), (0, 32), (0, 64)), range(7)):
+	for edges, bits, kind in itertools.product(range(0, 32, 2), itertools.product((0, 1), (0, 32), (0, 64)), range(8)):
 		flags = edges | sum(bits) | (kind << 8)
-		limits, attempts = _LIMITS[(k // 7) % len(_LIMITS)], 1 + (k // 3) % 2      # (k % 7 is the kind: every kind meets every budget)
-		budget = _budgets(flags, limits, mask, sumimage)[k % 4]
+		limits, attempts = _LIMITS[(k // 8) % len(_LIMITS)], 1 + (k // 3) % 2      # (k % 8 is the kind, 7 -- the empty KDE sample -- included)
+		budget = _budgets(flags, limits, mask, sumimage)[(k + k // 8) % 4]           # (... and every kind meets every budget)
 		cases.append((flags, 3 if flags & 1 else 1, _STAMP, limits, attempts, budget, mask, sumimage))
 		k += 1
 	outcomes = _check_decisions(driver, cases)
