@@ -188,7 +188,8 @@ __global__ __launch_bounds__(kMeshThreads) void tp_bkg_mesh_kernel(MeshArgs a)
 	// ---- SigmaClip(3, maxiters = 5) on the rank range [lo, hi), then the SExtractor estimate.  The keys are sorted, so what a pass
 	// clips is a piece at each end of the range: found by two binary searches, and the sums of the kept set follow by taking the
 	// clipped keys' contributions off running sums (round 4 made three strided passes over the whole range and four workgroup
-	// reductions per iteration).  The sums run over x - c, c = the first median: the one-pass variance then has nothing to cancel.
+	// reductions per iteration), or, where that would leave rounding noise, by summing the kept range again (below).  The sums run
+	// over x - c, c = the first median: the one-pass variance then has nothing to cancel.
 	double result = __builtin_nan("");
 	int nkept = 0;
 	if (n > 0) {
@@ -197,6 +198,7 @@ __global__ __launch_bounds__(kMeshThreads) void tp_bkg_mesh_kernel(MeshArgs a)
 		double s1 = 0.0, s2 = 0.0;
 		for (int i = tid; i < n; i += kMeshThreads) { const double d = (double)keys[i] - c0; s1 += d; s2 += d * d; }
 		mesh_block_sum2(s1, s2, red);
+		double s2_ref = s2;        // s2 when it was last summed directly (below)
 		double med = 0.0, mean = 0.0, sd = 0.0;
 		for (int it = 0; it <= 5; ++it) {
 			const int m = hi - lo;
@@ -223,9 +225,24 @@ __global__ __launch_bounds__(kMeshThreads) void tp_bkg_mesh_kernel(MeshArgs a)
 				r1 += d; r2 += d * d;
 			}
 			mesh_block_sum2(r1, r2, red);
-			s1 -= r1; s2 -= r2;
 			lo += nb; hi -= na;
 			if (hi <= lo) break;       // (cannot happen: the median is never clipped)
+			// Taking the clipped keys off leaves s2 with the rounding of the sums it came from: at most ~2^-46 s2_ref absolute (some 2^7
+			// roundings of 2^-53 each over the passes since), s2_ref = s2 when it was last summed directly.  A narrow cell with bright
+			// outliers (four float32 steps wide at level 1000, a hundred stars' pixels) keeps 1e-16 of s2: what the subtraction leaves
+			// there is that rounding, a variance of noise or below zero, and the next pass clips everything but the median.  So below
+			// 2^-24 s2_ref both sums are taken again over [lo, hi): the variance then stays within 2^-22 (std: 1.2e-7 relative, against
+			// the 1e-6 std no decision of a comparable cell comes near, tests/test_mesh_cells_host.py), and s1's error, bounded through
+			// Cauchy-Schwarz by the same s2_ref, moves neither.  25 pixels of a star at the cut-off over a sky of noise 3 keep 2^-22 of
+			// s2: the re-sum is for cells that are flat to rounding, not for ordinary ones (the frames of bench.py's full-frame leg and of
+			// tests/test_gpu_fullframe.py come out bit for bit as before).  s2, r2 and s2_ref come out of the block reductions: the same
+			// on every thread, so the branch is uniform and the result does not depend on the launch.
+			if (s2 - r2 < s2_ref * 0x1p-24) {
+				s1 = 0.0; s2 = 0.0;
+				for (int i = lo + tid; i < hi; i += kMeshThreads) { const double d = (double)keys[i] - c0; s1 += d; s2 += d * d; }
+				mesh_block_sum2(s1, s2, red);
+				s2_ref = s2;
+			} else { s1 -= r1; s2 -= r2; }
 		}
 		if (sd == 0.0) result = mean;
 		else if (fabs(mean - med) / sd < 0.3) result = 2.5 * med - 1.5 * mean;
