@@ -28,7 +28,8 @@
 //      of the partner lane: DPP quad_perm / row_half_mirror) turns two ascending runs into two bitonic halves, the
 //      remaining stages are ascending merges; a cross-lane compare-exchange is one DPP move + one v_med3_f32 against
 //      a per-lane -inf / +inf constant (min for the lower lane, max for the upper);
-//   3. the sorted values are staged in LDS where they can be indexed by rank.  The kept set of the sigma clipping is
+//   3. the sorted values are staged in LDS where they can be indexed by rank (rank r at word r of the frame's area; the
+//      range is kept as byte addresses).  The kept set of the sigma clipping is
 //      always a contiguous rank range: the median is two LDS reads, and the clipped ranks are found by walking in from
 //      both ends of the range, eight ranks per step (one per lane of the frame), summing what leaves the range as it
 //      goes.  The 3-sigma test is evaluated without division or square root: x is clipped iff
@@ -182,13 +183,23 @@ __device__ __forceinline__ void cross_stage(float (&v)[R], float sel) {
 // ascending bitonic MERGE of a lane's R values (strides R/2..1)
 template <int R> __device__ __forceinline__ void local_merge(float (&v)[R]) { BitonicStage<R, R, R / 2>::run(v); }
 
-// LDS index of rank r of a staged frame: every run of 32 ranks is followed by 4 pad words, so that the 16-byte stores of the
-// lanes of a frame fall into different banks
-__device__ __forceinline__ int rank_idx(int r) { return r + ((r >> 5) << 2); }
-// the staged value of rank r (0 <= r < 256); unsigned index arithmetic: the signed form cost two more address instructions
-__device__ __forceinline__ float rank_read(const float* fr, int r) {
-	const unsigned u = (unsigned)r;
-	return fr[u + ((u >> 5) << 2)];
+// A staged frame holds rank r at word r of its area (linear: the eight 16-byte stores of a frame's lanes lie 128 bytes apart and
+// share their banks -- timed against a padded layout).  The sigma clipping keeps its rank range as LDS BYTE
+// ADDRESSES, so that a rank is read without address arithmetic.
+typedef __attribute__((address_space(3))) const float lds_cfloat;
+__device__ __forceinline__ int lds_addr(const float* p) { return (int)(unsigned)(uintptr_t)(lds_cfloat*)p; }
+__device__ __forceinline__ float lds_read(int addr) { return *(lds_cfloat*)(uintptr_t)(unsigned)addr; }
+// the buffer loads of a lane's N pixel rows, `row_b` bytes apart: ONE running scalar offset (N offsets j * row_b, live across the
+// persistent loop of the one-pass kernel, filled the scalar file: 34 spills); the empty statement keeps the additions where they are
+template <int N>
+__device__ __forceinline__ void load_rows(float (&u)[N], const __amdgpu_buffer_rsrc_t rsrc, const int voff, const int row_b) {
+	int so = 0;
+#pragma unroll
+	for (int j = 0; j < N; ++j) {
+		u[j] = __int_as_float(__builtin_amdgcn_raw_buffer_load_b32(rsrc, voff, so, 0));
+		so += row_b;
+		asm volatile("" : "+s"(so));
+	}
 }
 // wavefront votes on a bool (the header's __ballot / __any take an int: a select and a compare more per call)
 __device__ __forceinline__ uint64_t tp_ballot(bool p) { return __builtin_amdgcn_ballot_w64(p); }
@@ -286,28 +297,33 @@ __device__ __forceinline__ float bkg_frame_clip(const BkgArgs& a, float (&v)[256
 	// --- stage the sorted frame (only the ranks that can hold a pixel; ranks >= n are +inf sentinels nobody reads)
 #pragma unroll
 	for (int j = 0; j < R; j += 4)
-		if (g * R + j < a.n_pix) *reinterpret_cast<float4*>(fr + rank_idx(g * R + j)) = make_float4(v[j], v[j + 1], v[j + 2], v[j + 3]);
+		if (g * R + j < a.n_pix) *reinterpret_cast<float4*>(fr + g * R + j) = make_float4(v[j], v[j + 1], v[j + 2], v[j + 3]);
 	__builtin_amdgcn_wave_barrier();
 
 	// --- sigma clipping on the staged ranks; the lanes of a frame carry the same scalars
 	const int nmasked = a.n_pix - n;
 	const bool usable = active && (n > 0) && !((float)nmasked > a.exclude_fraction * (float)a.n_pix);
-	int lo_i = 0, hi_i = usable ? n : 1;
+	// The kept range [lo, hi) is carried as the LDS byte addresses of its two ranks (the area is 16-byte aligned): the lowest kept
+	// rank is read at lo_a as it stands, the walk's address goes down (up) by 4 G bytes a step, the middle ranks take a shift and
+	// two masks.  As ranks, every read paid the scaling and the area's base again.
+	int lo_a = lds_addr(fr), hi_a = lo_a + 4 * (usable ? n : 1);
+	const int g4p = 4 * g + 4;                 // the walk's first rank from the top is hi - 1 - g
 	const uint64_t um = tp_ballot(usable);
 	double med = 0.0;
 	const int bshift = lane & (64 - G);
 	constexpr unsigned BMASK = (1u << G) - 1u;
 #pragma unroll 1
 	for (int it = 0; ; ++it) {
-		const int m = hi_i - lo_i;
-		const int m1 = lo_i + (m >> 1);          // upper middle rank
-		const int m0 = (m & 1) ? m1 : (m1 - 1);  // lower middle rank
-		med = ((double)rank_read(fr, m0) + (double)rank_read(fr, m1)) * 0.5;
+		const int m = (hi_a - lo_a) >> 2;
+		// t = base + 2 (lo + hi): cleared of its two low bits the address of the upper middle rank lo + m / 2; bit 1 is the parity
+		// of m, so t - 2 gives the same rank for an odd count and the rank below for an even one -- the lower middle rank
+		const int t = (lo_a + hi_a) >> 1;
+		med = ((double)lds_read((t - 2) & ~3) + (double)lds_read(t & ~3)) * 0.5;
 		if (it == 5) break;                        // maxiters = 5 clipping passes, then the final statistics
 		const double mm = (double)m;
 		double q9 = 9.0 * (mm * s2 - s1 * s1);    // 9 m^2 var
 		if (!(q9 > 0.0)) q9 = 0.0;
-		int top = 0, bot = 0;
+		int top4 = 0, bot4 = 0;                    // clipped at the two ends, in bytes of ranks
 		double r1 = 0.0, r2 = 0.0;
 		// The lanes' conditions are kept as wavefront masks in scalar registers (a comparison writes one directly; `and` between them is
 		// scalar work): as per-lane bools every vote cost a select and a compare to turn the bool back into a mask.
@@ -317,51 +333,54 @@ __device__ __forceinline__ float bkg_frame_clip(const BkgArgs& a, float (&v)[256
 		// almost never the case (stars clip at the top), and the walk then runs for the upper end alone -- about half the
 		// instructions of a step.  Same sums, same order.
 		{
-			const double db0 = ((double)rank_read(fr, lo_i) - med) * mm;
+			const double db0 = ((double)lds_read(lo_a) - med) * mm;
 			general = (um & tp_ballot(db0 < 0.0) & tp_ballot(db0 * db0 > q9)) != 0ull;
 			if (!general) {
+				int rt_a = hi_a - g4p;                // this lane's rank of the step, then G further down every step
 #pragma unroll 1
-				for (int base = 0; ; base += G) {
-					const int rt = hi_i - 1 - g - base;
-					const uint64_t vt = mt & tp_ballot(rt >= lo_i);
-					const float xt = rank_read(fr, tp_sel(vt, rt, lo_i));
+				for (;;) {
+					const uint64_t vt = mt & tp_ballot(rt_a >= lo_a);
+					const float xt = lds_read(tp_sel(vt, rt_a, lo_a));
 					const double dt = ((double)xt - med) * mm;
 					const uint64_t ot = vt & tp_ballot(dt > 0.0) & tp_ballot(dt * dt > q9);
 					const unsigned bt = (unsigned)(ot >> bshift) & BMASK;
 					const int ct = __builtin_ctz(~bt);
 					{ const double x = (double)((g < ct) ? xt : 0.f); r1 += x; r2 = __builtin_fma(x, x, r2); }   // + 0.0 changes nothing
-					top += ct;
+					top4 += 4 * ct;
 					mt = tp_ballot(ct == G);
 					if (mt == 0ull) break;
+					rt_a -= 4 * G;
 				}
 			}
 		}
-		if (general)
+		if (general) {
+			int rt_a = hi_a - g4p, rb_a = lo_a + g4p - 4;
 #pragma unroll 1
-		for (int base = 0; ; base += G) {
-			const int rt = hi_i - 1 - g - base, rb = lo_i + g + base;
-			const uint64_t vt = mt & tp_ballot(rt >= lo_i), vb = mb & tp_ballot(rb < hi_i);
-			const float xt = rank_read(fr, tp_sel(vt, rt, lo_i)), xb = rank_read(fr, tp_sel(vb, rb, lo_i));
-			const double dt = ((double)xt - med) * mm, db = ((double)xb - med) * mm;
-			const uint64_t ot = vt & tp_ballot(dt > 0.0) & tp_ballot(dt * dt > q9), ob = vb & tp_ballot(db < 0.0) & tp_ballot(db * db > q9);
-			// number of consecutive clipped ranks from the end of the range, among this step's G
-			const unsigned bt = (unsigned)(ot >> bshift) & BMASK, bb = (unsigned)(ob >> bshift) & BMASK;
-			const int ct = __builtin_ctz(~bt), cb = __builtin_ctz(~bb);
-			{ const double x = (double)((g < ct) ? xt : 0.f); r1 += x; r2 = __builtin_fma(x, x, r2); }
-			{ const double x = (double)((g < cb) ? xb : 0.f); r1 += x; r2 = __builtin_fma(x, x, r2); }
-			top += ct; bot += cb;
-			mt = tp_ballot(ct == G); mb = tp_ballot(cb == G);
-			if ((mt | mb) == 0ull) break;
+			for (;;) {
+				const uint64_t vt = mt & tp_ballot(rt_a >= lo_a), vb = mb & tp_ballot(rb_a < hi_a);
+				const float xt = lds_read(tp_sel(vt, rt_a, lo_a)), xb = lds_read(tp_sel(vb, rb_a, lo_a));
+				const double dt = ((double)xt - med) * mm, db = ((double)xb - med) * mm;
+				const uint64_t ot = vt & tp_ballot(dt > 0.0) & tp_ballot(dt * dt > q9), ob = vb & tp_ballot(db < 0.0) & tp_ballot(db * db > q9);
+				// number of consecutive clipped ranks from the end of the range, among this step's G
+				const unsigned bt = (unsigned)(ot >> bshift) & BMASK, bb = (unsigned)(ob >> bshift) & BMASK;
+				const int ct = __builtin_ctz(~bt), cb = __builtin_ctz(~bb);
+				{ const double x = (double)((g < ct) ? xt : 0.f); r1 += x; r2 = __builtin_fma(x, x, r2); }
+				{ const double x = (double)((g < cb) ? xb : 0.f); r1 += x; r2 = __builtin_fma(x, x, r2); }
+				top4 += 4 * ct; bot4 += 4 * cb;
+				mt = tp_ballot(ct == G); mb = tp_ballot(cb == G);
+				if ((mt | mb) == 0ull) break;
+				rt_a -= 4 * G; rb_a += 4 * G;
+			}
 		}
-		if (tp_ballot((top | bot) != 0) == 0ull) break;       // nchanged == 0 in every frame of the wavefront: the statistics are final
+		if (tp_ballot((top4 | bot4) != 0) == 0ull) break;     // nchanged == 0 in every frame of the wavefront: the statistics are final
 		s1 -= frame_sum<G>(r1);
 		s2 -= frame_sum<G>(r2);
-		lo_i += bot;
-		hi_i -= top;
+		lo_a += bot4;
+		hi_a -= top4;
 	}
 	float result = __builtin_nanf("");
 	{
-		const double mm = usable ? (double)(hi_i - lo_i) : 1.0;
+		const double mm = usable ? (double)((hi_a - lo_a) >> 2) : 1.0;
 		result = usable ? sextractor_mode_sums(med, mm, s1, s2) : result;
 	}
 	return result;
@@ -475,8 +494,7 @@ __global__ __launch_bounds__(256, 4) void tp_bkg_stamp_sum_kernel(BkgSumArgs s, 
 	{
 		const int k0 = wave * FPW + f;
 		const int voff = g * pitch_b + ((k0 < n_cad) ? k0 : (n_cad - 1)) * 4;
-#pragma unroll
-		for (int j = 0; j < NREAL; ++j) u[j] = __int_as_float(__builtin_amdgcn_raw_buffer_load_b32(rsrc, voff, j * G * pitch_b, 0));
+		load_rows<NREAL>(u, rsrc, voff, G * pitch_b);
 	}
 	// a lane's pixels in the summing phase: 4 lane .. 4 lane + 3
 	double acc[4] = {0.0, 0.0, 0.0, 0.0};
@@ -570,19 +588,30 @@ __global__ __launch_bounds__(256, 4) void tp_bkg_stamp_sum_kernel(BkgSumArgs s, 
 				if ((valid_mask >> L) & 1ull)
 					add4(*reinterpret_cast<const float4*>(s_pend + sl * n_pix4 + p0), __int_as_float(__builtin_amdgcn_readlane(__float_as_int(eff), L)), ((held_clean >> sl) & 1u) != 0u);
 			}
-			// four cadences' pixels are read at a time (the sorted values of the next block and its raw values are live in registers here)
+			// four cadences' pixels are read at a time (the sorted values of the next block and its raw values are live in registers here).
+			// The wavefront's eight cadences sit in lanes 32 + 8 wave ..: their bits of the vote are shifted down once, so that a
+			// cadence is a literal bit test, and the lane to read and the frame's place in the staging area are running values (the
+			// eight masks 1 << L, lane numbers and frame offsets of the unrolled loop are invariant in the block loop: hoisted, they
+			// were reloaded from spill registers in every block; the empty statements keep the additions where they are).
+			const unsigned own_valid = (unsigned)(valid_mask >> (32 + wave * FPW));
+			int L = 32 + wave * FPW, xo = p0;
 #pragma unroll
 			for (int h4 = 0; h4 < FPW; h4 += 4) {
 				float4 x[4];
 #pragma unroll
-				for (int ff = 0; ff < 4; ++ff) x[ff] = *reinterpret_cast<const float4*>(my_frames + (size_t)(h4 + ff) * frame_stride + p0);
+				for (int ff = 0; ff < 4; ++ff) {
+					x[ff] = *reinterpret_cast<const float4*>(my_frames + xo);
+					xo += frame_stride;
+					asm volatile("" : "+v"(xo));
+				}
 #pragma unroll
 				for (int ff = 0; ff < 4; ++ff) asm volatile("" : "+v"(x[ff].x), "+v"(x[ff].y), "+v"(x[ff].z), "+v"(x[ff].w));
 #pragma unroll
 				for (int ff = 0; ff < 4; ++ff) {
-					const int L = 32 + wave * FPW + h4 + ff;
-					if ((valid_mask >> L) & 1ull)
+					if ((own_valid >> (h4 + ff)) & 1u)
 						add4(x[ff], __int_as_float(__builtin_amdgcn_readlane(__float_as_int(eff), L)), ((clean_mask >> (8 * (h4 + ff))) & 1ull) != 0ull);
+					L += 1;
+					asm volatile("" : "+s"(L));
 				}
 			}
 		}
@@ -620,8 +649,7 @@ __global__ __launch_bounds__(256, 4) void tp_bkg_stamp_sum_kernel(BkgSumArgs s, 
 		if (b + 1 < nblocks) {
 			const int kn = k + kFramesPerBlock;
 			const int voff = g * pitch_b + ((kn < n_cad) ? kn : (n_cad - 1)) * 4;
-#pragma unroll
-			for (int j = 0; j < NREAL; ++j) u[j] = __int_as_float(__builtin_amdgcn_raw_buffer_load_b32(rsrc, voff, j * G * pitch_b, 0));
+			load_rows<NREAL>(u, rsrc, voff, G * pitch_b);
 		}
 	}
 	post_phase(nblocks - 1, clean_prev);
@@ -652,6 +680,11 @@ struct MedianArgs {
 	const float* frames; const double* reference; float* out;
 	int n_rows, n_cols; int64_t row_pitch, frame_stride; int size;
 };
+
+// Word of rank r in a sorted window of s_win: every run of 32 ranks is followed by 4 pad words (the 16-byte stores of a window's
+// lanes fall into different banks).  The filter's own layout: one rank is read per window, the address arithmetic is nothing here,
+// and the stamp kernels' linear staging was not timed for it.
+__device__ __forceinline__ int win_rank_idx(int r) { return r + ((r >> 5) << 2); }
 
 __device__ __forceinline__ int reflect_index(int i, int n) { // (d c b a | a b c d | d c b a)
 	if (n == 1) return 0;
@@ -717,9 +750,9 @@ __global__ __launch_bounds__(256) void tp_median_filter_kernel(MedianArgs a)
 	local_merge<R>(v);
 	float* fr = s_win + (wave * 8 + f) * 288;
 #pragma unroll
-	for (int j = 0; j < R; j += 4) *reinterpret_cast<float4*>(fr + rank_idx(g * R + j)) = make_float4(v[j], v[j + 1], v[j + 2], v[j + 3]);
+	for (int j = 0; j < R; j += 4) *reinterpret_cast<float4*>(fr + win_rank_idx(g * R + j)) = make_float4(v[j], v[j + 1], v[j + 2], v[j + 3]);
 	__builtin_amdgcn_wave_barrier();
-	const float med = fr[rank_idx((npix - 1) >> 1)];
+	const float med = fr[win_rank_idx((npix - 1) >> 1)];
 	if (g == 0 && active)
 		a.out[(int64_t)frame * a.frame_stride + (int64_t)row * a.row_pitch + col] = (med <= 3.402823466e+38f) ? med : __builtin_nanf("");
 }
@@ -1071,9 +1104,8 @@ extern "C" int tp_background_stamp(tp_ctx* ctx, const tp_cube_desc* desc, const 
 	a.t_pitch = desc->t_pitch; a.out_pitch = bkg_pitch;
 	a.flux_cutoff = (float)flux_cutoff; a.exclude_fraction = (float)(exclude_percentile / 100.0);
 	if (a.n_pix <= 256) {
-		// staged frame: rank_idx of the last 16-byte store + 1
-		const int last = (a.n_pix - 1) | 3;
-		const int frame_stride = ((last + ((last >> 5) << 2) + 1) + 3) & ~3;
+		// staged frame: rank r at word r, up to the end of the last 16-byte store
+		const int frame_stride = ((a.n_pix - 1) | 3) + 1;
 		const size_t shmem = (size_t)kFramesPerBlock * frame_stride * sizeof(float);
 		TP_REQUIRE(ctx, (int64_t)a.n_pix * a.t_pitch * 4 < 2147483647ll, "tp_background_stamp: stamp cube too large");
 		dim3 grid((unsigned)desc->n_targets, (unsigned)((desc->n_cad + kFramesPerBlock - 1) / kFramesPerBlock));
@@ -1115,10 +1147,10 @@ extern "C" int tp_background_sumimage(tp_ctx* ctx, const tp_cube_desc* desc, con
 	if (desc->n_targets == 0) return TP_OK;
 	const int n_pix = desc->height * desc->width;
 	const int w = time_smooth / 2;
-	// a frame's area holds its sorted ranks (rank_idx of the last 16-byte store + 1), then its raw pixels; an area stride that is
-	// a multiple of 32 words would put the eight frames of a wavefront on the same banks when the raw values are written
-	const int last = (n_pix - 1) | 3;
-	int frame_stride = ((last + ((last >> 5) << 2) + 1) + 3) & ~3;
+	// a frame's area holds its sorted ranks (rank r at word r, up to the end of the last 16-byte store: at least n_pix words), then
+	// its raw pixels; an area stride that is a multiple of 32 words would put the eight frames of a wavefront on the same banks
+	// when the raw values are written
+	int frame_stride = ((n_pix - 1) | 3) + 1;
 	if (frame_stride % 32 == 0) frame_stride += 8;
 	const int n_pix4 = (n_pix + 3) & ~3;
 	const size_t shmem = ((size_t)kFramesPerBlock * frame_stride + kRing + (size_t)(w <= 8 ? w : 0) * n_pix4) * sizeof(float) + (((size_t)desc->n_cad + 15) & ~(size_t)15) + 16;
