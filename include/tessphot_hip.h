@@ -1030,6 +1030,37 @@ uint64_t tp_deflate_work_bytes(const uint64_t* h_stream_offsets, int64_t n_strea
 uint64_t tp_deflate_chunk_bytes(void);
 uint32_t tp_crc32_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b);
 
+/* ---- batched INFLATE (csrc/inflate.hip; the rules in csrc/inflate_rules.h) -----------------------------------------------------------
+ * RFC 1951 decoded on the device, for gzip files read as they lie on disk.  The n_streams streams of a call are raw deflate streams
+ * (the gzip framing is host work): stream s is d_in[in[s], in[s + 1]) with in = h_in_offsets, and may write its slot
+ * d_out[o[s], o[s + 1]) with o = h_out_offsets (both HOST, n_streams + 1 values that do not fall).  One wavefront decodes a stream.
+ * tp_inflate: per stream s, d_status[s] is one of TP_INFLATE_*, d_out_bytes[s] the bytes produced (they lie at the front of the slot),
+ *   d_in_bytes[s] the bytes consumed up to the last bit of the block with BFINAL -- what lies behind it in the stream is not read --
+ *   and d_crc[s] the CRC-32 (gzip polynomial) of the bytes produced, formed on the device.  Acceptance is zlib's: the status is
+ *   TP_INFLATE_OK exactly where zlib's inflate reaches the end of the stream, and then bytes, consumed count and CRC are zlib's.  A
+ *   stream whose status is not TP_INFLATE_OK never makes the call fail: it has its status, the bytes it produced before the rule broke
+ *   (counted and summed; d_in_bytes[s] is then the stream's length), and has written nothing outside its slot.  Bytes of a slot behind
+ *   the bytes produced are never written.  The results are a function of the input bytes and the slot sizes alone.
+ *   Alignments: d_in and d_out none, d_status 4, d_out_bytes 8, d_in_bytes 8, d_crc 4.
+ *   TP_ERR_INVALID, checked on the host before anything is queued, nothing written: a null result or offset pointer, d_in null with
+ *   input bytes or d_out null with slot bytes, offsets that fall, n_streams < 1, 2^34 bytes or more of input or of slots, a
+ *   misaligned result pointer.
+ *   Asynchronous on the context's stream; one launch per call.                                                                    */
+enum tp_inflate_status {
+	TP_INFLATE_OK = 0,
+	TP_INFLATE_INPUT_ENDS = 1,        /* a bit behind the stream's last byte was needed */
+	TP_INFLATE_BAD_BLOCK_TYPE = 2,    /* BTYPE 3 */
+	TP_INFLATE_STORED_LENGTH = 3,     /* LEN != ~NLEN */
+	TP_INFLATE_TOO_MANY_SYMBOLS = 4,  /* HLIT > 286 or HDIST > 30 */
+	TP_INFLATE_BAD_CODE_LENGTHS = 5,  /* over-subscribed or incomplete code, symbol 16 first, a repeat past HLIT + HDIST */
+	TP_INFLATE_NO_END_OF_BLOCK = 6,   /* len[256] == 0 */
+	TP_INFLATE_BAD_SYMBOL = 7,        /* bits that are no code, length symbol 286 / 287, distance symbol 30 / 31 */
+	TP_INFLATE_DISTANCE_TOO_FAR = 8,  /* a distance beyond the bytes produced */
+	TP_INFLATE_OUTPUT_FULL = 9        /* the slot is smaller than the content */
+};
+int tp_inflate(tp_ctx* ctx, const void* d_in, const uint64_t* h_in_offsets, int64_t n_streams, void* d_out, const uint64_t* h_out_offsets,
+	int32_t* d_status, uint64_t* d_out_bytes, uint64_t* d_in_bytes, uint32_t* d_crc);
+
 /* ---- synthetic data (bench / test utility, not part of the reference path) -----------------
  * Fill images / images_err / backgrounds cubes on the device from scene parameters, following
  * the data model of simulation/simulateFITS.py:338-405 (see photometry_amd/simulate.py).

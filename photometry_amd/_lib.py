@@ -212,6 +212,7 @@ SIGNATURES = {
 	'tp_deflate_work_bytes': (c_uint64, [_p, c_int64]),
 	'tp_deflate_chunk_bytes': (c_uint64, []),
 	'tp_crc32_combine': (c_uint32, [c_uint32, c_uint32, c_uint64]),
+	'tp_inflate': (c_int, [c_void_p, _p, _p, c_int64, _p, _p, _p, _p, _p, _p]),
 	'tp_synth_fill': (c_int, [c_void_p, _desc_p, c_int32, _p, _p, _p, _p, _p, c_double, c_double, c_uint64, _p, _p, _p, _p]),
 }
 

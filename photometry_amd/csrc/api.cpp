@@ -79,6 +79,7 @@ static const char* const kKernelNames[TPK_COUNT] = {
 	"tp_deflate_kernel",
 	"tp_deflate_scan_kernel",
 	"tp_deflate_pack_kernel",
+	"tp_inflate_kernel",
 };
 
 extern "C" {

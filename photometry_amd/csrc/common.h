@@ -77,6 +77,7 @@ enum tp_kernel_id {
 	TPK_DEFLATE,
 	TPK_DEFLATE_SCAN,
 	TPK_DEFLATE_PACK,
+	TPK_INFLATE,
 	TPK_COUNT
 };
 

@@ -282,6 +282,33 @@ def scan_hdus(path, most):
 	return hdus
 
 
+def scan_hdus_from(read, most, behind_data=True):
+	"""
+	:func:`scan_hdus` over a source ``read(offset, n)`` that returns the ``n`` bytes at ``offset`` of the (inflated) file, fewer or none
+	where it holds no more: the same :class:`HDU` s, and the list ends quietly where the source does.  ``behind_data=False``: the list
+	ends with the first HDU that has a data unit -- the headers a source holds that knows the front of a file only.
+	"""
+	hdus, pos = [], 0
+	while len(hdus) < most:
+		at = [pos]
+
+		def next_block():
+			at[0] += BLOCK
+			return read(at[0] - BLOCK, BLOCK)
+		try:
+			header, cards = read_header_blocks(next_block)
+		except EOFError:
+			break
+		pos += _padded(len(cards) * 80)
+		shape, nbytes = data_unit_bytes(header)
+		nbytes = _padded(nbytes + int(header.get('PCOUNT', 0) or 0))
+		hdus.append(HDU(header, cards, pos, nbytes, tuple(int(n) for n in shape)))
+		pos += nbytes
+		if nbytes and not behind_data:
+			break
+	return hdus
+
+
 def read(path):
 	"""Returns a list of ``(header dict, data)``; data is None, an ndarray (image) or a dict of column arrays (table)."""
 	with opener(path)(path, 'rb') as fh:

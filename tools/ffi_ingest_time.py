@@ -14,6 +14,14 @@ Steps, all in one process, each timed with a host clock around work that ends in
               and the bytes they move over them;
 ``numpy``     today's converter restated: ``'>f4'`` view of the file -> crop -> ``astype('float32')`` into a ``(T, R, C)`` array on one
               host core, then ``frameio.upload_group``; per frame and per core.
+
+``--gz LEVEL`` writes the files as ``.fits.gz`` instead (``--distinct`` of them compressed, the rest copies; the compression ratio of
+what was written is printed) and times these steps only, ``--inflate host device`` choosing the paths:
+``load_gz``   ``load_ffis`` on the ``.gz`` files: ``inflate='host'`` (the reader thread's ``gzip``: today's path, on the first
+              ``--host-files`` files) and ``inflate='device'`` at every ``--batch-files`` (0: the loader's default), frames/s;
+``decoder``   ``tp_inflate`` alone on ``--decoder-files`` members already in device memory: MB/s of output in aggregate and per
+              wavefront, from the kernel's time in ``tp_profile_get``.
+Synthetic noise pixels compress less than real FFIs do.
 """
 import argparse
 import json
@@ -48,12 +56,76 @@ def make_files(root, n):
 	return files
 
 
+def compress_files(root, plain, n, level):
+	"""``n`` ``.fits.gz`` files from the plain ones at zlib level ``level``: each plain file compressed once, then copied in rotation
+	(the loader's work per file does not depend on the other files).  Returns the files and compressed / plain bytes."""
+	import gzip
+	import shutil
+	made, files = [], []
+	for k in range(n):
+		path = os.path.join(root, 'tess2018206%06d-s0001-1-1-0120-s_ffic.fits.gz' % (45240 + k))
+		if k < len(plain):
+			with open(plain[k], 'rb') as src, gzip.open(path, 'wb', compresslevel=level) as dst:
+				shutil.copyfileobj(src, dst, 1 << 24)
+			made.append(path)
+		else:
+			shutil.copyfile(made[k % len(made)], path)
+		files.append(path)
+	return files, sum(os.path.getsize(f) for f in made) / sum(os.path.getsize(f) for f in plain)
+
+
+def gz_steps(a, ctx, root, emit):
+	"""``--gz``: the same loader on ``.fits.gz`` files, the host's inflate (today's path) beside the device's, and the decoder alone."""
+	from photometry_amd import ffi, inflate
+	plain = make_files(root, min(a.files, a.distinct))
+	files, ratio = compress_files(root, plain, a.files, a.gz)
+	T = len(files)
+	emit({'step': 'gz_files', 'files': T, 'distinct': len(plain), 'level': a.gz, 'compression_ratio': ratio, 'gz_bytes_per_file': os.path.getsize(files[0]),
+		'note': 'synthetic noise pixels: real FFIs compress further'})
+	for mode in a.inflate:
+		subset = files[:a.host_files] if mode == 'host' else files
+		for batch in ([None] if mode == 'host' else a.batch_files):
+			how = {} if mode == 'host' else {'inflate': 'device', 'batch_files': batch or None}
+			ffi.load_ffis(ctx, subset[:max(2, len(subset) // 8)], **how).free()                # warm-up: page cache, code objects, the allocation cache
+			runs = []
+			for _ in range(a.repeats):
+				t0 = time.perf_counter()
+				loaded = ffi.load_ffis(ctx, subset, **how)
+				ctx.sync()
+				wall = time.perf_counter() - t0
+				runs.append({'wall_s': wall, 'read_s': loaded.stats['read_s'], 'wait_s': loaded.stats['wait_s'], 'inflate_wait_s': loaded.stats['inflate_wait_s']})
+				loaded.free()
+			best = min(runs, key=lambda r: r['wall_s'])
+			emit({'step': 'load_gz', 'inflate': mode, 'batch_files': batch or ('default' if mode == 'device' else None), 'files': len(subset), 'runs': runs,
+				'frames_per_s': len(subset) / best['wall_s'], 'ms_per_frame': best['wall_s'] / len(subset) * 1e3})
+	if 'device' in a.inflate:
+		# the decoder alone: the members in device memory, one tp_inflate, kernel time from the profile
+		members = [open(f, 'rb').read() for f in files[:a.decoder_files]]
+		frames = [inflate.parse_member(m) for m in members]
+		ctx.profile(True)
+		ctx.profile_reset()
+		call = inflate._Call(ctx, [memoryview(m)[b:e] for m, (b, e, _c, _i) in zip(members, frames)], [i for _b, _e, _c, i in frames])
+		ctx.profile(False)
+		ok = bool((call.statuses == 0).all() and all(int(c) == f[2] for c, f in zip(call.crcs, frames)))
+		call.free()
+		launches, ms = ctx.profile_report()['tp_inflate_kernel']
+		out_bytes = sum(f[3] for f in frames)
+		emit({'step': 'decoder', 'streams': len(members), 'all_ok_and_crc': ok, 'kernel_ms': ms, 'out_MB_per_s_aggregate': out_bytes / ms / 1e3,
+			'out_MB_per_s_per_wavefront': max(f[3] for f in frames) / ms / 1e3, 'in_MB_per_s_aggregate': sum(len(m) for m in members) / ms / 1e3})
+
+
 def main():
 	ap = argparse.ArgumentParser()
 	ap.add_argument('--files', type=int, default=24, help='synthetic FFIs (35.5 MB each)')
 	ap.add_argument('--repeats', type=int, default=3)
 	ap.add_argument('--dir', default=None, help='where the files go (default: a temporary directory, removed afterwards)')
 	ap.add_argument('--out', default=None)
+	ap.add_argument('--gz', type=int, default=None, metavar='LEVEL', help='write the files as .fits.gz at this zlib level and time the loader on them (the steps below only)')
+	ap.add_argument('--inflate', nargs='+', default=['host'], choices=['host', 'device'], help='with --gz: which inflate paths of load_ffis to time')
+	ap.add_argument('--batch-files', type=int, nargs='+', default=[64, 256, 0], help="with --gz: batch_files of the device path (0: the loader's default)")
+	ap.add_argument('--distinct', type=int, default=4, help='with --gz: files that are compressed; the others are copies of them')
+	ap.add_argument('--host-files', type=int, default=16, help="with --gz: the first so many files go through the host's inflate (it takes a second per file)")
+	ap.add_argument('--decoder-files', type=int, default=256, help='with --gz: streams of the decoder-alone launch')
 	a = ap.parse_args()
 	import numpy as np
 	from photometry_amd import ffi, frameio, staging
@@ -65,6 +137,10 @@ def main():
 			with open(a.out, 'a') as fh:
 				fh.write(json.dumps(res) + '\n')
 
+	if a.gz is not None:
+		with tempfile.TemporaryDirectory(dir=a.dir) as root, Context(0) as ctx:
+			gz_steps(a, ctx, root, emit)
+		return 0
 	with tempfile.TemporaryDirectory(dir=a.dir) as root, Context(0) as ctx:
 		files = make_files(root, a.files)
 		T = len(files)
