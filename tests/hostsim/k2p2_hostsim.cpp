@@ -10,6 +10,17 @@
 // bytes of work arrays per target: what decides between the LDS-resident kernel (up to 160 KiB) and the one on HBM scratch
 extern "C" long long hostsim_k2p2_shared_bytes(int n_pixels) { return (long long)k2p2::shared_bytes(n_pixels); }
 
+// byte offset of k.lab from the base of the work arrays, as shared_carve sets it for an H x W stamp: the fused per-target kernel
+// keeps its mask pixel list there during the extraction, and the floats between the end of its pixel table and the list are the
+// room that decides whether a target's series are staged in LDS or re-read from HBM (tests/extract_variants_common.py)
+extern "C" long long hostsim_k2p2_lab_offset(int H, int W) {
+	k2p2::Shared k;
+	std::vector<unsigned char> shm(k2p2::shared_bytes(H * W) + 16);
+	unsigned char* base = (unsigned char*)(((uintptr_t)shm.data() + 15) & ~(uintptr_t)15);
+	k2p2::shared_carve(k, base, H, W, 0, nullptr);   // (pointers are only formed, nothing is read or written)
+	return (long long)((const unsigned char*)k.lab - base);
+}
+
 extern "C" int hostsim_k2p2(int n_targets, int H, int W, const double* sumimage,
 	const int64_t* cat_offsets, const float* cat_column_stamp, const float* cat_row_stamp, const float* cat_tmag,
 	const float* cat_column, const float* cat_row, const int64_t* cat_starid,
