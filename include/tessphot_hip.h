@@ -1061,6 +1061,48 @@ enum tp_inflate_status {
 int tp_inflate(tp_ctx* ctx, const void* d_in, const uint64_t* h_in_offsets, int64_t n_streams, void* d_out, const uint64_t* h_out_offsets,
 	int32_t* d_status, uint64_t* d_out_bytes, uint64_t* d_in_bytes, uint32_t* d_crc);
 
+/* ---- light-curve table out (csrc/lctable.hip; the rules in csrc/lctable_rules.h) ---------------------------------------------------
+ * What fitsio.bintable_hdu does on the host for the LIGHTCURVE table of a light-curve file (FILEVER 1.5; BasePhotometry.py:1507-1600) --
+ * the recarray fill, `tobytes`, the pad and the DATASUM -- from the planes a run holds in device memory.  A row is 96 bytes, big-endian,
+ * 14 columns `D E J D D D D D J J D D D D`: TIME, TIMECORR, CADENCENO, FLUX_RAW, FLUX_RAW_ERR, FLUX_BKG, FLUX_CORR, FLUX_CORR_ERR,
+ * QUALITY, PIXEL_QUALITY, MOM_CENTR1, MOM_CENTR2, POS_CORR1, POS_CORR2.
+ * tp_lc_table_src: the source of a call.  Every pointer is a device pointer; every stride is in elements; a per-target stride of 0 is
+ *   one vector shared by all targets.  time, timecorr (float64), cadenceno, pixel_quality (int32): value of target i at cadence t at
+ *   [i * stride + t].  lc: the five float64 planes flux, flux_err, flux_background, centroid column, centroid row, value at
+ *   [p * lc_plane_stride + i * lc_target_stride + t] (the (5, m, T) block of the frames entry: m * T and T).  quality: int32
+ *   [i * stride + t], NULL: zeros.  pos_corr: float64 [i * stride + 2 * t + {0, 1}], NULL: zeros.
+ * tp_lc_table_pack: for target i in [0, n_targets) the n_rows rows of the cadences d_rows[0 .. n_rows) (device int32, rising, each in
+ *   [0, T); NULL: 0 .. n_rows - 1) at d_out + h_out_offsets[i] (HOST array), then zeros up to the next multiple of 2880 bytes; no
+ *   other byte of d_out is written.  The float64 columns move as 64-bit integers and are byte-swapped only: a NaN keeps payload and
+ *   sign, -0.0 stays -0.0, a signalling NaN stays signalling.  TIMECORR is the float32 nearest to the value, ties to even (numpy's
+ *   assignment into an '>f4' field).  FLUX_CORR and FLUX_CORR_ERR are the bits of np.nan, 0x7FF8000000000000.  An entry of d_rows
+ *   outside [0, T) reads nothing: its row is written from zeros.  d_datasum[i] (uint64, 8-byte aligned): the DATASUM of target i's data
+ *   unit in the form tp_fits_datasum returns, from the native values on the way (no written byte is read back; integer atomics only:
+ *   exact and the same in every run).  n_rows == 0 writes no byte of d_out and sets the sums to 0.
+ *   TP_ERR_INVALID, checked on the host before anything is queued, nothing written: a null pointer other than d_rows, quality and
+ *   pos_corr, n_targets outside [1, 2^20], T outside [1, 2^31), n_rows outside [0, T] or above 178 956 970 (kMaxRows of the rules: beyond
+ *   it the 64-bit word sum could wrap), a negative stride, d_out not 16-byte aligned, an offset that is no multiple of 16, a target's
+ *   range that leaves out_capacity, two ranges that overlap, d_datasum not 8-byte or d_rows not 4-byte aligned.
+ *   Asynchronous on the context's stream; two launches per call (pack, fold).
+ * tp_lc_place: n_segments byte ranges in one launch: h_lengths[k] bytes from d_src + h_src_offsets[k] to d_dst + h_dst_offsets[k] (HOST
+ *   arrays; all three multiples of 16 -- every FITS piece is a multiple of 2880), for the host-built pieces of a window of files after
+ *   one compact upload.  TP_ERR_INVALID, nothing written: a null pointer, n_segments outside [1, 2^20], a value or a buffer that is not
+ *   16-byte aligned, a range that leaves src_capacity or dst_capacity, destination ranges that overlap, 2^34 bytes or more in all.
+ *   Asynchronous on the context's stream; one launch per call (none without a byte to move).                                       */
+typedef struct tp_lc_table_src {
+	const double* time; int64_t time_stride;
+	const double* timecorr; int64_t timecorr_stride;
+	const int32_t* cadenceno; int64_t cadenceno_stride;
+	const int32_t* pixel_quality; int64_t pixel_quality_stride;
+	const double* lc; int64_t lc_plane_stride; int64_t lc_target_stride;
+	const int32_t* quality; int64_t quality_stride;
+	const double* pos_corr; int64_t pos_corr_stride;
+} tp_lc_table_src;
+int tp_lc_table_pack(tp_ctx* ctx, const tp_lc_table_src* h_src, const int32_t* d_rows, int64_t n_rows, int64_t T, int32_t n_targets, void* d_out,
+	const uint64_t* h_out_offsets, uint64_t out_capacity, uint64_t* d_datasum);
+int tp_lc_place(tp_ctx* ctx, const void* d_src, uint64_t src_capacity, const uint64_t* h_src_offsets, const uint64_t* h_dst_offsets, const uint64_t* h_lengths,
+	int64_t n_segments, void* d_dst, uint64_t dst_capacity);
+
 /* ---- synthetic data (bench / test utility, not part of the reference path) -----------------
  * Fill images / images_err / backgrounds cubes on the device from scene parameters, following
  * the data model of simulation/simulateFITS.py:338-405 (see photometry_amd/simulate.py).

@@ -52,6 +52,13 @@ class tp_k2p2_params(Structure):
 		('extend_overflow', c_int32), ('reserved', c_int32), ('ws_thres', c_double), ('saturation_limit', c_double)]
 
 
+class tp_lc_table_src(Structure):
+	_fields_ = [('time', c_void_p), ('time_stride', c_int64), ('timecorr', c_void_p), ('timecorr_stride', c_int64),
+		('cadenceno', c_void_p), ('cadenceno_stride', c_int64), ('pixel_quality', c_void_p), ('pixel_quality_stride', c_int64),
+		('lc', c_void_p), ('lc_plane_stride', c_int64), ('lc_target_stride', c_int64), ('quality', c_void_p), ('quality_stride', c_int64),
+		('pos_corr', c_void_p), ('pos_corr_stride', c_int64)]
+
+
 _p = c_void_p # device / host data pointers are passed as integers
 _desc_p = POINTER(tp_cube_desc)
 
@@ -213,6 +220,8 @@ SIGNATURES = {
 	'tp_deflate_chunk_bytes': (c_uint64, []),
 	'tp_crc32_combine': (c_uint32, [c_uint32, c_uint32, c_uint64]),
 	'tp_inflate': (c_int, [c_void_p, _p, _p, c_int64, _p, _p, _p, _p, _p, _p]),
+	'tp_lc_table_pack': (c_int, [c_void_p, POINTER(tp_lc_table_src), _p, c_int64, c_int64, c_int32, _p, _p, c_uint64, _p]),
+	'tp_lc_place': (c_int, [c_void_p, _p, c_uint64, _p, _p, _p, c_int64, _p, c_uint64]),
 	'tp_synth_fill': (c_int, [c_void_p, _desc_p, c_int32, _p, _p, _p, _p, _p, c_double, c_double, c_uint64, _p, _p, _p, _p]),
 }
 
@@ -255,5 +264,5 @@ def exported_symbols():
 	return sorted(SIGNATURES.keys())
 
 
-__all__ = ['load', 'TessphotError', 'TessphotLibraryError', 'tp_cube_desc', 'tp_k2p2_params', 'tp_frames_stack', 'tp_zoom_image', 'tp_radial_image', 'SIGNATURES', 'LIB_PATH',
+__all__ = ['load', 'TessphotError', 'TessphotLibraryError', 'tp_cube_desc', 'tp_k2p2_params', 'tp_frames_stack', 'tp_zoom_image', 'tp_radial_image', 'tp_lc_table_src', 'SIGNATURES', 'LIB_PATH',
 	'byref', 'c_void_p', 'c_int', 'c_int32', 'c_int64', 'c_uint64', 'c_float', 'c_double', 'c_uint8']

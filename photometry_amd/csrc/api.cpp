@@ -80,6 +80,9 @@ static const char* const kKernelNames[TPK_COUNT] = {
 	"tp_deflate_scan_kernel",
 	"tp_deflate_pack_kernel",
 	"tp_inflate_kernel",
+	"tp_lc_table_pack_kernel",
+	"tp_lc_table_fold_kernel",
+	"tp_lc_place_kernel",
 };
 
 extern "C" {

@@ -78,6 +78,9 @@ enum tp_kernel_id {
 	TPK_DEFLATE_SCAN,
 	TPK_DEFLATE_PACK,
 	TPK_INFLATE,
+	TPK_LC_TABLE_PACK,
+	TPK_LC_TABLE_FOLD,
+	TPK_LC_PLACE,
 	TPK_COUNT
 };
 

@@ -5,6 +5,8 @@ csrc/deflate_rules.h and DESIGN.md section 19).
 
 * :func:`gzip_many` -- a list of byte strings into a list of gzip members: one upload through the context's pooled page-locked
   staging, one ``tp_deflate`` per batch, one download of the chunks' end offsets and CRCs, one download of the packed bytes;
+* :func:`gzip_device` -- the same members from byte strings that already lie in a device buffer, given by offsets: no staging, no
+  upload (the light-curve files whose table the device wrote, ``lcfile`` with ``table='device'``);
 * :func:`deflate_chunks` -- the raw form of one call: the packed deflate bytes of all chunks, their end offsets and their CRCs.
 
 A member is a 10-byte gzip header without FNAME, with ``MTIME = 0`` and ``OS = 255``, the stream's chunks as the device wrote them,
@@ -30,35 +32,33 @@ def chunk_bytes(ctx):
 	return int(ctx.lib.tp_deflate_chunk_bytes())
 
 
+class _Lap(object):
+	"""Adds the seconds since the last lap to ``parts[name]`` (``parts`` may be None)."""
+
+	def __init__(self, parts):
+		self.parts, self.t0 = parts, _clock.perf_counter()
+
+	def __call__(self, name):
+		t1 = _clock.perf_counter()
+		if self.parts is not None:
+			self.parts[name] = self.parts.get(name, 0.0) + t1 - self.t0
+		self.t0 = t1
+
+
 def _call(ctx, blobs, members, parts=None):
 	"""One ``tp_deflate`` over ``blobs``.  ``members``: build the gzip members from the page-locked download (one copy per member);
 	else return ``(packed bytes, ends, crcs)``.  ``parts``: a dict that receives the seconds of the call's four parts."""
-	t0 = _clock.perf_counter()
-
-	def lap(name):
-		nonlocal t0
-		if parts is not None:
-			t1 = _clock.perf_counter()
-			parts[name] = parts.get(name, 0.0) + t1 - t0
-			t0 = t1
+	lap = _Lap(parts)
 	lib = ctx.lib
 	n = len(blobs)
-	chunk = chunk_bytes(ctx)
 	offsets = np.zeros(n + 1, dtype='uint64')
 	offsets[1:] = np.cumsum([len(b) for b in blobs], dtype='uint64')
 	total = int(offsets[-1])
-	per_stream = [-(-len(b) // chunk) for b in blobs]
-	n_chunks = sum(per_stream)
-	if n_chunks == 0:
-		ends, crcs = np.zeros(0, dtype='uint64'), np.zeros(0, dtype='uint32')
-		return [_member([], 0, 0)] * n if members else (b'', ends, crcs)
-	capacity = total + 5 * n_chunks                                    # the sum of tp_deflate_bound over the streams
-	work_bytes = int(lib.tp_deflate_work_bytes(offsets.ctypes.data, n))
+	if total == 0:
+		return _device_call(ctx, None, offsets, members, lap)
 	words = round_up(total, 4) // 4
 	up = ctx.pinned_block(4 * words)
-	meta = ctx.pinned_block(12 * n_chunks)
-	down = None
-	d_in = d_out = d_meta = d_work = None
+	d_in = None
 	try:
 		at = 0
 		for b in blobs:
@@ -66,11 +66,39 @@ def _call(ctx, blobs, members, parts=None):
 			at += len(b)
 		lap('stage')
 		d_in = ctx.empty(4 * words, 'uint8')
+		ctx._check(lib.tp_upload_cube_async(ctx.handle, d_in.ptr, words, up.ptr, words, 1, words))
+		return _device_call(ctx, d_in.ptr, offsets, members, lap, spare=up)
+	finally:
+		if d_in is not None:
+			d_in.free()
+		ctx.pinned_release(up)
+
+
+def _device_call(ctx, d_in_ptr, offsets, members, lap, spare=None):
+	"""One ``tp_deflate`` over streams that lie in device memory: stream ``s`` is ``[offsets[s], offsets[s + 1])`` behind ``d_in_ptr``
+	(whatever put them there is queued on the context's stream).  ``spare``: a page-locked block that is free once the kernels have
+	run and may take the download.  Results as :func:`_call`."""
+	lib = ctx.lib
+	offsets = np.ascontiguousarray(offsets, dtype='uint64')
+	n = len(offsets) - 1
+	chunk = chunk_bytes(ctx)
+	lens = [int(v) for v in np.diff(offsets.astype('int64'))]
+	total = int(offsets[-1]) - int(offsets[0])
+	per_stream = [-(-v // chunk) for v in lens]
+	n_chunks = sum(per_stream)
+	if n_chunks == 0:
+		ends, crcs = np.zeros(0, dtype='uint64'), np.zeros(0, dtype='uint32')
+		return [_member([], 0, 0)] * n if members else (b'', ends, crcs)
+	capacity = total + 5 * n_chunks                                    # the sum of tp_deflate_bound over the streams
+	work_bytes = int(lib.tp_deflate_work_bytes(offsets.ctypes.data, n))
+	meta = ctx.pinned_block(12 * n_chunks)
+	down = None
+	d_out = d_meta = d_work = None
+	try:
 		d_out = ctx.empty(capacity, 'uint8')
 		d_meta = ctx.empty(12 * n_chunks, 'uint8')                      # n_chunks ends (uint64), then n_chunks CRCs (uint32)
 		d_work = ctx.empty(work_bytes, 'uint8')
-		ctx._check(lib.tp_upload_cube_async(ctx.handle, d_in.ptr, words, up.ptr, words, 1, words))
-		ctx._check(lib.tp_deflate(ctx.handle, d_in.ptr, offsets.ctypes.data, n, d_out.ptr, capacity, d_meta.ptr, d_meta.ptr + 8 * n_chunks, d_work.ptr, work_bytes))
+		ctx._check(lib.tp_deflate(ctx.handle, d_in_ptr, offsets.ctypes.data, n, d_out.ptr, capacity, d_meta.ptr, d_meta.ptr + 8 * n_chunks, d_work.ptr, work_bytes))
 		ctx.download_async(meta, d_meta, nbytes=12 * n_chunks)
 		ctx.sync()
 		ends = np.array(meta.array[:8 * n_chunks].view('uint64'))
@@ -78,7 +106,7 @@ def _call(ctx, blobs, members, parts=None):
 		packed_bytes = int(ends[-1])
 		assert packed_bytes <= capacity
 		lap('upload_and_kernels')
-		down = up if up.nbytes >= packed_bytes else ctx.pinned_block(packed_bytes)   # (the upload is over: its block takes the download)
+		down = spare if spare is not None and spare.nbytes >= packed_bytes else ctx.pinned_block(packed_bytes)   # (the upload is over: its block takes the download)
 		ctx.download_async(down, d_out, nbytes=packed_bytes)
 		ctx.sync()
 		packed = memoryview(down.array)[:packed_bytes]
@@ -87,22 +115,21 @@ def _call(ctx, blobs, members, parts=None):
 			return bytes(packed), ends, crcs
 		out = []
 		c, begin = 0, 0
-		for b, k in zip(blobs, per_stream):
+		for nbytes, k in zip(lens, per_stream):
 			end = int(ends[c + k - 1]) if k else begin
 			crc = 0
 			for j in range(k):
-				crc = lib.tp_crc32_combine(crc, int(crcs[c + j]), min(chunk, len(b) - j * chunk))
-			out.append(_member([packed[begin:end]], crc, len(b)))
+				crc = lib.tp_crc32_combine(crc, int(crcs[c + j]), min(chunk, nbytes - j * chunk))
+			out.append(_member([packed[begin:end]], crc, nbytes))
 			c, begin = c + k, end
 		lap('members')
 		return out
 	finally:
-		for d in (d_in, d_out, d_meta, d_work):
+		for d in (d_out, d_meta, d_work):
 			if d is not None:
 				d.free()
 		ctx.pinned_release(meta)
-		ctx.pinned_release(up)
-		if down is not None and down is not up:
+		if down is not None and down is not spare:
 			ctx.pinned_release(down)
 
 
@@ -136,5 +163,27 @@ def gzip_many(ctx, blobs, max_batch_bytes=MAX_BATCH_BYTES, parts=None):
 			held += len(blobs[b])
 			b += 1
 		out.extend(_call(ctx, blobs[a:b], members=True, parts=parts))
+		a = b
+	return out
+
+
+def gzip_device(ctx, d_in, offsets, max_batch_bytes=MAX_BATCH_BYTES, parts=None):
+	"""
+	:func:`gzip_many` for byte strings that already lie in device memory: string ``s`` is ``[offsets[s], offsets[s + 1])`` of the
+	uint8 device array ``d_in`` (``offsets``: ``n + 1`` values that do not fall; what filled ``d_in`` is queued on the context's
+	stream).  The same members, batches and ``parts`` as :func:`gzip_many` without ``stage``: nothing is staged or uploaded.
+	"""
+	offsets = np.ascontiguousarray(offsets, dtype='uint64')
+	n = len(offsets) - 1
+	if n < 0 or (n and int(offsets[-1]) > d_in.nbytes) or np.any(np.diff(offsets.astype('int64')) < 0):
+		raise ValueError("offsets must be n + 1 values inside the device array that do not fall")
+	lap = _Lap(parts)
+	out = []
+	a = 0
+	while a < n:
+		b = a + 1
+		while b < n and int(offsets[b + 1]) - int(offsets[a]) <= max_batch_bytes:
+			b += 1
+		out.extend(_device_call(ctx, d_in.ptr, offsets[a:b + 1], True, lap))
 		a = b
 	return out

@@ -102,14 +102,19 @@ def _encode_checksum(value):
 	return s[-1] + s[:-1]
 
 
-def _hdu_bytes(cards, data):
-	"""Header + data with DATASUM / CHECKSUM filled in."""
-	datasum = _sum32(data) if data else 0
+def hdu_header(cards, datasum):
+	"""Header bytes with DATASUM / CHECKSUM filled in from the cards and the data unit's ``datasum`` (0: no data): the data is not needed."""
+	datasum = int(datasum)
 	cards = list(cards) + [card('CHECKSUM', '0' * 16, 'HDU checksum'), card('DATASUM', str(datasum), 'data unit checksum')]
 	hdr = _header_bytes(cards)
 	total = _sum32(hdr, datasum)
 	cards[-2] = card('CHECKSUM', _encode_checksum(total), 'HDU checksum')
-	return _header_bytes(cards) + data
+	return _header_bytes(cards)
+
+
+def _hdu_bytes(cards, data):
+	"""Header + data with DATASUM / CHECKSUM filled in."""
+	return hdu_header(cards, _sum32(data) if data else 0) + data
 
 
 def primary_hdu(cards):
@@ -152,14 +157,13 @@ def _parse_tdim(text):
 	return tuple(int(v) for v in text.strip().strip('()').split(','))
 
 
-def bintable_hdu(name, columns, cards=()):
-	"""``columns``: list of dicts ``name, format (D/E/J/..., or with a repeat count: 484E), array`` and optional ``unit, disp,
-	dim`` (the TDIM tuple, fastest axis first) and ``comments`` (dict of TTYPE/TFORM/TUNIT/TDISP/TDIM comments)."""
-	nrows = len(columns[0]['array'])
-	dt = np.dtype([_dtype_entry(c['name'], c['format'], c.get('dim')) for c in columns])
-	rec = np.zeros(nrows, dtype=dt)
-	for c in columns:
-		rec[c['name']] = np.asarray(c['array'])
+def _bintable_dtype(columns):
+	return np.dtype([_dtype_entry(c['name'], c['format'], c.get('dim')) for c in columns])
+
+
+def bintable_cards(name, columns, cards, nrows):
+	"""The cards of a binary table's header without CHECKSUM / DATASUM; ``columns`` need no arrays."""
+	dt = _bintable_dtype(columns)
 	base = [card('XTENSION', 'BINTABLE', 'binary table extension'), card('BITPIX', 8, 'array data type'),
 		card('NAXIS', 2, 'number of array dimensions'), card('NAXIS1', dt.itemsize, 'length of dimension 1'),
 		card('NAXIS2', nrows, 'length of dimension 2'), card('PCOUNT', 0, 'number of group parameters'),
@@ -176,7 +180,30 @@ def bintable_hdu(name, columns, cards=()):
 		if c.get('dim') is not None:
 			base.append(card(f'TDIM{i}', '(' + ','.join(str(int(v)) for v in c['dim']) + ')', cm.get('TDIM')))
 	base.append(card('EXTNAME', name, 'extension name'))
-	return _hdu_bytes(base, _pad(rec.tobytes()))
+	return base
+
+
+def bintable_header(name, columns, cards, nrows, datasum):
+	"""The header bytes of a binary table of ``nrows`` rows whose data unit (pad included) has the DATASUM ``datasum`` -- formed
+	elsewhere, on the device for instance: ``columns`` as for :func:`bintable_hdu` without ``array``.  ``bintable_header(...) + data
+	unit`` is :func:`bintable_hdu` of the same columns with their arrays."""
+	return hdu_header(bintable_cards(name, columns, cards, int(nrows)), datasum)
+
+
+def bintable_data(columns):
+	"""The data unit of :func:`bintable_hdu`: the rows, big-endian, padded with zeros to whole blocks."""
+	nrows = len(columns[0]['array'])
+	rec = np.zeros(nrows, dtype=_bintable_dtype(columns))
+	for c in columns:
+		rec[c['name']] = np.asarray(c['array'])
+	return _pad(rec.tobytes())
+
+
+def bintable_hdu(name, columns, cards=()):
+	"""``columns``: list of dicts ``name, format (D/E/J/..., or with a repeat count: 484E), array`` and optional ``unit, disp,
+	dim`` (the TDIM tuple, fastest axis first) and ``comments`` (dict of TTYPE/TFORM/TUNIT/TDISP/TDIM comments)."""
+	data = bintable_data(columns)
+	return bintable_header(name, columns, cards, len(columns[0]['array']), _sum32(data) if data else 0) + data
 
 
 def write(path, hdus, compresslevel=9):
@@ -377,6 +404,13 @@ def tdb_to_utc_isot(jd1, jd2=0.0):
 	mjd_day = int(day - 0.5 - 2400000.5 + 0.5) # = day - 2400001
 	g = np.deg2rad(357.53 + 0.98560028 * ((big - 2451545.0) + small))
 	sec = frac * 86400.0 - (0.001657 * np.sin(g) + 0.000014 * np.sin(2 * g)) - 32.184 # TAI seconds of the TDB day
+	# whole days in `frac` (a TESS time against BJDREFI brings about a thousand): the loop below would walk them off one at a time,
+	# through the states (mjd_day + j, sec - j * 86400.0), each subtraction exact.  With k = floor(frac) >= 2 the state j = k - 2 still
+	# has sec >= 2 * 86400 - 33 - 37 > 86400 + TAI-UTC and lies on that walk: start there, and the loops below finish as before.
+	if frac >= 2.0 and np.isfinite(frac):
+		skip = int(np.floor(frac)) - 2
+		mjd_day += skip
+		sec -= skip * 86400.0
 	# leap seconds: decide with the UTC day the instant falls into
 	sec_utc = sec - _tai_minus_utc(mjd_day)
 	while sec_utc < 0:

@@ -13,14 +13,21 @@ paths that produce one:
 Building the bytes is host work: a file is 96 bytes per cadence against the 40 + 16 that cross the link as light curve and
 ``QUALITY``.  Compressing them is host work too by default (``compress='zlib'``) and dominates it (DESIGN.md section 17);
 ``compress='device'`` hands the bytes of a window of files to the device's DEFLATE encoder instead (``deflate.gzip_many``, section 19).
+With ``table='device'`` besides, the ``LIGHTCURVE`` table's data unit -- what grows with the series -- is written by a kernel straight
+into the encoder's input with its DATASUM (:func:`lightcurve_pieces`, ``tp_lc_table_pack``, section 21) and the host builds headers
+and the image HDUs only.
 """
 
+import ctypes
 import datetime
 import os
+from collections import namedtuple
 from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 from . import fitsio
 from .fitsio import card
+from .device import round_up
+from ._lib import tp_lc_table_src
 from .status import STATUS
 
 #: PixelQualityFlags.BackgroundShenanigans / CorrectorQualityFlags.BackgroundShenanigans (photometry/quality.py:163, :85)
@@ -32,6 +39,11 @@ PROCVER = 'photometry_amd-0.2'
 MAX_WORKERS = 16
 #: what ``compress=`` takes: gzip on the workers (the default: the bytes ``gzip.open`` writes), or DEFLATE on the device
 COMPRESS = ('zlib', 'device')
+#: what ``table=`` takes: the ``LIGHTCURVE`` table's data unit from numpy on the workers (the default), or written on the device straight
+#: into the encoder's input with its DATASUM (``tp_lc_table_pack``, csrc/lctable.hip; needs ``compress='device'``)
+TABLE = ('host', 'device')
+#: bytes of a row of the ``LIGHTCURVE`` table (``NAXIS1``)
+ROW_BYTES = 96
 #: files whose bytes are held at a time with ``compress='device'``: built, compressed in batches, written, then the next window
 DEVICE_WINDOW = 256
 
@@ -44,14 +56,17 @@ def _add_timings(timings, spent):
 			timings[k] = timings.get(k, 0.0) + v
 
 
-def _write_files(build, wanted, workers, compress, compresslevel, ctx, spent):
+def _write_files(build, wanted, workers, compress, compresslevel, ctx, spent, table='host', shared=None):
 	"""
 	The files of the targets ``wanted``: ``build(i) -> (path, hdus, seconds)`` on ``workers`` threads, then the gzip member.
 	``'zlib'``: the worker that built the bytes compresses and writes them (``fitsio.write``).  ``'device'``: per window of
 	:data:`DEVICE_WINDOW` files the workers build the bytes, the calling thread -- the owner of ``ctx`` -- compresses them in batches
 	(``deflate.gzip_many``), and the workers write the members.  Returns the paths in the order of ``wanted``; adds the seconds to
 	``spent['build']`` and ``spent['gzip']`` (``'device'``: the wall time of the device path, its parts as ``deflate.gzip_many`` names
-	them in ``spent['gzip_parts']``, and ``spent['write']`` for the files).
+	them in ``spent['gzip_parts']``, and ``spent['write']`` for the files).  ``table='device'`` (with ``'device'``):
+	``build(i) -> (path, LightcurvePieces, source, seconds)`` -- the host pieces of the file and the series its table is made of --, and
+	the window's bytes are completed on the device before they are compressed from there (:func:`_pack_window`, which takes ``shared``
+	and adds ``spent['table']`` and ``spent['place']``; ``deflate.gzip_device``).
 	"""
 	import time as _clock
 	workers = min(MAX_WORKERS, os.cpu_count() or 1) if workers is None else max(1, min(MAX_WORKERS, int(workers)))
@@ -90,10 +105,19 @@ def _write_files(build, wanted, workers, compress, compresslevel, ctx, spent):
 	try:
 		run = (lambda f, jobs: [f(j) for j in jobs]) if serial else (lambda f, jobs: list(pool.map(f, jobs)))
 		for a in range(0, len(wanted), DEVICE_WINDOW):
-			built = run(build_one, wanted[a:a + DEVICE_WINDOW])
-			spent['build'] += sum(b[2] for b in built)
-			tb = _clock.perf_counter()
-			members = deflate.gzip_many(ctx, [b[1] for b in built], parts=spent.setdefault('gzip_parts', {}))
+			built = run(build if table == 'device' else build_one, wanted[a:a + DEVICE_WINDOW])
+			spent['build'] += sum(b[-1] for b in built)
+			parts = spent.setdefault('gzip_parts', {})
+			if table == 'device':
+				d_files, offsets = _pack_window(ctx, built, shared, spent)
+				tb = _clock.perf_counter()
+				try:
+					members = deflate.gzip_device(ctx, d_files, offsets, parts=parts)
+				finally:
+					d_files.free()
+			else:
+				tb = _clock.perf_counter()
+				members = deflate.gzip_many(ctx, [b[1] for b in built], parts=parts)
 			spent['gzip'] += _clock.perf_counter() - tb
 			spent['write'] = spent.get('write', 0.0) + sum(run(write_one, [(b[0], m) for b, m in zip(built, members)]))
 			paths.extend(b[0] for b in built)
@@ -101,6 +125,161 @@ def _write_files(build, wanted, workers, compress, compresslevel, ctx, spent):
 		if pool is not None:
 			pool.shutdown()
 	return paths
+
+
+def _check_table(table, compress):
+	if table not in TABLE:
+		raise ValueError(f"table must be one of {TABLE}, not {table!r}")
+	if table == 'device' and compress != 'device':
+		raise ValueError("table='device' needs compress='device': the table's bytes never exist on the host")
+
+
+def _upload(ctx, block, nbytes):
+	"""The first ``nbytes`` bytes (rounded up to 16) of the page-locked ``block`` into a new device array, queued on the context's stream."""
+	words = round_up(max(int(nbytes), 16), 16) // 4
+	d = ctx.empty(4 * words, 'uint8')
+	ctx._check(ctx.lib.tp_upload_cube_async(ctx.handle, d.ptr, words, block.ptr, words, 1, words))
+	return d
+
+
+class _PackGroup(object):
+	"""The files of a window whose tables one ``tp_lc_table_pack`` writes: one ``T``, one list of kept rows."""
+
+	def __init__(self, T, rows):
+		self.T, self.rows, self.members = int(T), rows, []
+
+
+def _pack_window(ctx, built, shared, spent):
+	"""
+	The device work of one window of ``table='device'`` files.  ``built``: per file ``(path, LightcurvePieces, source, seconds)`` with
+	``source`` a dict ``time, timecorr, cadenceno, pixel_quality`` (length ``T``), ``lc`` (five series of length ``T``: flux, flux_err,
+	flux_background, centroid column, centroid row), ``quality`` (``T`` or None) and ``pos_corr`` (``(T, 2)`` or None); ``shared``: the
+	four vectors when all files have the same (stride 0), else None.  Returns ``(device array of the files' bytes, offsets)`` with every
+	file complete in it: the tables packed on the device (one launch per group of files with one ``T`` and one row list), the host
+	pieces -- primary HDU, the table's header with the downloaded DATASUM, the image HDUs -- uploaded compactly and placed by one
+	``tp_lc_place``.  ``spent``: ``table`` (upload, pack, download of the sums), ``build`` (the headers) and ``place`` are added to.
+	"""
+	import time as _clock
+	lib = ctx.lib
+	n = len(built)
+	t0 = _clock.perf_counter()
+	groups = {}
+	for k, (_path, pieces, src, _t) in enumerate(built):
+		key = (len(src['time']), pieces.rows.tobytes())
+		groups.setdefault(key, _PackGroup(key[0], pieces.rows)).members.append(k)
+	# the files' layout: front | table header | table data | back, every piece a multiple of 2880
+	hdr_bytes = [fitsio._padded(80 * (len(fitsio.bintable_cards('LIGHTCURVE', b[1].columns, b[1].cards, len(b[1].rows))) + 3)) for b in built]
+	unit = [fitsio._padded(ROW_BYTES * len(b[1].rows)) for b in built]
+	sizes = [len(b[1].front) + h + u + len(b[1].back) for b, h, u in zip(built, hdr_bytes, unit)]
+	offsets = np.zeros(n + 1, dtype='uint64')
+	offsets[1:] = np.cumsum(sizes, dtype='uint64')
+	table_at = [int(offsets[k]) + len(built[k][1].front) + hdr_bytes[k] for k in range(n)]
+	# the sources of all groups in one page-locked block: per group the float64 arrays, then the int32 arrays
+	plan, at = [], 0
+	for g in groups.values():
+		m, T = len(g.members), g.T
+		vec = T if shared is not None else m * T
+		has_q = any(built[k][2].get('quality') is not None for k in g.members)
+		has_pc = any(built[k][2].get('pos_corr') is not None for k in g.members)
+		list_rows = len(g.rows) != T
+		lay = {'time': at, 'timecorr': at + 8 * vec, 'lc': at + 16 * vec}
+		at += 16 * vec + 40 * m * T
+		if has_pc:
+			lay['pos_corr'] = at
+			at += 16 * m * T
+		lay['cadenceno'], lay['pixel_quality'] = at, at + 4 * vec
+		at += 8 * vec
+		if has_q:
+			lay['quality'] = at
+			at += 4 * m * T
+		if list_rows:
+			lay['rows'] = at
+			at += 4 * len(g.rows)
+		at = round_up(at, 16)
+		plan.append((g, lay, vec))
+	up = ctx.pinned_block(max(at, 16))
+	d_src = d_files = d_sums = d_host = None
+	host = sums_block = None
+	try:
+		buf = up.array
+		for g, lay, vec in plan:
+			m, T = len(g.members), g.T
+			f8 = lambda name, count: buf[lay[name]:lay[name] + 8 * count].view('float64')   # noqa: E731
+			i4 = lambda name, count: buf[lay[name]:lay[name] + 4 * count].view('int32')     # noqa: E731
+			for name, view in (('time', f8), ('timecorr', f8), ('cadenceno', i4), ('pixel_quality', i4)):
+				dst = view(name, vec)
+				if shared is not None:
+					dst[:] = shared[name]
+				else:
+					for j, k in enumerate(g.members):
+						dst[j * T:(j + 1) * T] = built[k][2][name]
+			lc = f8('lc', 5 * m * T).reshape(5, m, T)
+			pc = f8('pos_corr', 2 * m * T).reshape(m, T, 2) if 'pos_corr' in lay else None
+			q = i4('quality', m * T).reshape(m, T) if 'quality' in lay else None
+			for j, k in enumerate(g.members):
+				src = built[k][2]
+				for p in range(5):
+					lc[p, j] = src['lc'][p]
+				if pc is not None:
+					pc[j] = 0.0 if src.get('pos_corr') is None else src['pos_corr']
+				if q is not None:
+					q[j] = 0 if src.get('quality') is None else src['quality']
+			if 'rows' in lay:
+				i4('rows', len(g.rows))[:] = g.rows
+		d_src = _upload(ctx, up, at)
+		d_files = ctx.empty(max(int(offsets[-1]), 16), 'uint8')
+		d_sums = ctx.empty(8 * n, 'uint8')
+		order = []
+		for g, lay, vec in plan:
+			m, T = len(g.members), g.T
+			stride = 0 if shared is not None else T
+			base = d_src.ptr
+			desc = tp_lc_table_src(base + lay['time'], stride, base + lay['timecorr'], stride, base + lay['cadenceno'], stride, base + lay['pixel_quality'], stride,
+				base + lay['lc'], m * T, T, (base + lay['quality']) if 'quality' in lay else None, T, (base + lay['pos_corr']) if 'pos_corr' in lay else None, 2 * T)
+			out_offsets = np.array([table_at[k] for k in g.members], dtype='uint64')
+			ctx._check(lib.tp_lc_table_pack(ctx.handle, ctypes.byref(desc), (base + lay['rows']) if 'rows' in lay else None, len(g.rows), T, m, d_files.ptr,
+				out_offsets.ctypes.data, d_files.nbytes, d_sums.ptr + 8 * len(order)))
+			order.extend(g.members)
+		sums_block = ctx.pinned_block(8 * n)
+		ctx.download_async(sums_block, d_sums, nbytes=8 * n)
+		ctx.sync()
+		sums = np.array(sums_block.array[:8 * n].view('uint64'))
+		t1 = _clock.perf_counter()
+		spent['table'] = spent.get('table', 0.0) + t1 - t0
+		# the host pieces, compact: front + table header (they touch in the file), then back
+		datasum = dict(zip(order, (int(v) for v in sums)))
+		pieces_bytes, seg = [], []
+		at = 0
+		for k, (_path, pieces, _src, _t) in enumerate(built):
+			head = pieces.front + fitsio.bintable_header('LIGHTCURVE', pieces.columns, pieces.cards, len(pieces.rows), datasum[k])
+			assert len(head) == len(pieces.front) + hdr_bytes[k]
+			for blob, dst in ((head, int(offsets[k])), (pieces.back, table_at[k] + unit[k])):
+				if blob:
+					pieces_bytes.append(blob)
+					seg.append((at, dst, len(blob)))
+					at += len(blob)
+		t2 = _clock.perf_counter()
+		spent['build'] += t2 - t1
+		host = ctx.pinned_block(max(at, 16))
+		pos = 0
+		for blob in pieces_bytes:
+			host.array[pos:pos + len(blob)] = np.frombuffer(blob, dtype='uint8')
+			pos += len(blob)
+		d_host = _upload(ctx, host, at)
+		seg = np.array(seg, dtype='uint64').reshape(-1, 3)
+		so, do, ln = (np.ascontiguousarray(seg[:, c]) for c in range(3))
+		ctx._check(lib.tp_lc_place(ctx.handle, d_host.ptr, d_host.nbytes, so.ctypes.data, do.ctypes.data, ln.ctypes.data, len(seg), d_files.ptr, d_files.nbytes))
+		ctx.sync()                                    # (the page-locked blocks return to the pool below: their transfers are over)
+		spent['place'] = spent.get('place', 0.0) + _clock.perf_counter() - t2
+		out, d_files = d_files, None
+		return out, offsets
+	finally:
+		for d in (d_src, d_sums, d_host, d_files):
+			if d is not None:
+				d.free()
+		for block in (up, host, sums_block):
+			if block is not None:
+				ctx.pinned_release(block)
 
 
 def weightmap_hdu(weightmap, shape, cards=()):
@@ -189,11 +368,52 @@ def lightcurve_hdus(target, starid, sector, camera, ccd, cadence, data_rel, vers
 	no table can hold -- it is cut to the same rows).  ``aperture``: the ``APERTURE`` image with the mask bits already in it
 	(:func:`aperture_with_masks`).  ``image_cards``: the cards of the two image extensions without ``INHERIT`` (:func:`image_cards`).
 	"""
-	cadence = int(cadence)
-	SumImage = np.asarray(sumimage, dtype='float64')
 	indx = np.isfinite(np.asarray(lightcurve['time']))
 	quality = np.asarray(quality)[indx]
 	col = {k: np.asarray(lightcurve[k])[indx] for k in lightcurve.keys()}
+	nan = np.full(len(col['time']), np.nan)
+	arrays = {'TIME': col['time'], 'TIMECORR': col['timecorr'], 'CADENCENO': col['cadenceno'], 'FLUX_RAW': col['flux'], 'FLUX_RAW_ERR': col['flux_err'],
+		'FLUX_BKG': col['flux_background'], 'FLUX_CORR': nan, 'FLUX_CORR_ERR': nan, 'QUALITY': quality, 'PIXEL_QUALITY': col['quality'],
+		'MOM_CENTR1': col['pos_centroid'][:, 0], 'MOM_CENTR2': col['pos_centroid'][:, 1], 'POS_CORR1': col['pos_corr'][:, 0], 'POS_CORR2': col['pos_corr'][:, 1]}
+	columns = [dict(c, array=arrays[c['name']]) for c in table_columns()]
+	tcards = _time_cards(col['time'], cadence, header, num_frm, n_readout)
+	return ([fitsio.primary_hdu(_primary_cards(target, starid, sector, camera, ccd, data_rel, version, method, ticver, header, additional_headers, weightmap is not None)),
+		fitsio.bintable_hdu('LIGHTCURVE', columns, tcards)] + _image_hdus(sumimage, aperture, image_cards, weightmap))
+
+
+#: what :func:`lightcurve_pieces` returns: ``front`` (the bytes before the table header: the primary HDU), ``columns`` and ``cards`` of the
+#: ``LIGHTCURVE`` table (``fitsio.bintable_header('LIGHTCURVE', columns, cards, len(rows), datasum)`` is its header), ``rows`` (int32: the
+#: kept cadences, rising) and ``back`` (the bytes behind the table's data unit: ``SUMIMAGE``, ``APERTURE`` and a Halo target's ``WEIGHTMAP``)
+LightcurvePieces = namedtuple('LightcurvePieces', 'front columns cards rows back')
+
+
+def lightcurve_pieces(target, starid, sector, camera, ccd, cadence, data_rel, version, method, ticver, header, num_frm, n_readout,
+	additional_headers, time, sumimage, aperture, image_cards, weightmap=None):
+	"""
+	The light-curve file of :func:`lightcurve_hdus` without the ``LIGHTCURVE`` table's data unit and without the header that needs its
+	``DATASUM``, for a table whose bytes are formed elsewhere (``tp_lc_table_pack``): a :data:`LightcurvePieces`.  The arguments are
+	those of :func:`lightcurve_hdus` with ``time`` (the ``time`` column at its full length) in place of the columns;
+	``front + bintable_header(...) + data unit + back`` is ``b''.join(lightcurve_hdus(...))``.
+	"""
+	time = np.asarray(time)
+	rows = np.flatnonzero(np.isfinite(time)).astype('int32')
+	return LightcurvePieces(
+		fitsio.primary_hdu(_primary_cards(target, starid, sector, camera, ccd, data_rel, version, method, ticver, header, additional_headers, weightmap is not None)),
+		table_columns(), _time_cards(time[rows], cadence, header, num_frm, n_readout), rows, b''.join(_image_hdus(sumimage, aperture, image_cards, weightmap)))
+
+
+def _image_hdus(sumimage, aperture, image_cards, weightmap):
+	"""``SUMIMAGE``, ``APERTURE`` and, for a Halo target, ``WEIGHTMAP``: the cards of the stamp, then INHERIT."""
+	SumImage = np.asarray(sumimage, dtype='float64')
+	icards = list(image_cards) + [card('INHERIT', True, 'inherit the primary header')]
+	hdus = [fitsio.image_hdu('SUMIMAGE', SumImage, icards), fitsio.image_hdu('APERTURE', np.asarray(aperture, dtype='int32'), icards)]
+	if weightmap is not None:
+		hdus.append(weightmap_hdu(weightmap, SumImage.shape, icards))
+	return hdus
+
+
+def _primary_cards(target, starid, sector, camera, ccd, data_rel, version, method, ticver, header, additional_headers, has_weightmap):
+	"""The cards of the primary header (:1463-1505)."""
 	tgt = target
 	undef = fitsio.Undefined()
 
@@ -206,7 +426,7 @@ def lightcurve_hdus(target, starid, sector, camera, ccd, cadence, data_rel, vers
 		pmtotal = np.sqrt(tgt['pm_ra']**2 + tgt['pm_decl']**2)
 	hdr = header
 	prim = [
-		card('NEXTEND', 3 + int(weightmap is not None), 'number of standard extensions'), card('EXTNAME', 'PRIMARY', 'name of extension'),
+		card('NEXTEND', 3 + int(has_weightmap), 'number of standard extensions'), card('EXTNAME', 'PRIMARY', 'name of extension'),
 		card('ORIGIN', 'TASOC/Aarhus', 'institution responsible for creating this file'),
 		card('DATE', datetime.datetime.now().strftime("%Y-%m-%d"), 'date the file was created'),
 		card('TELESCOP', 'TESS', 'telescope'), card('INSTRUME', 'TESS Photometer', 'detector type'),
@@ -232,37 +452,46 @@ def lightcurve_hdus(target, starid, sector, camera, ccd, cadence, data_rel, vers
 		else:
 			prim.append(card(key, value))
 	prim.append(card('DATAVAL', 0, 'Data validation flags'))
+	return prim
 
-	n = len(col['time'])
-	nan = np.full(n, np.nan)
+
+def table_columns():
+	"""The 14 columns of the ``LIGHTCURVE`` table (:1507-1600) as :func:`fitsio.bintable_hdu` takes them, without their arrays: 96 bytes
+	per row, ``D E J D D D D D J J D D D D`` -- the layout csrc/lctable_rules.h restates."""
 	f64 = 'column format: 64-bit floating point'
 	i32 = 'column format: signed 32-bit integer'
 	disp = 'column display format'
 
-	def column(name, fmt, arr, unit=None, dsp=None, title=None, unitc=None):
-		return {'name': name, 'format': fmt, 'array': arr, 'unit': unit, 'disp': dsp,
+	def column(name, fmt, unit=None, dsp=None, title=None, unitc=None):
+		return {'name': name, 'format': fmt, 'unit': unit, 'disp': dsp,
 			'comments': {'TTYPE': title, 'TFORM': f64 if fmt == 'D' else ('column format: 32-bit floating point' if fmt == 'E' else i32),
 				'TUNIT': unitc, 'TDISP': disp}}
-	columns = [
-		column('TIME', 'D', col['time'], 'BJD - 2457000, days', 'D14.7', 'column title: data time stamps', 'column units: Barycenter corrected TESS Julian'),
-		column('TIMECORR', 'E', col['timecorr'], 'd', 'E13.6', 'column title: barycenter - timeslice correction', 'column units: day'),
-		column('CADENCENO', 'J', col['cadenceno'], None, 'I10', 'column title: unique cadence number'),
-		column('FLUX_RAW', 'D', col['flux'], 'e-/s', 'E26.17', 'column title: photometric flux', 'column units: electrons per second'),
-		column('FLUX_RAW_ERR', 'D', col['flux_err'], 'e-/s', 'E26.17', 'column title: photometric flux error', 'column units: electrons per second'),
-		column('FLUX_BKG', 'D', col['flux_background'], 'e-/s', 'E26.17', 'column title: photometric background flux', 'column units: electrons per second'),
-		column('FLUX_CORR', 'D', nan, 'ppm', 'E26.17', 'column title: corrected photometric flux', 'column units: rel. flux in parts-per-million'),
-		column('FLUX_CORR_ERR', 'D', nan, 'ppm', 'E26.17', 'column title: corrected photometric flux error', 'column units: parts-per-million'),
-		column('QUALITY', 'J', quality, None, 'B16.16', 'column title: photometry quality flags'),
-		column('PIXEL_QUALITY', 'J', col['quality'], None, 'B16.16', 'column title: pixel quality flags'),
-		column('MOM_CENTR1', 'D', col['pos_centroid'][:, 0], 'pixels', 'F10.5', 'column title: moment-derived column centroid', 'column units: pixels'),
-		column('MOM_CENTR2', 'D', col['pos_centroid'][:, 1], 'pixels', 'F10.5', 'column title: moment-derived row centroid', 'column units: pixels'),
-		column('POS_CORR1', 'D', col['pos_corr'][:, 0], 'pixels', 'F14.7', 'column title: column position correction', 'column units: pixels'),
-		column('POS_CORR2', 'D', col['pos_corr'][:, 1], 'pixels', 'F14.7', 'column title: row position correction', 'column units: pixels'),
+	return [
+		column('TIME', 'D', 'BJD - 2457000, days', 'D14.7', 'column title: data time stamps', 'column units: Barycenter corrected TESS Julian'),
+		column('TIMECORR', 'E', 'd', 'E13.6', 'column title: barycenter - timeslice correction', 'column units: day'),
+		column('CADENCENO', 'J', None, 'I10', 'column title: unique cadence number'),
+		column('FLUX_RAW', 'D', 'e-/s', 'E26.17', 'column title: photometric flux', 'column units: electrons per second'),
+		column('FLUX_RAW_ERR', 'D', 'e-/s', 'E26.17', 'column title: photometric flux error', 'column units: electrons per second'),
+		column('FLUX_BKG', 'D', 'e-/s', 'E26.17', 'column title: photometric background flux', 'column units: electrons per second'),
+		column('FLUX_CORR', 'D', 'ppm', 'E26.17', 'column title: corrected photometric flux', 'column units: rel. flux in parts-per-million'),
+		column('FLUX_CORR_ERR', 'D', 'ppm', 'E26.17', 'column title: corrected photometric flux error', 'column units: parts-per-million'),
+		column('QUALITY', 'J', None, 'B16.16', 'column title: photometry quality flags'),
+		column('PIXEL_QUALITY', 'J', None, 'B16.16', 'column title: pixel quality flags'),
+		column('MOM_CENTR1', 'D', 'pixels', 'F10.5', 'column title: moment-derived column centroid', 'column units: pixels'),
+		column('MOM_CENTR2', 'D', 'pixels', 'F10.5', 'column title: moment-derived row centroid', 'column units: pixels'),
+		column('POS_CORR1', 'D', 'pixels', 'F14.7', 'column title: column position correction', 'column units: pixels'),
+		column('POS_CORR2', 'D', 'pixels', 'F14.7', 'column title: row position correction', 'column units: pixels'),
 	]
+
+
+def _time_cards(time, cadence, hdr, num_frm, n_readout):
+	"""The cards of the ``LIGHTCURVE`` header before the columns' (:1602-1641) from the kept ``time`` values."""
+	cadence = int(cadence)
+	n = len(time)
 	# time keywords (:1602-1641)
 	tdel = cadence / 86400
-	tstart = float(col['time'][0] - tdel/2) if n else float('nan')
-	tstop = float(col['time'][-1] + tdel/2) if n else float('nan')
+	tstart = float(time[0] - tdel/2) if n else float('nan')
+	tstop = float(time[-1] + tdel/2) if n else float('nan')
 	telapse = tstop - tstart
 	frametime, int_time, readtime = 2.0, 1.98, 0.02
 	if hdr.get('CRMITEN'):
@@ -271,7 +500,7 @@ def lightcurve_hdus(target, starid, sector, camera, ccd, cadence, data_rel, vers
 	else:
 		deadc = int_time / frametime
 	bjdref = 2457000
-	tcards = [
+	return [
 		card('INHERIT', True, 'inherit the primary header'),
 		card('TIMEREF', 'SOLARSYSTEM', 'barycentric correction applied to times'),
 		card('TIMESYS', 'TDB', 'time system is Barycentric Dynamical Time (TDB)'),
@@ -290,13 +519,6 @@ def lightcurve_hdus(target, starid, sector, camera, ccd, cadence, data_rel, vers
 		card('FRAMETIM', frametime, '[s] frame time (INT_TIME + READTIME)'), card('NUM_FRM', num_frm, 'number of frames per time stamp'),
 		card('NREADOUT', int(n_readout), 'number of read per cadence'),
 	]
-	# image extensions: the cards of the stamp, then INHERIT
-	icards = list(image_cards) + [card('INHERIT', True, 'inherit the primary header')]
-	hdus = [fitsio.primary_hdu(prim), fitsio.bintable_hdu('LIGHTCURVE', columns, tcards),
-		fitsio.image_hdu('SUMIMAGE', SumImage, icards), fitsio.image_hdu('APERTURE', np.asarray(aperture, dtype='int32'), icards)]
-	if weightmap is not None:
-		hdus.append(weightmap_hdu(weightmap, SumImage.shape, icards))
-	return hdus
 
 
 #--------------------------------------------------------------------------------------------------
@@ -337,7 +559,7 @@ def _crop(image, stamp, row0, col0):
 
 
 def save_lightcurves(results, stack, output_folder, info, time, quality, version, timecorr=None, cadenceno=None, targets=None, workers=None,
-	compresslevel=9, timings=None, compress='zlib'):
+	compresslevel=9, timings=None, compress='zlib', table='host'):
 	"""
 	Write the light-curve file of every target of ``results`` (a ``tessphot.BatchResults`` over ``stack``) whose final status is OK
 	or WARNING -- the rule of ``run_plugin`` (tessphot.py:52-53) --, as the per-target run would: same name, same folder,
@@ -348,10 +570,16 @@ def save_lightcurves(results, stack, output_folder, info, time, quality, version
 	workers build the bytes, the calling thread compresses them on the stack's device (``deflate.gzip_many``) and the workers write the
 	members -- the same content in other compressed bytes, which depend on the content alone; ``compresslevel`` is ignored, and
 	``timings['gzip']`` is the wall time of the device path (``timings['write']``: writing the files, summed over the workers).
+	``table``: ``'host'`` (the default) or, with ``compress='device'`` only, ``'device'``: the workers build the headers and the image
+	HDUs, and per window the calling thread uploads the light curves, ``QUALITY`` rows and ``pos_corr``, writes the ``LIGHTCURVE`` data
+	units with their DATASUMs on the device in one launch (``tp_lc_table_pack``: ``time`` is shared, so are the kept rows), places the
+	host pieces around them and compresses from that buffer -- the same file bytes as ``compress='device'`` alone.  ``timings['table']``:
+	the wall time of upload, pack and the download of the sums; ``timings['build']`` is then the host pieces only.
 	"""
 	import time as _clock
 	if compress not in COMPRESS:
 		raise ValueError(f"compress must be one of {COMPRESS}, not {compress!r}")
+	_check_table(table, compress)
 	if version is None:
 		raise ValueError("VERSION has not been set")
 	if targets is None:
@@ -408,13 +636,22 @@ def save_lightcurves(results, stack, output_folder, info, time, quality, version
 		# (the aperture plugin positions on its photometry mask; the Halo plugin has no position mask)
 		aperture = aperture_with_masks(ffi_aperture(sumimage, stamp, bpu, stack.row0, stack.col0), r.final_phot_mask, None if r.method == 'halo' else r.final_phot_mask)
 		ta = _clock.perf_counter()
-		hdus = lightcurve_hdus(target, int(results.starid[i]), info.sector, info.camera, info.ccd, info.cadence, info.data_rel, version, r.method, info.ticver,
-			info.header, info.num_frm, info.n_readout, headers, lc, flag_series[i], sumimage, aperture, image_cards(stamp, info.wcs_header), weightmap=r.halo_weightmap)
+		args = (target, int(results.starid[i]), info.sector, info.camera, info.ccd, info.cadence, info.data_rel, version, r.method, info.ticver,
+			info.header, info.num_frm, info.n_readout, headers)
 		path = os.path.join(output_folder, lightcurve_filename(results.starid[i], info.sector, info.camera, info.ccd, info.cadence, info.data_rel, version))
+		if table == 'device':
+			pieces = lightcurve_pieces(*args, time, sumimage, aperture, image_cards(stamp, info.wcs_header), weightmap=r.halo_weightmap)
+			spent_here = _clock.perf_counter() - ta
+			centroid = np.asarray(lc['pos_centroid'])
+			source = {'time': time, 'lc': (lc['flux'], lc['flux_err'], lc['flux_background'], centroid[:, 0], centroid[:, 1]), 'quality': flag_series[i],
+				'pos_corr': results.pos_corr[i] if results.pos_corr is not None else None}
+			return path, pieces, source, spent_here
+		hdus = lightcurve_hdus(*args, lc, flag_series[i], sumimage, aperture, image_cards(stamp, info.wcs_header), weightmap=r.halo_weightmap)
 		return path, hdus, _clock.perf_counter() - ta
 
 	paths = [None] * n
-	for i, path in zip(wanted, _write_files(one, wanted, workers, compress, compresslevel, getattr(stack, 'ctx', None), spent)):
+	vectors = {'time': time, 'timecorr': shared['timecorr'], 'cadenceno': shared['cadenceno'], 'pixel_quality': shared['quality']}   # (table='device': stride 0)
+	for i, path in zip(wanted, _write_files(one, wanted, workers, compress, compresslevel, getattr(stack, 'ctx', None), spent, table=table, shared=vectors)):
 		paths[int(i)] = path
 	if timings is not None:
 		_add_timings(timings, spent)
@@ -423,7 +660,7 @@ def save_lightcurves(results, stack, output_folder, info, time, quality, version
 	return paths
 
 
-def save_tpf_lightcurves(results, output_folder, version, workers=None, compresslevel=9, timings=None, compress='zlib', ctx=None):
+def save_tpf_lightcurves(results, output_folder, version, workers=None, compresslevel=9, timings=None, compress='zlib', ctx=None, table='host'):
 	"""
 	The light-curve files of a ``tessphot.TpfBatchResults`` (a chunk of ``tessphot_tpfs``): for every target whose final status is OK or
 	WARNING the file ``tessphot('aperture', starid, TpfStampSource(...), output_folder, datasource='tpf')`` writes.  Every file has a
@@ -432,10 +669,13 @@ def save_tpf_lightcurves(results, output_folder, version, workers=None, compress
 	the ``APERTURE`` image is the file's without SPOC's mask and centroid flags plus this run's, the image cards are the stamp's
 	limits.  Threads, ``compresslevel``, ``timings`` (``build`` / ``gzip``), ``compress`` and the return value as :func:`save_lightcurves`;
 	``compress='device'`` runs on ``ctx`` (default: the context the results were computed on), whose owner the calling thread must be.
+	``table='device'`` (with ``compress='device'``) as in :func:`save_lightcurves`; here every file has its own ``time`` .. ``PIXEL_QUALITY``,
+	so the vectors are strided per target and there is one ``tp_lc_table_pack`` per set of files with one length and one list of kept rows.
 	"""
 	import time as _clock
 	if compress not in COMPRESS:
 		raise ValueError(f"compress must be one of {COMPRESS}, not {compress!r}")
+	_check_table(table, compress)
 	ctx = getattr(results, 'ctx', None) if ctx is None else ctx
 	if compress == 'device' and ctx is None:
 		raise ValueError("compress='device' needs the context of the batch (ctx=)")
@@ -462,14 +702,23 @@ def save_tpf_lightcurves(results, output_folder, version, workers=None, compress
 		T = len(r.lightcurve['time'])
 		aperture = aperture_with_masks(results.aperture_image(i), r.final_phot_mask, r.final_phot_mask)
 		ta = _clock.perf_counter()
-		hdus = lightcurve_hdus({'tmag': float(results.tmag[i])}, int(results.starid[i]), info.sector, info.camera, info.ccd, info.cadence, info.data_rel, version, r.method,
-			info.ticver, info.header, info.num_frm, info.n_readout, headers, r.lightcurve, np.zeros(T, dtype='int32'), results.sumimage(i), aperture, image_cards(stamp))
+		args = ({'tmag': float(results.tmag[i])}, int(results.starid[i]), info.sector, info.camera, info.ccd, info.cadence, info.data_rel, version, r.method,
+			info.ticver, info.header, info.num_frm, info.n_readout, headers)
 		path = os.path.join(output_folder, lightcurve_filename(results.starid[i], info.sector, info.camera, info.ccd, info.cadence, info.data_rel, version))
+		if table == 'device':
+			lc = r.lightcurve
+			pieces = lightcurve_pieces(*args, lc['time'], results.sumimage(i), aperture, image_cards(stamp))
+			spent_here = _clock.perf_counter() - ta
+			centroid = np.asarray(lc['pos_centroid'])
+			source = {'time': lc['time'], 'timecorr': lc['timecorr'], 'cadenceno': lc['cadenceno'], 'pixel_quality': lc['quality'],
+				'lc': (lc['flux'], lc['flux_err'], lc['flux_background'], centroid[:, 0], centroid[:, 1]), 'quality': None, 'pos_corr': lc['pos_corr']}
+			return path, pieces, source, spent_here
+		hdus = lightcurve_hdus(*args, r.lightcurve, np.zeros(T, dtype='int32'), results.sumimage(i), aperture, image_cards(stamp))
 		return path, hdus, _clock.perf_counter() - ta
 
 	spent = {'build': 0.0, 'gzip': 0.0}
 	paths = [None] * n
-	for i, path in zip(wanted, _write_files(one, wanted, workers, compress, compresslevel, ctx, spent)):
+	for i, path in zip(wanted, _write_files(one, wanted, workers, compress, compresslevel, ctx, spent, table=table)):
 		paths[int(i)] = path
 	if timings is not None:
 		_add_timings(timings, spent)

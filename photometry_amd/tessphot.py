@@ -215,7 +215,8 @@ class BatchResults(object):
 	def __len__(self):
 		return len(self.frames)
 
-	def save_lightcurves(self, output_folder, info, time, quality, version, *, timecorr=None, cadenceno=None, targets=None, workers=None, compresslevel=9, compress='zlib'):
+	def save_lightcurves(self, output_folder, info, time, quality, version, *, timecorr=None, cadenceno=None, targets=None, workers=None, compresslevel=9, compress='zlib',
+		table='host'):
 		"""
 		Write ``tess…-tasoc_lc.fits.gz`` for every target whose final status is OK or WARNING (the rule of :func:`run_plugin`): the file
 		``tessphot('aperture', ...)`` -- or, for a target switched to Halo photometry, ``tessphot(None, ...)`` -- writes for it, into
@@ -227,14 +228,16 @@ class BatchResults(object):
 		without flags).  ``workers`` threads (default ``min(16, os.cpu_count())``, never more than 16) build and compress the files;
 		``compresslevel`` is gzip's (9: what the per-target plugin writes with).  ``compress='device'``: the workers build the bytes, the
 		calling thread compresses them on the stack's device and the workers write the members (``lcfile.save_lightcurves``; the same
-		content, other compressed bytes; ``compresslevel`` is ignored).  Returns the paths, ``None`` where no file was written
+		content, other compressed bytes; ``compresslevel`` is ignored).  ``table='device'`` (with ``compress='device'`` only; anything else
+		raises ``ValueError``): the ``LIGHTCURVE`` data units are written on the device with their DATASUMs straight into the encoder's input
+		(``tp_lc_table_pack``) and the workers build headers and image HDUs only -- the same file bytes.  Returns the paths, ``None`` where no file was written
 		(also ``self.filepaths``); ``results[i]._details['filepath_lightcurve']`` is set as the plugin sets it.
 		"""
 		from . import lcfile
 		if self.stack is None:
 			raise ValueError("these results do not know their frame stack: run the batch through tessphot_frames")
 		return lcfile.save_lightcurves(self, self.stack, output_folder, info, time, quality, version, timecorr=timecorr, cadenceno=cadenceno,
-			targets=self.targets if targets is None else targets, workers=workers, compresslevel=compresslevel, compress=compress)
+			targets=self.targets if targets is None else targets, workers=workers, compresslevel=compresslevel, compress=compress, table=table)
 
 	def edge_flux_column(self):
 		"""``details['edge_flux']`` of every target as a column (NaN: none): the flux on the stuck edge of the haloswitch quick break,
@@ -378,7 +381,7 @@ def _pos_corr(ctx, movement, targets, time, timecorr):
 	return movement.jitter_many(t, targets['column'], targets['row']).to_host()
 
 
-def _finish_batch(ctx, out, stack, targets, time, quality, timecorr, cadenceno, movement, output_folder, fileinfo, version, compress='zlib'):
+def _finish_batch(ctx, out, stack, targets, time, quality, timecorr, cadenceno, movement, output_folder, fileinfo, version, compress='zlib', table='host'):
 	"""What both batched entries do with a batch after the method switch: ``pos_corr``, the stack and targets, the files when asked for."""
 	if movement is not None:
 		out.pos_corr = _pos_corr(ctx, movement, targets, time, timecorr)
@@ -386,12 +389,12 @@ def _finish_batch(ctx, out, stack, targets, time, quality, timecorr, cadenceno, 
 	if output_folder is not None:
 		if fileinfo is None:
 			raise ValueError("output_folder needs fileinfo (a photometry_amd.lcfile.FileInfo)")
-		out.save_lightcurves(output_folder, fileinfo, time, quality, version, timecorr=timecorr, cadenceno=cadenceno, compress=compress)
+		out.save_lightcurves(output_folder, fileinfo, time, quality, version, timecorr=timecorr, cadenceno=cadenceno, compress=compress, table=table)
 	return out
 
 
 def tessphot_frames(ctx, stack, targets, catalog, time, quality, settings=None, sector=None, timecorr=None, cadenceno=None, movement=None,
-	output_folder=None, fileinfo=None, version=None, compress='zlib'):
+	output_folder=None, fileinfo=None, version=None, compress='zlib', table='host'):
 	"""
 	Aperture photometry of every target of a CCD region resident in HBM (:class:`photometry_amd.pipeline.FrameStack`), stamp
 	resizes included: what ``tessphot('aperture', ...)`` returns per target, for the whole batch in a few device passes.
@@ -403,26 +406,28 @@ def tessphot_frames(ctx, stack, targets, catalog, time, quality, settings=None, 
 	curve's ``'pos_corr'`` are then its jitter at the targets' positions at ``time - timecorr``, as the plugins write it.
 	``output_folder`` with ``fileinfo`` (a :class:`~photometry_amd.lcfile.FileInfo`) and ``version``: the light-curve files of the batch
 	are written as well (:meth:`BatchResults.save_lightcurves`), as ``run_plugin`` writes them per target; ``compress``: ``'zlib'`` or
-	``'device'``, as there.
+	``'device'``, and ``table``: ``'host'`` or ``'device'``, as there.
 	Returns a :class:`BatchResults`: columns for the whole batch, one :class:`BatchResult` per target on demand (``results[i]``).
 	"""
-	from . import pipeline
+	from . import pipeline, lcfile
+	lcfile._check_table(table, compress)
 	res = pipeline.aperture_frames(ctx, stack, targets, catalog, time, quality, settings=settings)
 	out = _halo_switch_frames(ctx, stack, BatchResults(res, targets['starid']), targets, catalog, time, quality, settings, sector, timecorr, cadenceno)
-	return _finish_batch(ctx, out, stack, targets, time, quality, timecorr, cadenceno, movement, output_folder, fileinfo, version, compress)
+	return _finish_batch(ctx, out, stack, targets, time, quality, timecorr, cadenceno, movement, output_folder, fileinfo, version, compress, table)
 
 
 def tessphot_frames_pipelined(ctx, stack, batches, catalog, time, quality, settings=None, in_flight=4, sector=None, timecorr=None, cadenceno=None,
-	movement=None, output_folder=None, fileinfo=None, version=None, compress='zlib'):
+	movement=None, output_folder=None, fileinfo=None, version=None, compress='zlib', table='host'):
 	"""
 	:func:`tessphot_frames` over consecutive batches of targets of one CCD region -- what a run over a whole CCD does, a few
 	thousand targets per call -- with ``in_flight`` batches on the device at a time (``pipeline.aperture_frames_pipelined``: the
 	first round of a batch runs under the latency-bound resize rounds of the one before it).  ``batches``: an iterable of
 	``targets`` dicts; yields one :class:`BatchResults` per batch, in order, equal to what a call of its own returns (the switch to
 	Halo photometry included, applied to each batch before it is yielded; ``movement`` as there; with ``output_folder`` / ``fileinfo`` /
-	``version`` the files of each batch are written as it is collected, ``compress`` as there).
+	``version`` the files of each batch are written as it is collected, ``compress`` and ``table`` as there).
 	"""
-	from . import pipeline
+	from . import pipeline, lcfile
+	lcfile._check_table(table, compress)
 	batches = list(batches) if not hasattr(batches, '__next__') else batches
 	seen = []
 	def feed():
@@ -431,7 +436,7 @@ def tessphot_frames_pipelined(ctx, stack, batches, catalog, time, quality, setti
 			yield t
 	for k, res in enumerate(pipeline.aperture_frames_pipelined(ctx, stack, feed(), catalog, time, quality, settings=settings, in_flight=in_flight)):
 		out = _halo_switch_frames(ctx, stack, BatchResults(res, seen[k]['starid']), seen[k], catalog, time, quality, settings, sector, timecorr, cadenceno)
-		yield _finish_batch(ctx, out, stack, seen[k], time, quality, timecorr, cadenceno, movement, output_folder, fileinfo, version, compress)
+		yield _finish_batch(ctx, out, stack, seen[k], time, quality, timecorr, cadenceno, movement, output_folder, fileinfo, version, compress, table)
 
 
 def tessphot_batch(ctx, scene, cubes='host'):
@@ -509,11 +514,12 @@ class TpfBatchResults(BatchResults):
 		#: the context the chunk was computed on (set by :func:`tessphot_tpfs`): where ``compress='device'`` runs
 		self.ctx = None
 
-	def save_lightcurves(self, output_folder, version, workers=None, compresslevel=9, compress='zlib'):
+	def save_lightcurves(self, output_folder, version, workers=None, compresslevel=9, compress='zlib', table='host'):
 		"""Write the light-curve file of every OK / WARNING target as the per-file plugin call does (``lcfile.save_tpf_lightcurves``);
-		``compress='device'`` compresses on the context of the batch, by the calling thread."""
+		``compress='device'`` compresses on the context of the batch, by the calling thread; ``table='device'`` (with it only) writes the
+		``LIGHTCURVE`` data units on the device as well, one ``tp_lc_table_pack`` per set of files with one length and one list of kept rows."""
 		from . import lcfile
-		return lcfile.save_tpf_lightcurves(self, output_folder, version, workers=workers, compresslevel=compresslevel, compress=compress, ctx=self.ctx)
+		return lcfile.save_tpf_lightcurves(self, output_folder, version, workers=workers, compresslevel=compresslevel, compress=compress, ctx=self.ctx, table=table)
 
 	def aperture_image(self, i):
 		"""The APERTURE image of file ``i`` without SPOC's mask and centroid flags: ``BasePhotometry.aperture`` of a ``tpf`` run."""
@@ -640,7 +646,7 @@ def _tpf_chunk(ctx, files, headers, starid, catalog, targets, verify):
 
 
 def tessphot_tpfs(ctx, files, catalog, targets=None, settings=None, output_folder=None, version=None, chunk_files=None, verify=True,
-	workers=None, compresslevel=9, compress='zlib'):
+	workers=None, compresslevel=9, compress='zlib', table='host'):
 	"""
 	Aperture photometry of many target pixel files: what ``tessphot('aperture', starid, tpf.TpfStampSource(loaded, catalog,
 	targets=targets), output_folder, datasource='tpf', version=version)`` returns and writes per file, with one pass of the fused
@@ -657,7 +663,8 @@ def tessphot_tpfs(ctx, files, catalog, targets=None, settings=None, output_folde
 	are freed before the next chunk is loaded.
 	``output_folder`` with ``version``: the ``tess…-tasoc_lc.fits.gz`` of every OK / WARNING target is written on ``workers`` threads (at
 	most 16) with gzip's ``compresslevel`` -- or, with ``compress='device'``, compressed on the device by the calling thread while the
-	workers build the bytes and write the members (``lcfile.save_tpf_lightcurves``) --; ``QUALITY`` is all zero, what the plugin writes for a source without pixel flags.
+	workers build the bytes and write the members (``lcfile.save_tpf_lightcurves``), and with ``table='device'`` besides, the tables' data
+	units written on the device too (``ValueError`` without ``compress='device'``) --; ``QUALITY`` is all zero, what the plugin writes for a source without pixel flags.
 	``verify``: the ``DATASUM`` check of ``tpf.load_tpfs``.
 	This is ``tessphot('aperture', ...)``: with ``[halo] enabled`` in the settings nothing is switched to Halo photometry, which is logged.
 	"""
@@ -670,6 +677,8 @@ def tessphot_tpfs(ctx, files, catalog, targets=None, settings=None, output_folde
 		raise ValueError("VERSION has not been set")
 	if compress not in ('zlib', 'device'):
 		raise ValueError(f"compress must be one of ('zlib', 'device'), not {compress!r}")
+	from . import lcfile
+	lcfile._check_table(table, compress)
 	settings = load_settings() if settings is None else settings
 	if halo.enabled(settings):
 		logger.info("Halo photometry is enabled in the settings, but batches of target pixel files do not switch methods: aperture results are kept.")
@@ -683,5 +692,5 @@ def tessphot_tpfs(ctx, files, catalog, targets=None, settings=None, output_folde
 		out = _tpf_chunk(ctx, files[a:b], headers[a:b], starid[a:b], catalog, targets, verify)
 		out.ctx = ctx
 		if output_folder is not None:
-			out.save_lightcurves(output_folder, version, workers=workers, compresslevel=compresslevel, compress=compress)
+			out.save_lightcurves(output_folder, version, workers=workers, compresslevel=compresslevel, compress=compress, table=table)
 		yield out

@@ -11,7 +11,8 @@ three times; all three times are given beside the best.
              its upload and its download of ``(N, T)`` int32 from a host clock, and the numpy restatement of the same reduction
              (``np.any(flags[:, r1:r2, c1:c2] & 4, axis=(1, 2))`` per target) on one host core;
 ``files``    ``save_lightcurves`` at ``workers`` 1 and 16 and ``compresslevel`` 9 and 1: files per second, and the share of the
-             workers' time spent in gzip (the rest builds the bytes of the HDUs);
+             workers' time spent in gzip (the rest builds the bytes of the HDUs); ``--compress device`` and, with it, ``--table host
+             device``: the device's DEFLATE encoder and the ``LIGHTCURVE`` data units written on the device (``tp_lc_table_pack``, DESIGN.md 21);
 ``plugin``   the per-target plugin loop (``run_plugin(AperturePhotometry, ...)`` with its ``save_lightcurve``) over the first
              ``--plugin-targets`` targets: what a caller had to do for the files before.
 """
@@ -61,6 +62,7 @@ def main():
 	ap.add_argument('--out', default=None)
 	ap.add_argument('--compress', choices=('zlib', 'device'), nargs='+', default=['zlib'], help="how the files are compressed; 'device': one run per worker count")
 	ap.add_argument('--compresslevel', type=int, nargs='+', default=[9, 1], help="gzip's levels with --compress zlib")
+	ap.add_argument('--table', choices=('host', 'device'), nargs='+', default=['host'], help="who writes the LIGHTCURVE data units; 'device' runs with --compress device only")
 	ap.add_argument('--skip-baselines', action='store_true', help='the files alone: no flag-series timing on the host, no per-target plugin')
 	a = ap.parse_args()
 	import numpy as np
@@ -117,28 +119,30 @@ def main():
 
 		# ---- the files ----
 		info = FileInfo(14, 2, 3)
-		save_lightcurves(res, stack, os.path.join(root, 'warm'), info, tstamp, quality, 6, targets=targets, workers=16, compresslevel=1, compress=a.compress[-1])      # warm-up
+		for table in (a.table if a.compress[-1] == 'device' else ['host']):      # warm-up
+			save_lightcurves(res, stack, os.path.join(root, 'warm'), info, tstamp, quality, 6, targets=targets, workers=16, compresslevel=1, compress=a.compress[-1], table=table)
 		n_files = int(wanted.sum())
-		for compress, workers, level in [(c, w, l) for c in a.compress for l in (a.compresslevel if c == 'zlib' else a.compresslevel[:1]) for w in (1, 16)]:
+		for compress, table, workers, level in [(c, t, w, l) for c in a.compress for t in (a.table if c == 'device' else ['host'])
+				for l in (a.compresslevel if c == 'zlib' else a.compresslevel[:1]) for w in (1, 16)]:
 			runs = []
 			for k in range(a.repeats):
 				timings = {}
 				t0 = time.perf_counter()
 				paths = save_lightcurves(res, stack, os.path.join(root, f'w{workers}l{level}'), info, tstamp, quality, 6, targets=targets, workers=workers,
-					compresslevel=level, timings=timings, compress=compress)
-				runs.append({'wall_s': time.perf_counter() - t0, 'quality_s': timings['quality'], 'build_s': timings['build'], 'gzip_s': timings['gzip'],
-					'write_s': timings.get('write'), 'gzip_parts_s': timings.get('gzip_parts')})
+					compresslevel=level, timings=timings, compress=compress, table=table)
+				runs.append({'wall_s': time.perf_counter() - t0, 'quality_s': timings['quality'], 'build_s': timings['build'], 'table_s': timings.get('table'), 'place_s': timings.get('place'),
+					'gzip_s': timings['gzip'], 'write_s': timings.get('write'), 'gzip_parts_s': timings.get('gzip_parts')})
 			best = min(runs, key=lambda r: r['wall_s'])
 			size = sum(os.path.getsize(p) for p in paths if p is not None)
 			deflate_kernels = None
 			if compress == 'device':                                          # once more under the kernel profile
 				ctx.profile(True)
 				ctx.profile_reset()
-				save_lightcurves(res, stack, os.path.join(root, f'w{workers}l{level}'), info, tstamp, quality, 6, targets=targets, workers=workers, compress='device')
+				save_lightcurves(res, stack, os.path.join(root, f'w{workers}l{level}'), info, tstamp, quality, 6, targets=targets, workers=workers, compress='device', table=table)
 				ctx.sync()
-				deflate_kernels = {k: v for k, v in ctx.profile_report().items() if 'deflate' in k}
+				deflate_kernels = {k: v for k, v in ctx.profile_report().items() if 'deflate' in k or 'tp_lc_' in k}
 				ctx.profile(False)
-			emit({'step': 'files', 'workers': workers, 'compress': compress, 'deflate_kernels': deflate_kernels, 'compresslevel': level if compress == 'zlib' else None, 'files': n_files, 'runs': runs, 'files_per_s': n_files / best['wall_s'],
+			emit({'step': 'files', 'workers': workers, 'compress': compress, 'table': table, 'deflate_kernels': deflate_kernels, 'compresslevel': level if compress == 'zlib' else None, 'files': n_files, 'runs': runs, 'files_per_s': n_files / best['wall_s'],
 				'gzip_share_of_worker_time': best['gzip_s'] / (best['gzip_s'] + best['build_s']), 'quality_share_of_wall': best['quality_s'] / best['wall_s'],
 				'MB_written': size / 1e6})
 

@@ -78,6 +78,7 @@ def main():
 	ap.add_argument('--out', default=None)
 	ap.add_argument('--compress', choices=('zlib', 'device'), nargs='+', default=['zlib'], help="how the light-curve files of the batch are compressed (one run of the step each)")
 	ap.add_argument('--compresslevel', type=int, nargs='+', default=[9], help="gzip's levels with --compress zlib (one run of the step each)")
+	ap.add_argument('--table', choices=('host', 'device'), nargs='+', default=['host'], help="who writes the LIGHTCURVE data units; 'device' runs with --compress device only")
 	ap.add_argument('--skip-baselines', action='store_true', help='stop behind the batched entry: no per-file runs')
 	a = ap.parse_args()
 	from photometry_amd import tpf, tessphot, tessphot_tpfs, lcfile, STATUS
@@ -126,9 +127,9 @@ def main():
 		emit({'step': 'groups', 'files': N, 'groups': n_groups, 'files_per_s': N / t, 'GB_per_s': file_bytes / t / 1e9, 'all_s': times})
 
 		# ---- the batched entry ----
-		def batch(folder=None, compress='zlib', level=9):
+		def batch(folder=None, compress='zlib', level=9, table='host'):
 			status = []
-			for res in tessphot_tpfs(ctx, files, catalog, output_folder=folder, version=6 if folder else None, compress=compress, compresslevel=level):
+			for res in tessphot_tpfs(ctx, files, catalog, output_folder=folder, version=6 if folder else None, compress=compress, compresslevel=level, table=table):
 				status += [res[i].status for i in range(len(res))]
 			return status
 		batch()                                                               # warm-up
@@ -143,11 +144,11 @@ def main():
 			return save(*args, timings=spent, **kwargs)
 		lcfile.save_tpf_lightcurves = timed_save
 
-		for compress, level in [(c, l) for c in a.compress for l in (a.compresslevel if c == 'zlib' else a.compresslevel[:1])]:
+		for compress, table, level in [(c, t, l) for c in a.compress for t in (a.table if c == 'device' else ['host']) for l in (a.compresslevel if c == 'zlib' else a.compresslevel[:1])]:
 			def batch_files():
 				shutil.rmtree(out_dir, ignore_errors=True)
 				spent.clear()
-				return batch(out_dir, compress, level)
+				return batch(out_dir, compress, level, table)
 			batch_files()                                                     # warm-up of the writer (the device path: code object, buffers)
 			t, times, status = best_of(batch_files)
 			written = len(os.listdir(out_dir))
@@ -157,11 +158,11 @@ def main():
 				ctx.profile_reset()
 				batch_files()
 				ctx.sync()
-				deflate_kernels = {k: v for k, v in ctx.profile_report().items() if 'deflate' in k}
+				deflate_kernels = {k: v for k, v in ctx.profile_report().items() if 'deflate' in k or 'tp_lc_' in k}
 				ctx.profile(False)
 			emit({'step': 'batch_files', 'files': N, 'written': written, 'lc_bytes': sum(os.path.getsize(os.path.join(out_dir, f)) for f in os.listdir(out_dir)),
 				'files_per_s': N / t, 'ms_per_file': t / N * 1e3, 'worker_build_s': spent.get('build'), 'worker_gzip_s': spent.get('gzip'),
-				'workers': min(lcfile.MAX_WORKERS, os.cpu_count() or 1), 'all_s': times, 'compress': compress, 'compresslevel': level if compress == 'zlib' else None,
+				'workers': min(lcfile.MAX_WORKERS, os.cpu_count() or 1), 'all_s': times, 'compress': compress, 'table': table, 'table_s': spent.get('table'), 'place_s': spent.get('place'), 'compresslevel': level if compress == 'zlib' else None,
 				'worker_write_s': spent.get('write'), 'gzip_parts_s': spent.get('gzip_parts'), 'deflate_kernels': deflate_kernels})
 		lcfile.save_tpf_lightcurves = save
 		if a.skip_baselines:
