@@ -910,6 +910,33 @@ int tp_halo_outputs_stack(tp_ctx* ctx, const float* d_images_err, int32_t n_fram
 	const uint8_t* d_fit, const double* d_w, const double* d_l, const int32_t* d_status, const double* h_normfactor, double* d_median,
 	double* d_corr, double* d_flux, double* d_flux_err, double* d_weightmap);
 
+/* ---- Halo photometry of a group of target pixel files straight from their stamp cubes (csrc/halo_cubes.hip) ------------------
+ * The same problems, rules and outputs as the _stack entries above, for targets that share a stamp shape and a number of cadences
+ * and nothing else.  d_images / d_images_err: float32 [n_targets][height * width][t_pitch], time fastest, t_pitch >= n_cad (the
+ * pads are never read); height * width <= 4096.  Every target has its own segments: h_prob_off HOST int32 [n_targets + 1], rising
+ * from 0 by 1 .. 64 per target; problem q = h_prob_off[i] + k is segment k of target i, n_prob = h_prob_off[n_targets] (<= 65535).
+ * h_seg HOST int32 [n_targets][n_cad]: the segment of every cadence of every target, -1 .. n_seg_i - 1 in row i (-1: none; anything
+ * else is rejected); h_quality HOST int32 [n_targets][n_cad].
+ * tp_halo_select_cubes: d_mask uint8 [n_targets][height * width]; the pixel and cadence rules of tp_halo_select_stack per problem (a
+ *   segment without a cadence keeps every mask pixel).  Out: d_pix int32 [n_prob][height * width], d_cad int32 [n_prob][n_cad],
+ *   d_fit uint8 [n_prob][n_cad], d_cadpos int32 [n_targets][n_cad], d_npix / d_ncad int32 [n_prob], as there.
+ * tp_halo_gather_cubes: the n_run problems h_index with h_npix / h_ncad / h_p_offset (HOST, as for tp_halo_gather_stack): d_P in
+ *   tp_halo_tvmin's layout (zero padded rows) and d_fit_out uint8 [sum ncad].
+ * tp_halo_outputs_cubes: d_median float64 [n_prob], d_weightmap float64 [n_prob][height * width], d_corr / d_flux / d_flux_err
+ *   float64 [n_targets][n_cad], defined as for tp_halo_outputs_stack; the sum of d_flux_err runs over the stamp's pixels in ascending
+ *   order in the grouping of numpy's pairwise sum, NaN terms counting as 0, and is 0 for a cadence without a segment.
+ * Nothing uses float atomics: results are bit-reproducible, and a target gives the same bits alone, in a batch and in any chunking. */
+int tp_halo_select_cubes(tp_ctx* ctx, const float* d_images, int32_t n_targets, int32_t height, int32_t width, int32_t n_cad, int32_t t_pitch,
+	const uint8_t* d_mask, const int32_t* h_prob_off, const int32_t* h_seg, const int32_t* h_quality, int32_t bitmask, double minflux,
+	int32_t* d_pix, int32_t* d_cad, uint8_t* d_fit, int32_t* d_cadpos, int32_t* d_npix, int32_t* d_ncad);
+int tp_halo_gather_cubes(tp_ctx* ctx, const float* d_images, int32_t n_targets, int32_t height, int32_t width, int32_t n_cad, int32_t t_pitch,
+	const int32_t* h_prob_off, const int32_t* d_pix, const int32_t* d_cad, const uint8_t* d_fit, int32_t n_run, const int32_t* h_index,
+	const int64_t* h_p_offset, const int32_t* h_npix, const int32_t* h_ncad, float* d_P, uint8_t* d_fit_out);
+int tp_halo_outputs_cubes(tp_ctx* ctx, const float* d_images_err, int32_t n_targets, int32_t height, int32_t width, int32_t n_cad, int32_t t_pitch,
+	const int32_t* h_prob_off, const int32_t* h_seg, const int32_t* d_pix, const int32_t* d_cadpos, int32_t n_run, const int32_t* h_index,
+	const int32_t* h_npix, const int32_t* h_ncad, const uint8_t* d_fit, const double* d_w, const double* d_l, const int32_t* d_status,
+	const double* h_normfactor, double* d_median, double* d_corr, double* d_flux, double* d_flux_err, double* d_weightmap);
+
 /* ---- TAN-SIP world coordinate systems (astropy.wcs as ImageMovementKernel('wcs') uses it, image_motion.py:113-421) ---------
  * One frame's WCS is a block of TP_WCS_PARAMS float64 values packed by photometry_amd/wcs.py: [0:9] the native -> celestial
  * rotation (row-major), [9:11] CRPIX, [11:15] CD, [15:19] CD^-1, [19] A_ORDER, [20] B_ORDER, [21] 1 with SIP, [24:124] A_p_q at

@@ -204,6 +204,10 @@ SIGNATURES = {
 		_p, _p, _p, _p, _p, _p]),
 	'tp_halo_outputs_stack': (c_int, [c_void_p, _p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, _p, c_int32, c_int32, c_int32, _p, _p, _p, c_int32,
 		_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+	'tp_halo_select_cubes': (c_int, [c_void_p, _p, c_int32, c_int32, c_int32, c_int32, c_int32, _p, _p, _p, _p, c_int32, c_double, _p, _p, _p, _p, _p, _p]),
+	'tp_halo_gather_cubes': (c_int, [c_void_p, _p, c_int32, c_int32, c_int32, c_int32, c_int32, _p, _p, _p, _p, c_int32, _p, _p, _p, _p, _p, _p]),
+	'tp_halo_outputs_cubes': (c_int, [c_void_p, _p, c_int32, c_int32, c_int32, c_int32, c_int32, _p, _p, _p, _p, c_int32, _p, _p, _p, _p, _p, _p, _p,
+		_p, _p, _p, _p, _p, _p]),
 	'tp_wcs_pix2world': (c_int, [c_void_p, _p, c_int64, _p, c_int32, c_int32, _p, _p]),
 	'tp_wcs_radec': (c_int, [c_void_p, c_int64, _p, _p]),
 	'tp_wcs_world2pix': (c_int, [c_void_p, _p, c_int32, c_int64, c_int32, _p, _p, c_int32, c_int32, c_double, c_int32, _p, _p, _p]),

@@ -83,6 +83,12 @@ static const char* const kKernelNames[TPK_COUNT] = {
 	"tp_lc_table_pack_kernel",
 	"tp_lc_table_fold_kernel",
 	"tp_lc_place_kernel",
+	"tp_halo_cube_stat_kernel",
+	"tp_halo_cube_cad_kernel",
+	"tp_halo_cube_compact_kernel",
+	"tp_halo_cube_gather_kernel",
+	"tp_halo_cube_norm_kernel",
+	"tp_halo_cube_lightcurve_kernel",
 };
 
 extern "C" {

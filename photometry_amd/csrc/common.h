@@ -81,6 +81,12 @@ enum tp_kernel_id {
 	TPK_LC_TABLE_PACK,
 	TPK_LC_TABLE_FOLD,
 	TPK_LC_PLACE,
+	TPK_HALO_CUBE_STAT,
+	TPK_HALO_CUBE_CAD,
+	TPK_HALO_CUBE_COMPACT,
+	TPK_HALO_CUBE_GATHER,
+	TPK_HALO_CUBE_NORM,
+	TPK_HALO_CUBE_LIGHTCURVE,
 	TPK_COUNT
 };
 

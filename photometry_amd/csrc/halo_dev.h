@@ -1,4 +1,4 @@
-// halo_dev.h -- the parallel plumbing of Halo photometry's kernels (halo.hip, halo_stack.hip), once each: fixed-order reductions,
+// halo_dev.h -- the parallel plumbing of Halo photometry's kernels (halo.hip, halo_stack.hip, halo_cubes.hip), once each: fixed-order reductions,
 // the softmax, the ballot-ordered rank of a flag inside a block and the radix selection of a rank.  What they compute is decided in
 // halo_rules.h.  No float atomics: every reduction has a fixed order.  Also DevBlocks, the device blocks of one host entry.
 #pragma once
@@ -45,6 +45,44 @@ template <class Term> __device__ double wave_np_pairwise_sum(Term&& term, int n,
 		if (state[sp] == 0) {
 			if (len[sp] > 128 && sp < kLevels - 1) { state[sp] = 1; off[sp + 1] = off[sp]; len[sp + 1] = n2; state[sp + 1] = 0; ++sp; continue; }
 			ret = wave_np_pairwise_leaf(term, off[sp], len[sp], lane);
+		} else if (state[sp] == 1) {
+			left[sp] = ret; state[sp] = 2; off[sp + 1] = off[sp] + n2; len[sp + 1] = len[sp] - n2; state[sp + 1] = 0; ++sp; continue;
+		} else ret = left[sp] + ret;
+		if (sp == 0) break;
+		--sp;
+	}
+	return ret;
+}
+
+// The same sum by ONE lane (halo_cubes.hip: the lanes of a wavefront are cadences, each with a sum of its own over the stamp): the
+// leaf's eight running sums live in the lane's registers, the recursion is the same explicit stack (8 levels: 128 * 2^8 terms).
+// n is the same in every lane, so the control flow is uniform.
+template <class Term> __device__ double lane_np_pairwise_leaf(Term&& term, int off, int n) {
+	if (n < 8) { double r = 0.0; for (int i = 0; i < n; ++i) r += term(off + i); return r; }
+	double r[8];
+#pragma unroll
+	for (int j = 0; j < 8; ++j) r[j] = term(off + j);
+	int i = 8;
+	for (; i < n - (n % 8); i += 8) {
+#pragma unroll
+		for (int j = 0; j < 8; ++j) r[j] += term(off + i + j);
+	}
+	double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+	for (; i < n; ++i) res += term(off + i);
+	return res;
+}
+template <class Term> __device__ double lane_np_pairwise_sum(Term&& term, int n) {
+	constexpr int kLevels = 8;
+	int off[kLevels], len[kLevels], state[kLevels];
+	double left[kLevels];
+	int sp = 0;
+	off[0] = 0; len[0] = n; state[0] = 0;
+	double ret = 0.0;
+	while (true) {
+		int n2 = len[sp] / 2; n2 -= n2 % 8;
+		if (state[sp] == 0) {
+			if (len[sp] > 128 && sp < kLevels - 1) { state[sp] = 1; off[sp + 1] = off[sp]; len[sp + 1] = n2; state[sp + 1] = 0; ++sp; continue; }
+			ret = lane_np_pairwise_leaf(term, off[sp], len[sp]);
 		} else if (state[sp] == 1) {
 			left[sp] = ret; state[sp] = 2; off[sp + 1] = off[sp] + n2; len[sp + 1] = len[sp] - n2; state[sp + 1] = 0; ++sp; continue;
 		} else ret = left[sp] + ret;

@@ -1,4 +1,5 @@
-// halo_rules.h -- what Halo photometry decides (halo.hip: the TV-min solver; halo_stack.hip: the frames path), each rule stated once
+// halo_rules.h -- what Halo photometry decides (halo.hip: the TV-min solver; halo_stack.hip: the frames path; halo_cubes.hip: the
+// same for the time-fastest cubes of target pixel files), each rule stated once
 // over plain values: the order-preserving keys and the bookkeeping of a radix pass (select_rules.h), the pixel and cadence rules of the frames path,
 // the optimiser's state machine (line search, pair keeping, history slots, stopping tests, direction), and the host tables of the
 // entries with their argument checks.  No device code, no HIP runtime: the kernels call these from their parallel plumbing
@@ -401,6 +402,107 @@ inline const char* norm_table(const StackGeom& g, int32_t n_run, const int32_t* 
 		w_tot += h_npix[r];
 	}
 	return nullptr;
+}
+
+//--------------------------------------------------------------------------------------------------
+// host tables of the cubes path (tp_halo_select_cubes, tp_halo_gather_cubes, tp_halo_outputs_cubes): a group of target pixel files in
+// one time-fastest cube [n_targets][height * width][t_pitch].  Every target has its own segments: problem q = h_prob_off[i] + k is
+// segment k of target i, n_prob = h_prob_off[n_targets].
+//--------------------------------------------------------------------------------------------------
+struct CubeGeom {
+	int32_t n_targets, height, width, n_cad, t_pitch, n_prob;
+};
+// first element of the series of stamp pixel p of target i
+TP_RULE inline int64_t cube_offset(const CubeGeom& g, int i, int p) { return ((int64_t)i * (g.height * g.width) + p) * g.t_pitch; }
+// target of problem q (h_prob_off rises: the last i with h_prob_off[i] <= q)
+inline int32_t cube_target_of(const int32_t* h_prob_off, int32_t n_targets, int32_t q)
+{
+	return (int32_t)(std::upper_bound(h_prob_off, h_prob_off + n_targets + 1, q) - h_prob_off) - 1;
+}
+
+// the geometry and the problem offsets; sets g.n_prob
+inline const char* check_cube(CubeGeom& g, const void* d_cube, const int32_t* h_prob_off)
+{
+	g.n_prob = 0;
+	if (!(d_cube && h_prob_off)) return "tp_halo: null pointer";
+	if (!(g.n_targets >= 1 && g.n_targets <= 65535 && g.n_cad >= 1 && g.t_pitch >= g.n_cad)) return "tp_halo: bad cube or batch size";
+	if (!(g.height >= 1 && g.width >= 1 && (int64_t)g.height * g.width <= kMaxStamp)) return "tp_halo: a stamp holds 1 .. 4096 pixels";
+	if (h_prob_off[0] != 0) return "tp_halo: h_prob_off must start at 0";
+	for (int i = 0; i < g.n_targets; i++) {
+		const int64_t n_seg = (int64_t)h_prob_off[i + 1] - h_prob_off[i];
+		if (!(n_seg >= 1 && n_seg <= 64)) return "tp_halo: h_prob_off must rise by 1 .. 64 segments per target";
+	}
+	if (!(h_prob_off[g.n_targets] <= 65535)) return "tp_halo: at most 65535 problems per call";
+	g.n_prob = h_prob_off[g.n_targets];
+	return nullptr;
+}
+// h_seg [n_targets][n_cad]: -1 .. n_seg_i - 1 in row i
+inline const char* check_cube_seg(const CubeGeom& g, const int32_t* h_prob_off, const int32_t* h_seg)
+{
+	if (!h_seg) return "tp_halo: null pointer";
+	for (int i = 0; i < g.n_targets; i++) {
+		const int32_t n_seg = h_prob_off[i + 1] - h_prob_off[i];
+		const int32_t* s = h_seg + (int64_t)i * g.n_cad;
+		for (int t = 0; t < g.n_cad; t++)
+			if (!(s[t] >= -1 && s[t] < n_seg)) return "tp_halo: segment outside -1 .. n_seg - 1 of its target";
+	}
+	return nullptr;
+}
+
+// per target the cadences with a segment, sorted by (segment, cadence), in row i of cadlist [n_targets][n_cad] with their fit flags;
+// problem q owns the entries [lo[q], hi[q]) of its target's row; target[q] is that target
+struct CubeLists {
+	std::vector<int32_t> cadlist, lo, hi, target;
+	std::vector<uint8_t> fitlist;
+};
+inline CubeLists cube_lists(const CubeGeom& g, const int32_t* h_prob_off, const int32_t* h_seg, const int32_t* h_quality, int32_t bitmask)
+{
+	CubeLists s;
+	const int T = g.n_cad;
+	s.cadlist.assign((size_t)g.n_targets * T, 0);
+	s.fitlist.assign((size_t)g.n_targets * T, 0);
+	s.lo.assign(g.n_prob, 0);
+	s.hi.assign(g.n_prob, 0);
+	s.target.assign(g.n_prob, 0);
+	for (int i = 0; i < g.n_targets; i++) {
+		const int32_t q0 = h_prob_off[i], n_seg = h_prob_off[i + 1] - q0;
+		const int32_t* seg = h_seg + (int64_t)i * T;
+		const int32_t* quality = h_quality + (int64_t)i * T;
+		int32_t count[64] = {0};
+		for (int t = 0; t < T; t++)
+			if (seg[t] >= 0) count[seg[t]]++;
+		int32_t at = 0, next[64] = {0};
+		for (int k = 0; k < n_seg; k++) {
+			s.target[q0 + k] = i;
+			s.lo[q0 + k] = next[k] = at;
+			at += count[k];
+			s.hi[q0 + k] = at;
+		}
+		for (int t = 0; t < T; t++)
+			if (seg[t] >= 0) {
+				const int64_t j = (int64_t)i * T + next[seg[t]]++;
+				s.cadlist[j] = t;
+				s.fitlist[j] = (quality[t] & bitmask) == 0;
+			}
+	}
+	return s;
+}
+
+// the problems a gather / outputs call of the cubes path works on: the stack's tables over n_prob problems of n_cad cadences
+inline StackGeom cube_as_problems(const CubeGeom& g) { return StackGeom{g.n_cad, 1, 1, 0, 0, g.height, g.width, 1, g.n_prob}; }
+inline const char* check_cube_gather(const CubeGeom& g, int32_t n_run, const int32_t* h_index, const int64_t* h_p_offset, const int32_t* h_npix,
+	const int32_t* h_ncad, std::vector<GatherProb>& probs, int32_t& max_ncad, int32_t& max_pitch)
+{
+	const char* bad = gather_table(cube_as_problems(g), n_run, h_index, h_p_offset, h_npix, h_ncad, probs, max_ncad);
+	max_pitch = 0;
+	if (!bad)
+		for (const GatherProb& p : probs) max_pitch = std::max(max_pitch, p.pitch);
+	return bad ? "tp_halo_gather_cubes: problem index, npix, ncad or p_offset out of range" : nullptr;
+}
+inline const char* check_cube_norm(const CubeGeom& g, int32_t n_run, const int32_t* h_index, const int32_t* h_npix, const int32_t* h_ncad,
+	std::vector<NormProb>& probs, std::vector<int32_t>& run)
+{
+	return norm_table(cube_as_problems(g), n_run, h_index, h_npix, h_ncad, probs, run) ? "tp_halo_outputs_cubes: problem index, npix or ncad out of range" : nullptr;
 }
 
 } // namespace tp_halo

@@ -13,7 +13,9 @@ batched optimiser entry :func:`tvmin` (``tp_halo_tvmin``, csrc/halo.hip), :func:
 :func:`photometry`, the whole light-curve extraction of one target that ``plugins.HaloPhotometry`` calls, and
 :func:`photometry_frames`, the same for a batch of targets of a CCD region whose frames are resident on the device: the problems
 are built there from the stack (``tp_halo_select_stack``, ``tp_halo_gather_stack``), one ``tp_halo_tvmin`` call serves the batch and
-the outputs are formed there too (``tp_halo_outputs_stack``) -- no pixel value passes through the host.
+the outputs are formed there too (``tp_halo_outputs_stack``) -- no pixel value passes through the host.  :func:`photometry_cubes` is
+the same for a group of target pixel files whose time-fastest cubes are on the device, every target with its own time axis, flags and
+segments (``tp_halo_select_cubes``, ``tp_halo_gather_cubes``, ``tp_halo_outputs_cubes``; csrc/halo_cubes.hip).
 """
 
 import ctypes
@@ -472,4 +474,171 @@ def photometry_frames(ctx, stack, targets, time, quality, sector=None, timecorr=
 			for j, i in enumerate(sub):
 				out['pixel_mask'][i] = masks[a + j]
 			_frames_chunk(ctx, stack, stamps[sub], masks[a:a + per], seg, quality, normfactor[sub], maxiter, out, sub)
+	return out
+
+
+# -- the batched path for target pixel files: problems built on the device from a group's time-fastest cubes ------------------------
+def _cubes_chunk(ctx, images, images_err, a, b, chosen, masks, segs, quality, normfactor, maxiter, out, minflux=SETTINGS['minflux'], bitmask=None):
+	"""select -> counts -> gather -> ONE tp_halo_tvmin -> outputs -> download for the slots ``chosen`` of a group's cubes.  The call
+	covers the slots ``[a, b)``; a slot in between that was not chosen travels as one problem without mask pixel or cadence."""
+	from .device import device_view
+	from .engine import TESS_DEFAULT_BITMASK
+	m, T, H, W = b - a, images.n_cad, images.height, images.width
+	HW = H * W
+	seg = np.full((m, T), -1, dtype='int32')
+	mask = np.zeros((m, HW), dtype='uint8')
+	qual = np.zeros((m, T), dtype='int32')
+	n_seg = np.ones(m, dtype='int32')
+	for i in chosen:
+		k = int(segs[i].max()) + 1 if len(segs[i]) and segs[i].max() >= 0 else 0
+		if k < 1:
+			continue                                                       # no cadence with a finite time: no problem, not usable
+		seg[i - a], qual[i - a], n_seg[i - a] = segs[i], quality[i], k
+		mask[i - a] = np.asarray(masks[i], dtype='uint8').ravel()
+	prob_off = np.concatenate([[0], np.cumsum(n_seg)]).astype('int32')
+	n_prob = int(prob_off[-1])
+	cube, cube_err = images.slice0(a, m), images_err.slice0(a, m)
+	geometry = (m, H, W, T, cube.t_pitch)
+	d_mask = ctx.array(mask)
+	pix, cad, fit = ctx.empty((n_prob, HW), 'int32'), ctx.empty((n_prob, T), 'int32'), ctx.empty((n_prob, T), 'uint8')
+	cadpos = ctx.empty((m, T), 'int32')
+	counts = ctx.empty((2, n_prob), 'int32')
+	ctx._check(ctx.lib.tp_halo_select_cubes(ctx.handle, cube.ptr, *geometry, d_mask.ptr, _host_ptr(prob_off), _host_ptr(seg), _host_ptr(qual),
+		int(TESS_DEFAULT_BITMASK if bitmask is None else bitmask), float(minflux), pix.ptr, cad.ptr, fit.ptr, cadpos.ptr, counts.ptr, counts.ptr + 4 * n_prob))
+	c = counts.to_host()
+	npix, ncad = c[0], c[1]
+	counts.free()
+	d_mask.free()
+	usable = np.zeros(m, dtype=bool)
+	for i in chosen:
+		q0, q1 = prob_off[i - a], prob_off[i - a + 1]
+		usable[i - a] = bool(np.any(seg[i - a] >= 0)) and bool(np.all((npix[q0:q1] >= 1) & (npix[q0:q1] <= MAX_PIXELS)))
+	index = np.ascontiguousarray(np.flatnonzero(np.repeat(usable, n_seg)), dtype='int32')
+	run_npix, run_ncad = np.ascontiguousarray(npix[index], dtype='int32'), np.ascontiguousarray(ncad[index], dtype='int32')
+	sizes = (run_npix.astype('int64') + 3) // 4 * 4 * run_ncad
+	offset = np.zeros(len(index), dtype='int64')
+	offset[1:] = np.cumsum(sizes)[:-1]
+	n_run, n_w, n_c = len(index), int(run_npix.sum()), int(run_ncad.sum())
+	P = ctx.empty((max(int(sizes.sum()), 4),), 'float32')
+	fitc = ctx.empty((max(n_c, 1),), 'uint8')
+	ctx._check(ctx.lib.tp_halo_gather_cubes(ctx.handle, cube.ptr, *geometry, _host_ptr(prob_off), pix.ptr, cad.ptr, fit.ptr, n_run, _host_ptr(index),
+		_host_ptr(offset), _host_ptr(run_npix), _host_ptr(run_ncad), P.ptr, fitc.ptr))
+	# one block of float64 for everything that goes back: w, f, median, corr_flux, flux, flux_err, the weight maps
+	parts = (n_w, n_run, n_prob, m * T, m * T, m * T, n_prob * HW)
+	starts = np.concatenate([[0], np.cumsum(parts)])
+	block = ctx.empty((max(int(starts[-1]), 1),), 'float64')
+	d_w, d_f, d_med, d_corr, d_flux, d_err, d_wm = (device_view(ctx, block.ptr + 8 * int(s), (max(int(k), 1),), 'float64', base=block)
+		for s, k in zip(starts[:-1], parts))
+	d_l = ctx.empty((max(n_c, 1),), 'float64')
+	d_is = ctx.empty((2, max(n_run, 1)), 'int32')
+	if n_run:
+		ctx._check(ctx.lib.tp_halo_tvmin(ctx.handle, n_run, _host_ptr(offset), _host_ptr(run_npix), _host_ptr(run_ncad), P.ptr, fitc.ptr, int(maxiter),
+			int(HISTORY), float(FTOL), float(GTOL), d_w.ptr, d_l.ptr, d_f.ptr, d_is.ptr, d_is.ptr + 4 * n_run))
+	nf = np.ascontiguousarray(normfactor[a:b], dtype='float64')
+	ctx._check(ctx.lib.tp_halo_outputs_cubes(ctx.handle, cube_err.ptr, *geometry, _host_ptr(prob_off), _host_ptr(seg), pix.ptr, cadpos.ptr, n_run,
+		_host_ptr(index), _host_ptr(run_npix), _host_ptr(run_ncad), fitc.ptr, d_w.ptr, d_l.ptr, d_is.ptr + 4 * n_run, _host_ptr(nf), d_med.ptr, d_corr.ptr,
+		d_flux.ptr, d_err.ptr, d_wm.ptr))
+	host, ints = block.to_host(), d_is.to_host()
+	w, f, med, corr, flux, err, wm = (host[int(s):int(s) + int(k)] for s, k in zip(starts[:-1], parts))
+	corr, flux, err, wm = corr.reshape(m, T), flux.reshape(m, T), err.reshape(m, T), wm.reshape(n_prob, H, W)
+	wo = np.concatenate([[0], np.cumsum(run_npix)])
+	run_of = np.full(n_prob, -1, dtype='int64')
+	run_of[index] = np.arange(n_run)
+	for i in chosen:
+		j = i - a
+		q0, q1 = int(prob_off[j]), int(prob_off[j + 1])
+		if not np.any(seg[j] >= 0):
+			continue
+		out['corr_flux'][i], out['flux'][i], out['flux_err'][i] = corr[j], flux[j], err[j]
+		out['npix'][i], out['ncad'][i], out['usable'][i] = npix[q0:q1].copy(), ncad[q0:q1].copy(), usable[j]
+		out['median'][i] = med[q0:q1].copy()
+		if not usable[j]:
+			continue
+		r = int(run_of[q0])
+		k = q1 - q0
+		out['weightmap'][i] = [np.array(wm[q]) for q in range(q0, q1)]
+		out['w'][i] = [np.array(w[wo[r + s]:wo[r + s + 1]]) for s in range(k)]
+		out['f'][i], out['iterations'][i], out['status'][i] = f[r:r + k].copy(), ints[0, r:r + k].copy(), ints[1, r:r + k].copy()
+	for arr in (block, d_l, d_is, P, fitc, pix, cad, fit, cadpos):
+		arr.free()
+
+
+def photometry_cubes(ctx, group_cubes, masks, time, timecorr, cadenceno, quality, sector, normfactor, maxiter=SETTINGS['maxiter'],
+	budget_bytes=None, targets=None):
+	"""
+	:func:`photometry` for the targets of a group of target pixel files whose cubes are resident on the device (``tpf.TpfGroup.cubes``:
+	``images`` and ``images_err``, :class:`~photometry_amd.device.DeviceCube` s of ``n`` targets with one stamp shape and one number of
+	cadences ``T``), without a host copy of any pixel: the analogue of :func:`photometry_frames`.  ``masks``: bool ``(n, H, W)`` pixel
+	masks; ``time`` / ``timecorr`` / ``cadenceno`` / ``quality``: ``(n, T)``, one row per target -- the files share a shape, not their
+	time axes, flags or gaps, so the split times and segments are every target's own (:func:`split_times`, :func:`segments`) and a
+	batch mixes targets with one, two or more segments; ``sector`` / ``normfactor``: ``(n,)``.  ``targets``: the slots to run (default:
+	all).  Per chunk select -> counts -> gather -> one ``tp_halo_tvmin`` for every usable problem -> outputs -> one download
+	(``tp_halo_select_cubes``, ``tp_halo_gather_cubes``, ``tp_halo_outputs_cubes``).  A batch whose ``P`` could exceed ``budget_bytes``
+	(default: a quarter of the device's memory) runs in chunks of targets; a target's result is independent of the chunking, to the bit.
+
+	Returns a dict of columns over the ``n`` slots (``None`` / NaN for a slot that was not run): ``usable`` (every segment has 1 .. 4096
+	pixels), ``corr_flux`` / ``flux`` / ``flux_err`` float64 ``(n, T)``, and per target ``weightmap`` and ``w`` (one entry per segment),
+	``f`` / ``iterations`` / ``status`` / ``npix`` / ``ncad`` / ``median`` (arrays over its segments; ``median``: numpy's median of the
+	segment's light curve over its fitted cadences, NaN for a target that is not usable), ``messages`` (what :func:`split_times` logged
+	at WARNING level for the target, as ``"LEVEL: message"``: the plugin keeps these in its details), ``initial_cadence`` / ``final_cadence``,
+	``split_times``, ``segments``.
+	"""
+	images, images_err = group_cubes['images'], group_cubes['images_err']
+	n, T, H, W = images.n_targets, images.n_cad, images.height, images.width
+	if (images_err.n_targets, images_err.n_cad, images_err.height, images_err.width, images_err.t_pitch) != (n, T, H, W, images.t_pitch):
+		raise ValueError("photometry_cubes: images and images_err must have one shape and pitch")
+	if H * W > MAX_PIXELS:
+		raise ValueError(f"every Halo problem needs 1 .. {MAX_PIXELS} pixels")
+	time = np.asarray(time, dtype='float64').reshape(n, T)
+	timecorr = np.asarray(timecorr, dtype='float64').reshape(n, T)
+	cadenceno = np.asarray(cadenceno).reshape(n, T)
+	quality = np.ascontiguousarray(quality, dtype='int32').reshape(n, T)
+	masks = np.asarray(masks).reshape(n, H, W)
+	sector = np.broadcast_to(np.asarray(sector), (n,))
+	normfactor = np.ascontiguousarray(np.broadcast_to(np.asarray(normfactor, dtype='float64'), (n,)))
+	chosen = np.arange(n) if targets is None else np.unique(np.asarray(targets, dtype='int64'))
+	if len(chosen) and (chosen[0] < 0 or chosen[-1] >= n):
+		raise IndexError("photometry_cubes: target outside the cubes")
+	none = lambda: [None] * n
+	out = {'usable': np.zeros(n, dtype=bool), 'corr_flux': np.full((n, T), np.nan), 'flux': np.full((n, T), np.nan), 'flux_err': np.zeros((n, T)),
+		'weightmap': none(), 'w': none(), 'f': none(), 'iterations': none(), 'status': none(), 'npix': none(), 'ncad': none(), 'median': none(), 'messages': none(), 'split_times': none(),
+		'segments': none(), 'initial_cadence': none(), 'final_cadence': none()}
+	bound = {}
+	from .plugins import _DetailLog
+	for i in chosen:
+		# (what split_times warns about goes into the target's messages, as the plugin's log handler keeps it)
+		out['messages'][i] = []
+		handler = _DetailLog(out['messages'][i])
+		logger.addHandler(handler)
+		try:
+			splits = split_times(sector[i], time[i], timecorr[i])
+		finally:
+			logger.removeHandler(handler)
+		seg = segments(time[i], splits)
+		k = int(seg.max()) + 1 if len(seg) and seg.max() >= 0 else 0
+		out['split_times'][i], out['segments'][i] = splits, seg
+		# (a segment may hold no cadence: 0 then, as halo.photometry writes it)
+		out['initial_cadence'][i] = [int(cadenceno[i][seg == s].min()) if np.any(seg == s) else 0 for s in range(k)]
+		out['final_cadence'][i] = [int(cadenceno[i][seg == s].max()) if np.any(seg == s) else 0 for s in range(k)]
+		out['npix'][i], out['ncad'][i], out['median'][i] = np.zeros(k, dtype='int32'), np.zeros(k, dtype='int32'), np.full(k, np.nan)
+		out['f'][i], out['iterations'][i], out['status'][i] = np.full(k, np.nan), np.zeros(k, dtype='int32'), np.zeros(k, dtype='int32')
+		if k > 64:
+			raise ValueError("Halo photometry: more than 64 segments")
+		# the most P the target can need (every cadence with a segment, every stamp pixel) and its problems
+		bound[int(i)] = (4.0 * ((H * W + 3) // 4 * 4) * int(np.count_nonzero(seg >= 0)), max(k, 1))
+	if budget_bytes is None:
+		budget_bytes = ctx.info()['hbm_bytes'] / 4.0
+	# chunks of chosen slots in rising order: P within the budget, at most 65535 problems with the slots in between
+	a = 0
+	while a < len(chosen):
+		b, nbytes, probs = a, 0.0, 0
+		while b < len(chosen):
+			more = bound[int(chosen[b])]
+			between = int(chosen[b] - chosen[b - 1] - 1) if b > a else 0
+			if b > a and (nbytes + more[0] > budget_bytes or probs + between + more[1] > 65535):
+				break
+			nbytes, probs, b = nbytes + more[0], probs + between + more[1], b + 1
+		sub = [int(i) for i in chosen[a:b]]
+		_cubes_chunk(ctx, images, images_err, sub[0], sub[-1] + 1, sub, masks, out['segments'], quality, normfactor, maxiter, out)
+		a = b
 	return out

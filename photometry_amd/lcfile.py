@@ -667,7 +667,8 @@ def save_tpf_lightcurves(results, output_folder, version, workers=None, compress
 	:class:`FileInfo` of its own, from its headers as :meth:`FileInfo.from_source` takes it from the ``TpfStampSource``; ``TIME`` ..
 	``PIXEL_QUALITY`` and ``POS_CORR1/2`` are the file's columns, ``QUALITY`` is all zero (a target pixel file brings no pixel flags),
 	the ``APERTURE`` image is the file's without SPOC's mask and centroid flags plus this run's, the image cards are the stamp's
-	limits.  Threads, ``compresslevel``, ``timings`` (``build`` / ``gzip``), ``compress`` and the return value as :func:`save_lightcurves`;
+	limits.  A target done with Halo photometry (``tessphot_tpfs(method=None)`` or ``'halo'``) gets the file of the per-file Halo run: the
+	``HALO_*`` cards in place of the K2P2 ones, the Halo mask without a position mask and the ``WEIGHTMAP`` extension.  Threads, ``compresslevel``, ``timings`` (``build`` / ``gzip``), ``compress`` and the return value as :func:`save_lightcurves`;
 	``compress='device'`` runs on ``ctx`` (default: the context the results were computed on), whose owner the calling thread must be.
 	``table='device'`` (with ``compress='device'``) as in :func:`save_lightcurves`; here every file has its own ``time`` .. ``PIXEL_QUALITY``,
 	so the vectors are strided per target and there is one ``tp_lc_table_pack`` per set of files with one length and one list of kept rows.
@@ -695,25 +696,29 @@ def save_tpf_lightcurves(results, output_folder, version, workers=None, compress
 		header = dict(ld.header)
 		header['TIME_OFFSET_CORRECTED'] = bool(ld.time_offset_corrected)
 		info = FileInfo(ld.sector, ld.camera, ld.ccd, cadence=ld.cadence, n_readout=ld.n_readout, num_frm=ld.num_frm or 60, header=header)   # (60: BasePhotometry.py:372)
-		headers = dict(k2p2_headers)
-		if 'contamination' in r._details:
-			headers['AP_CONT'] = (r._details['contamination'], 'AP contamination')
+		if r.method == 'halo':
+			headers = dict(results.halo.headers)
+		else:
+			headers = dict(k2p2_headers)
+			if 'contamination' in r._details:
+				headers['AP_CONT'] = (r._details['contamination'], 'AP contamination')
 		stamp = tuple(int(v) for v in ld.max_stamp)
 		T = len(r.lightcurve['time'])
-		aperture = aperture_with_masks(results.aperture_image(i), r.final_phot_mask, r.final_phot_mask)
+		# (the aperture plugin positions on its photometry mask; the Halo plugin has no position mask)
+		aperture = aperture_with_masks(results.aperture_image(i), r.final_phot_mask, None if r.method == 'halo' else r.final_phot_mask)
 		ta = _clock.perf_counter()
 		args = ({'tmag': float(results.tmag[i])}, int(results.starid[i]), info.sector, info.camera, info.ccd, info.cadence, info.data_rel, version, r.method,
 			info.ticver, info.header, info.num_frm, info.n_readout, headers)
 		path = os.path.join(output_folder, lightcurve_filename(results.starid[i], info.sector, info.camera, info.ccd, info.cadence, info.data_rel, version))
 		if table == 'device':
 			lc = r.lightcurve
-			pieces = lightcurve_pieces(*args, lc['time'], results.sumimage(i), aperture, image_cards(stamp))
+			pieces = lightcurve_pieces(*args, lc['time'], results.sumimage(i), aperture, image_cards(stamp), weightmap=r.halo_weightmap)
 			spent_here = _clock.perf_counter() - ta
 			centroid = np.asarray(lc['pos_centroid'])
 			source = {'time': lc['time'], 'timecorr': lc['timecorr'], 'cadenceno': lc['cadenceno'], 'pixel_quality': lc['quality'],
 				'lc': (lc['flux'], lc['flux_err'], lc['flux_background'], centroid[:, 0], centroid[:, 1]), 'quality': None, 'pos_corr': lc['pos_corr']}
 			return path, pieces, source, spent_here
-		hdus = lightcurve_hdus(*args, r.lightcurve, np.zeros(T, dtype='int32'), results.sumimage(i), aperture, image_cards(stamp))
+		hdus = lightcurve_hdus(*args, r.lightcurve, np.zeros(T, dtype='int32'), results.sumimage(i), aperture, image_cards(stamp), weightmap=r.halo_weightmap)
 		return path, hdus, _clock.perf_counter() - ta
 
 	spent = {'build': 0.0, 'gzip': 0.0}

@@ -1298,3 +1298,128 @@ def halo_frames(ctx, stack, targets, catalog, time, quality, sector=None, timeco
 		d_time.free()
 		d_q.free()
 	return out
+
+
+class HaloResultsOfGroups(object):
+	"""The :class:`HaloFramesResult` s of several groups of target pixel files (:func:`halo_tpfs`; the groups differ in stamp shape or
+	number of cadences) as one result: row ``r`` is row ``places[r][1]`` of ``parts[places[r][0]]``.  What ``BatchResults.switch_to_halo``
+	and the light-curve writer read: ``status``, ``stamp``, ``diagnostics``, ``headers``, ``result[r]``."""
+	def __init__(self, parts, places):
+		self.parts, self.places = list(parts), [(int(g), int(j)) for g, j in places]
+		self.n = len(self.places)
+		self.status = np.array([self.parts[g].status[j] for g, j in self.places], dtype='int32')
+		self.stamp = np.array([self.parts[g].stamp[j] for g, j in self.places], dtype='int64').reshape(self.n, 4)
+		self.diagnostics = [self.parts[g].diagnostics[j] for g, j in self.places]
+		self.headers = self.parts[0].headers if self.parts else {}
+
+	def __len__(self):
+		return self.n
+
+	def __getitem__(self, r):
+		g, j = self.places[int(r)]
+		return self.parts[g][j]
+
+	def __iter__(self):
+		return (self[r] for r in range(self.n))
+
+
+def _halo_headers():
+	from . import halo
+	return {'HALO_VER': (halo.VERSION, 'Version of halo photometry'), 'HALO_OBJ': (halo.SETTINGS['objective'], 'Halophot objective function'),
+		'HALO_THR': (halo.SETTINGS['thresh'], 'Halophot saturated pixel threshold'), 'HALO_MXI': (halo.SETTINGS['maxiter'], 'Halophot maximum optimisation iterations'),
+		'HALO_SCL': (halo.SETTINGS['sigclip'], 'Halophot sigma clipping enabled'), 'HALO_MFL': (halo.SETTINGS['minflux'], 'Halophot minimum flux')}
+
+
+def halo_tpfs(ctx, group, idx, catalogs, positions, starid=None, sumimage=None, settings=None, budget_bytes=None):
+	"""
+	``HaloPhotometry.do_photometry`` for the slots ``idx`` of a ``tpf.TpfGroup`` whose cubes are resident on the device --
+	``tessphot('halo', starid, TpfStampSource(...), datasource='tpf')`` for many files of one shape: the problems of all chosen targets
+	built on the device from the group's cubes, ONE ``tp_halo_tvmin`` call per chunk, light curves, flux errors and weight maps formed
+	there too (``halo.photometry_cubes``).  The stamp is the file's ``max_stamp`` (the plugin resizes for ``'ffi'`` only), the pixel mask
+	``halo.pixel_mask`` of the file's aperture image, ``pos_centroid`` the target position plus the file's ``pos_corr``; split times and
+	segments are every file's own.  ``catalogs``: per chosen slot the stars of its stamp (``starid, row, column``); ``positions``:
+	``(len(idx), 3)`` row, column and Tmag of the main targets; ``starid``: their star numbers (``skip_targets`` lists the others in
+	the mask); ``sumimage``: ``(len(idx), H, W)`` the sum images of the chosen slots (the group's aperture pass has them) for the
+	light-curve diagnostics, which run with every target's own time row (``tp_lightcurve_diagnostics_times``).  Status and messages are
+	the plugin's: ERROR "Halo optimization failed", ERROR "no usable pixels in the pixel mask".  Raises ``NotImplementedError`` while
+	``[halo] enabled`` is off.  Returns a :class:`HaloFramesResult` over ``idx`` (``f`` / ``iterations`` / ``tv_status`` /
+	``split_times`` / ``segments``: one entry per target).
+	"""
+	from . import halo
+	from .plugins import load_settings, mag2flux
+	settings = load_settings() if settings is None else settings
+	if not halo.enabled(settings):
+		raise NotImplementedError("HaloPhotometry is off: set '[halo] enabled = true' in the settings file named by "
+			"TESSPHOT_SETTINGS to run this engine's TV-min implementation")
+	idx = [int(s) for s in idx]
+	n, m = len(group), len(idx)
+	H, W, T = group.shape
+	positions = np.asarray(positions, dtype='float64').reshape(m, 3)
+	starid = [None] * m if starid is None else [int(s) for s in starid]
+	masks = np.zeros((n, H, W), dtype=bool)
+	normfactor = np.ones(n)
+	grids = []
+	for j, s in enumerate(idx):
+		st = group.loaded[s].max_stamp
+		cols, rows = np.meshgrid(np.arange(st[2] + 1, st[3] + 1, 1, dtype='int32'), np.arange(st[0] + 1, st[1] + 1, 1, dtype='int32'))
+		grids.append((cols, rows))
+		masks[s] = halo.pixel_mask(group.aperture[s], cols, rows, positions[j, 0], positions[j, 1])
+		normfactor[s] = mag2flux(float(positions[j, 2]))                    # (one scalar call per target, as the plugin makes it)
+	timecorr = np.stack([np.asarray(ld.timecorr, dtype='float64') for ld in group.loaded])
+	cadenceno = np.stack([np.asarray(ld.cadenceno) for ld in group.loaded])
+	sector = np.array([-1 if ld.sector is None else int(ld.sector) for ld in group.loaded])
+	res = halo.photometry_cubes(ctx, group.cubes, masks, group.time, timecorr, cadenceno, group.quality, sector, normfactor,
+		budget_bytes=budget_bytes, targets=idx)
+	out = HaloFramesResult(m, T)
+	out.headers = _halo_headers()
+	out.f, out.iterations, out.tv_status = ([res[k][s] for s in idx] for k in ('f', 'iterations', 'status'))
+	out.split_times, out.segments = [res['split_times'][s] for s in idx], [res['segments'][s] for s in idx]
+	for j, s in enumerate(idx):
+		ld = group.loaded[s]
+		out.stamp[j] = ld.max_stamp
+		out.corr_flux[j], out.flux_err[j] = res['corr_flux'][s], res['flux_err'][s]
+		out.pixel_mask[j], out.w[j] = masks[s], res['w'][s]
+		messages = list(res['messages'][s])                                 # (the warnings of the split times: the plugin's log keeps them)
+		if not res['usable'][s]:
+			out.status[j] = STATUS.ERROR.value
+			out.errors[j] = messages + ['ValueError: Halo photometry: no usable pixels in the pixel mask']
+		elif np.any(res['status'][s] == halo.DEGENERATE):
+			out.status[j] = STATUS.ERROR.value
+			out.errors[j] = messages + ['ERROR: Halo optimization failed']
+		else:
+			out.status[j] = STATUS.OK.value
+			if messages:
+				out.errors[j] = messages
+			good = np.isfinite(group.time[s])
+			out.flux[j, good] = res['flux'][s][good]
+			# the target position per cadence; no centroids are calculated (:162-164, :221-222)
+			jit = np.asarray(ld.pos_corr, dtype='float64')
+			out.pos_centroid[j, :, 0] = positions[j, 1] + jit[:, 0]
+			out.pos_centroid[j, :, 1] = positions[j, 0] + jit[:, 1]
+			k = len(res['status'][s])
+			out.weightmap[j] = {'weightmap': res['weightmap'][s], 'initial_cadence': list(res['initial_cadence'][s]),
+				'final_cadence': list(res['final_cadence'][s]), 'sat_pixels': [0] * k}
+			# other targets in the mask (:257-262)
+			cat, (cc, rr) = catalogs[j], grids[j]
+			out.skip_targets[j] = [int(sid) for sid, r, c in zip(cat['starid'], cat['row'], cat['column'])
+				if sid != starid[j] and np.any(masks[s] & (rr == np.round(r) + 1) & (cc == np.round(c) + 1))]
+	# the light-curve diagnostics of the OK targets (BasePhotometry.py:1343-1407), every target on its own time axis: one device call
+	ok = np.flatnonzero(out.status == STATUS.OK.value)
+	if len(ok):
+		slots = [idx[j] for j in ok]
+		block = np.zeros((5, len(ok), T))
+		block[0], block[1] = out.flux[ok], out.flux_err[ok]
+		block[3], block[4] = out.pos_centroid[ok, :, 0], out.pos_centroid[ok, :, 1]
+		sums = np.full((len(ok), H, W), np.nan) if sumimage is None else np.ascontiguousarray(np.asarray(sumimage, dtype='float64').reshape(m, H, W)[ok])
+		d_time, d_q = ctx.array(np.ascontiguousarray(group.time[slots])), ctx.array(np.ascontiguousarray(group.quality[slots], dtype='int32'))
+		d_sum, d_mask = ctx.array(sums), ctx.array(np.stack([out.pixel_mask[j] for j in ok]).astype('uint8'))
+		d_status = ctx.array(np.full(len(ok), STATUS.OK.value, dtype='int32'))
+		d_block = ctx.array(block)
+		lc = engine.LightCurves(ctx, len(ok), T, block=d_block)
+		diag = engine.lightcurve_diagnostics(ctx, lc, d_time, d_q, status=d_status, sumimage=d_sum, mask=d_mask)
+		host = diag.to_host()
+		for r, j in enumerate(ok):
+			out.diagnostics[j] = dict(zip(engine.DIAGNOSTICS_COLUMNS, host[r]))
+		for a in (diag, d_block, d_status, d_mask, d_sum, d_time, d_q):
+			a.free()
+	return out

@@ -14,7 +14,8 @@ call sites run_tessphot.py:153, run_tessphot_mpi.py:178) with the contract they 
 
 ``tessphot_batch`` / ``tessphot_frames`` are the throughput entries (not in the reference): a whole batch per device pass.
 ``tessphot_tpfs`` is the one for target pixel files: ``tessphot('aperture', ..., datasource='tpf')`` for many files, one pass per group
-of files that share stamp shape and number of cadences.
+of files that share stamp shape and number of cadences; with ``method=None`` or ``'halo'`` it is ``tessphot(None, ...)`` /
+``tessphot('halo', ...)`` for them, the Halo problems built on the device from the group's cubes (``pipeline.halo_tpfs``).
 """
 
 import logging
@@ -202,6 +203,7 @@ class BatchResults(object):
 		self.status = status
 		#: targets redone with Halo photometry (:meth:`switch_to_halo`): target -> row of ``self.halo``
 		self.halo, self.halo_rows, self._stamp = None, {}, None
+		self._halo_direct = False
 		#: ``(N, T, 2)`` changes in column and row of every target's position (``lightcurve['pos_corr']``, BasePhotometry.py:473) when
 		#: the entry was given movement kernels, else None
 		self.pos_corr = None
@@ -295,10 +297,15 @@ class BatchResults(object):
 			status = _diagnostics_into(details, r['diagnostics'], status)
 			details['mask_size'] = int(mask.sum())
 			errors += details.pop('errors', [])
-		# the diagnostics that led to the switch are kept (tessphot.py:104-109)
-		details['errors'] = errors + ['Automatically switched to Halo photometry']
-		ef = self._aperture_edge_flux[i]
-		details['edge_flux'] = None if np.isnan(ef) else float(ef)
+		if self._halo_direct:
+			# Halo photometry was asked for (``method='halo'``): nothing was switched, the details are the Halo run's alone
+			if errors:
+				details['errors'] = errors
+		else:
+			# the diagnostics that led to the switch are kept (tessphot.py:104-109)
+			details['errors'] = errors + ['Automatically switched to Halo photometry']
+			ef = self._aperture_edge_flux[i]
+			details['edge_flux'] = None if np.isnan(ef) else float(ef)
 		if i in self._filepath_rel:
 			details['filepath_lightcurve'] = self._filepath_rel[i]
 		out = BatchResult(int(self.starid[i]), status, 'halo', details, lc, mask)
@@ -497,7 +504,9 @@ class TpfBatchResults(BatchResults):
 	What :func:`tessphot_tpfs` yields per chunk: :class:`BatchResults` over target pixel files.  ``starid``, ``status``, ``paths`` (the
 	input files) and ``filepaths`` (the light-curve files, ``None`` where none was written or asked for) are in input order;
 	``column(name)`` as there; ``results[i]`` is the :class:`BatchResult` the per-file call ``tessphot('aperture', starid,
-	TpfStampSource(...), datasource='tpf')`` returns: its light curve carries ``time, timecorr, cadenceno, quality`` and ``pos_corr``
+	TpfStampSource(...), datasource='tpf')`` returns (with ``method=None`` / ``'halo'`` of the entry: what ``tessphot(None, ...)`` /
+	``tessphot('halo', ...)`` returns; ``halo_rows``, ``halo`` and ``halo_requests`` say which targets were switched, to what, or would have
+	been with Halo photometry on): its light curve carries ``time, timecorr, cadenceno, quality`` and ``pos_corr``
 	(``POS_CORR1/2``) of the file besides the photometry.  ``stamp_resizes`` is 0 throughout (a ``tpf`` stamp is the whole file) and is
 	kept in the details, as on :class:`BatchResults`; where the diagnostics raise upstream the details carry that error alone, as the
 	plugin's do.  ``loaded``: the ``tpf.LoadedTPF`` of every file (its cubes are gone once the chunk has been yielded).
@@ -513,6 +522,16 @@ class TpfBatchResults(BatchResults):
 		self.filepaths = [None] * len(self.paths)
 		#: the context the chunk was computed on (set by :func:`tessphot_tpfs`): where ``compress='device'`` runs
 		self.ctx = None
+		#: ``method=None`` with Halo photometry off: target -> the recorded request (:meth:`keep_aperture_results`)
+		self.halo_requests = {}
+
+	def keep_aperture_results(self, idx, codes):
+		"""The targets ``idx`` should have gone to Halo photometry (reasons ``codes``) but it is off: the aperture results are kept, the
+		request is recorded in their errors and OK becomes WARNING -- what ``tessphot(None, ...)`` does before it saves the light curve."""
+		for i, code in zip(idx, codes):
+			self.halo_requests[int(i)] = 'Halo switch requested (' + _SWITCH_TEXT[int(code)] + ') but Halo photometry is not available: aperture result kept'
+			if self.status[i] == STATUS.OK.value:
+				self.status[i] = STATUS.WARNING.value
 
 	def save_lightcurves(self, output_folder, version, workers=None, compresslevel=9, compress='zlib', table='host'):
 		"""Write the light-curve file of every OK / WARNING target as the per-file plugin call does (``lcfile.save_tpf_lightcurves``);
@@ -532,8 +551,12 @@ class TpfBatchResults(BatchResults):
 	def __getitem__(self, i):
 		i = int(i) + len(self) if int(i) < 0 else int(i)
 		out = super().__getitem__(i)
-		if (self._problems[i] & 7) and 'errors' in out._details:
+		if i not in self.halo_rows and (self._problems[i] & 7) and 'errors' in out._details:
 			out._details['errors'] = out._details['errors'][-1:]       # (the plugin raises: what it had logged is lost, BasePhotometry.py:1346-1349)
+		if i in self.halo_requests:
+			# Halo photometry off: the aperture result is kept and the request recorded, as tessphot(None, ...) does before it saves
+			out._details.setdefault('errors', []).append(self.halo_requests[i])
+			out.status = STATUS(int(self.status[i]))
 		if out.lightcurve is not None:
 			ld = self.loaded[i]
 			lc = {'time': np.array(ld.time, dtype='float64'), 'timecorr': np.array(ld.timecorr, dtype='float64'), 'cadenceno': np.array(ld.cadenceno),
@@ -569,8 +592,8 @@ def _one_attempt(flags):
 	return (STATUS.WARNING if flags & 1 else status), True, messages
 
 
-def _tpf_chunk(ctx, files, headers, starid, catalog, targets, verify):
-	"""One chunk of :func:`tessphot_tpfs`: load, one device pass per ``(H, W, T)`` group, the results in input order."""
+def _tpf_chunk(ctx, files, headers, starid, catalog, targets, verify, method='aperture', settings=None):
+	"""One chunk of :func:`tessphot_tpfs`: load, one device pass per ``(H, W, T)`` group, the method switch, the results in input order."""
 	from . import tpf, pipeline
 	n = len(files)
 	groups, index = tpf.load_tpf_groups(ctx, files, verify=verify, headers=headers)
@@ -639,19 +662,65 @@ def _tpf_chunk(ctx, files, headers, starid, catalog, targets, verify):
 					fr.errors[i] = messages
 				if int(res['flags'][s]) >> 8 == 6:
 					res['contamination'][s] = np.nan                    # photometry.py:243-246
+		out = TpfBatchResults(fr, starid, pos[:, 2], files, loaded, apertures)
+		if method != 'aperture':
+			_halo_switch_tpfs(ctx, out, groups, by_slot, cats, pos, lost, method, settings)   # (while the cubes are resident)
 	finally:
 		for grp in groups:
 			grp.free()
-	return TpfBatchResults(fr, starid, pos[:, 2], files, loaded, apertures)
+	return out
+
+
+def _halo_switch_tpfs(ctx, out, groups, by_slot, cats, pos, lost, method, settings):
+	"""The method switch of ``tessphot(None, ...)`` (tessphot.py:76-109) for a chunk of target pixel files after its aperture passes, or
+	``tessphot('halo', ...)`` for every file (``method='halo'``): the chosen files of every group go through ``pipeline.halo_tpfs`` while
+	the group's cubes are on the device.  With Halo photometry off a switch is recorded and the aperture result kept."""
+	from . import pipeline, halo
+	logger = logging.getLogger(__name__)
+	if method == 'halo':
+		idx = np.array([i for i in range(len(out)) if i not in lost], dtype='int64')
+		out._halo_direct = True
+	else:
+		idx, codes = out.halo_switch(out.tmag, settings, datasource='tpf')
+		for code in codes:
+			logger.warning(_SWITCH_TEXT[int(code)])
+		if len(idx) and not halo.enabled(settings):
+			out.keep_aperture_results(idx, codes)
+			return
+	if len(idx) == 0:
+		return
+	chosen = set(int(i) for i in idx)
+	parts, where = [], {}
+	for g, grp in enumerate(groups):
+		slots = [s for s, i in enumerate(by_slot[g]) if i in chosen]
+		if not slots:
+			continue
+		ids = [by_slot[g][s] for s in slots]
+		sums = np.stack([np.asarray(out.frames.groups[g]['sumimage'][s], dtype='float64') for s in slots])
+		res = pipeline.halo_tpfs(ctx, grp, slots, [cats[i] for i in ids], pos[ids], starid=out.starid[ids], sumimage=sums, settings=settings)
+		for j, i in enumerate(ids):
+			where[i] = (len(parts), j)
+		parts.append(res)
+	out.switch_to_halo(idx, pipeline.HaloResultsOfGroups(parts, [where[int(i)] for i in idx]))
 
 
 def tessphot_tpfs(ctx, files, catalog, targets=None, settings=None, output_folder=None, version=None, chunk_files=None, verify=True,
-	workers=None, compresslevel=9, compress='zlib', table='host'):
+	workers=None, compresslevel=9, compress='zlib', table='host', method='aperture'):
 	"""
 	Aperture photometry of many target pixel files: what ``tessphot('aperture', starid, tpf.TpfStampSource(loaded, catalog,
 	targets=targets), output_folder, datasource='tpf', version=version)`` returns and writes per file, with one pass of the fused
 	kernel, one launch of the diagnostics and one download per group of files that share ``(H, W, T)``.  A generator: one
 	:class:`TpfBatchResults` per chunk of ``chunk_files`` files, in input order.
+
+	``method``: ``'aperture'`` (the default), ``None`` or ``'halo'`` -- what the per-file :func:`tessphot` does with it; anything else
+	raises ``ValueError("Invalid method: '...'")`` before a file is opened.  ``None``: after a group's aperture pass the bright targets
+	whose mask still carries flux on the stamp edge (``TpfBatchResults.halo_switch`` with the ``tpf`` datasource; every reason is logged
+	as a warning) are redone with Halo photometry while the group's cubes are still on the device (``pipeline.halo_tpfs``: the problems
+	built there by ``csrc/halo_cubes.hip``, one ``tp_halo_tvmin`` call per chunk of targets); ``results[i]`` then has ``method == 'halo'``,
+	``halo_weightmap``, "Automatically switched to Halo photometry" among its errors and the aperture run's ``edge_flux``, and its file
+	carries the ``WEIGHTMAP`` extension and the ``HALO_*`` cards.  With ``[halo] enabled`` off the aperture result is kept, the request
+	recorded among its errors and OK turned into WARNING before the file is written, as the per-file entry does.  ``'halo'``: Halo
+	photometry for every file (the aperture pass still runs: it supplies the sum images); ``NotImplementedError`` while Halo is off.
 
 	``files``: the paths; ``catalog`` / ``targets``: as for :class:`~photometry_amd.tpf.TpfStampSource` -- ``row`` / ``column`` in CCD
 	pixels, or ``ra`` / ``dec``, which every file projects through the WCS of its own APERTURE header and moves by its stamp's place
@@ -666,10 +735,13 @@ def tessphot_tpfs(ctx, files, catalog, targets=None, settings=None, output_folde
 	workers build the bytes and write the members (``lcfile.save_tpf_lightcurves``), and with ``table='device'`` besides, the tables' data
 	units written on the device too (``ValueError`` without ``compress='device'``) --; ``QUALITY`` is all zero, what the plugin writes for a source without pixel flags.
 	``verify``: the ``DATASUM`` check of ``tpf.load_tpfs``.
-	This is ``tessphot('aperture', ...)``: with ``[halo] enabled`` in the settings nothing is switched to Halo photometry, which is logged.
+	With ``method='aperture'`` this is ``tessphot('aperture', ...)``: with ``[halo] enabled`` in the settings nothing is switched to Halo
+	photometry, which is logged.
 	"""
 	from . import tpf, halo
 	logger = logging.getLogger(__name__)
+	if method is not None and method not in ('aperture', 'halo'):
+		raise ValueError(f"Invalid method: '{method}'")
 	files = [str(f) for f in files]
 	if not files:
 		raise ValueError("tessphot_tpfs: no files")
@@ -680,7 +752,10 @@ def tessphot_tpfs(ctx, files, catalog, targets=None, settings=None, output_folde
 	from . import lcfile
 	lcfile._check_table(table, compress)
 	settings = load_settings() if settings is None else settings
-	if halo.enabled(settings):
+	if method == 'halo' and not halo.enabled(settings):
+		raise NotImplementedError("HaloPhotometry is off: set '[halo] enabled = true' in the settings file named by "
+			"TESSPHOT_SETTINGS to run this engine's TV-min implementation")
+	if method == 'aperture' and halo.enabled(settings):
 		logger.info("Halo photometry is enabled in the settings, but batches of target pixel files do not switch methods: aperture results are kept.")
 	headers = [tpf.read_tpf_header(f) for f in files]
 	starid = tpf.main_targets(files, [h.header.get('TICID') for h in headers], targets)
@@ -689,7 +764,7 @@ def tessphot_tpfs(ctx, files, catalog, targets=None, settings=None, output_folde
 	chunk_files = max(1, int(chunk_files))
 	for a in range(0, len(files), chunk_files):
 		b = min(a + chunk_files, len(files))
-		out = _tpf_chunk(ctx, files[a:b], headers[a:b], starid[a:b], catalog, targets, verify)
+		out = _tpf_chunk(ctx, files[a:b], headers[a:b], starid[a:b], catalog, targets, verify, method=method, settings=settings)
 		out.ctx = ctx
 		if output_folder is not None:
 			out.save_lightcurves(output_folder, version, workers=workers, compresslevel=compresslevel, compress=compress, table=table)
