@@ -512,6 +512,17 @@ int tp_linpsf_last_counts(tp_ctx* ctx, int64_t* counts, int32_t n);
  * linpsf_photometry.py:116-121 does -- for n_stars stars and n_cad cadences, pos_pitch >= n_cad doubles per star.  (Built on the
  * host these arrays were most of the batched LinPSF entry's time: 75 MB for 2 000 targets.) */
 int tp_star_positions(tp_ctx* ctx, int64_t n_stars, int32_t n_cad, const float* d_base, const float* d_shift, double* d_pos, int64_t pos_pitch);
+/* The same for stars of many targets that each move by a series of their own -- a group of target pixel files, POS_CORR1/2 being per
+ * file: d_pos[s][k] = (double)(d_base[s] + (float)d_shift[t][j]) with t = d_star_target[s] and j = d_lookup[t][k], or j = k when
+ * d_lookup is NULL.  d_base [n_stars] float32 (row_stamp or column_stamp); d_star_target [n_stars]; d_shift [n_targets][shift_pitch]
+ * float64 as loaded (the sum is the plugin's `cat['row_stamp'] + np.float32(jit[k, 1])`, BasePhotometry.catalog_attime for a source
+ * with `jitter`, widened as linpsf_photometry.py:116-121 does; a NaN shift gives a NaN position); d_lookup [n_targets][lookup_pitch]
+ * cadence -> row of d_shift: the plugin's argmin(|tref - tref[k]|), which is k itself for a finite, strictly increasing tref.
+ * pos_pitch >= n_cad, lookup_pitch >= n_cad, shift_pitch >= n_cad without a lookup and >= 1 with one; d_pos beyond n_cad in a row is
+ * left as it is.  A star whose target is outside [0, n_targets) and a lookup outside [0, shift_pitch) are not followed: the position
+ * is NaN.  All offsets are 64-bit (4 096 files x a few stars x 19 008 doubles pass 2^31 bytes). */
+int tp_star_positions_targets(tp_ctx* ctx, int64_t n_stars, int32_t n_cad, const float* d_base, const int32_t* d_star_target,
+	const double* d_shift, int64_t shift_pitch, const int32_t* d_lookup, int64_t lookup_pitch, int32_t n_targets, double* d_pos, int64_t pos_pitch);
 int tp_linpsf_fit(tp_ctx* ctx, const tp_cube_desc* desc, const float* d_images,
 	const float* d_subtract, int64_t subtract_pitch,
 	const double* d_coef, const double* d_knots_x, const double* d_knots_y, int32_t n_coef_axis, int32_t max_stars,

@@ -89,6 +89,7 @@ static const char* const kKernelNames[TPK_COUNT] = {
 	"tp_halo_cube_gather_kernel",
 	"tp_halo_cube_norm_kernel",
 	"tp_halo_cube_lightcurve_kernel",
+	"tp_star_positions_targets_kernel",
 };
 
 extern "C" {

@@ -87,6 +87,7 @@ enum tp_kernel_id {
 	TPK_HALO_CUBE_GATHER,
 	TPK_HALO_CUBE_NORM,
 	TPK_HALO_CUBE_LIGHTCURVE,
+	TPK_STAR_POSITIONS_TARGETS,
 	TPK_COUNT
 };
 

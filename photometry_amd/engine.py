@@ -352,6 +352,24 @@ def star_positions(ctx, base, shift):
 	return out
 
 
+def star_positions_targets(ctx, base, star_target, shift, n_cad, lookup=None, out=None):
+	"""Positions of ``n_stars`` stars of many targets that each move by a series of their own (the files of a ``tpf.TpfGroup``:
+	``POS_CORR1/2`` is per file): ``float64(base[s] + float32(shift[t, j]))`` with ``t = star_target[s]`` and ``j = lookup[t, k]``, or ``k``
+	without a ``lookup`` -- the plugin's ``cat['row_stamp'] + np.float32(jit[k, 1])`` widened, on the device
+	(``tp_star_positions_targets``).  ``base`` float32 ``(n_stars,)``, ``star_target`` int32 ``(n_stars,)``, ``shift`` float64
+	``(n_targets, pitch)``, ``lookup`` int32 ``(n_targets, pitch)`` DeviceArrays; ``out``: a float64 ``(>= n_stars, >= n_cad)`` array to
+	write (what lies beyond ``n_cad`` in a row is left alone).  Returns the float64 DeviceArray ``(n_stars, n_cad)``, or ``out``."""
+	n = int(base.shape[0])
+	assert star_target.shape[0] == n and base.dtype == np.float32 and star_target.dtype == np.int32 and shift.dtype == np.float64
+	assert lookup is None or (lookup.dtype == np.int32 and lookup.shape[0] == shift.shape[0])
+	if out is None:
+		out = ctx.empty((max(n, 1), int(n_cad)), 'float64')
+	assert out.dtype == np.float64 and out.shape[0] >= n
+	ctx._check(ctx.lib.tp_star_positions_targets(ctx.handle, n, int(n_cad), base.ptr, star_target.ptr, shift.ptr, int(shift.shape[1]),
+		_ptr(lookup), 0 if lookup is None else int(lookup.shape[1]), int(shift.shape[0]), out.ptr, int(out.shape[1])))
+	return out
+
+
 def linpsf_fit(ctx, images, coef, knots_x, knots_y, star_offsets, target_index, pos_row, pos_col, max_stars,
 	cutoff_radius=5.0, subtract=None, out=None):
 	"""P2-P4 (psf.py:122-148, linpsf_photometry.py:22-34, 79-219).  ``cutoff_radius=None``: no cut-off (psf.py:142)."""

@@ -668,7 +668,8 @@ def save_tpf_lightcurves(results, output_folder, version, workers=None, compress
 	``PIXEL_QUALITY`` and ``POS_CORR1/2`` are the file's columns, ``QUALITY`` is all zero (a target pixel file brings no pixel flags),
 	the ``APERTURE`` image is the file's without SPOC's mask and centroid flags plus this run's, the image cards are the stamp's
 	limits.  A target done with Halo photometry (``tessphot_tpfs(method=None)`` or ``'halo'``) gets the file of the per-file Halo run: the
-	``HALO_*`` cards in place of the K2P2 ones, the Halo mask without a position mask and the ``WEIGHTMAP`` extension.  Threads, ``compresslevel``, ``timings`` (``build`` / ``gzip``), ``compress`` and the return value as :func:`save_lightcurves`;
+	``HALO_*`` cards in place of the K2P2 ones, the Halo mask without a position mask and the ``WEIGHTMAP`` extension; a target done with
+	LinPSF photometry (``method='linpsf'``) the file of the per-file LinPSF run: ``PSF_FERR`` / ``PSF_CONT`` and no mask bits.  Threads, ``compresslevel``, ``timings`` (``build`` / ``gzip``), ``compress`` and the return value as :func:`save_lightcurves`;
 	``compress='device'`` runs on ``ctx`` (default: the context the results were computed on), whose owner the calling thread must be.
 	``table='device'`` (with ``compress='device'``) as in :func:`save_lightcurves`; here every file has its own ``time`` .. ``PIXEL_QUALITY``,
 	so the vectors are strided per target and there is one ``tp_lc_table_pack`` per set of files with one length and one list of kept rows.
@@ -698,6 +699,8 @@ def save_tpf_lightcurves(results, output_folder, version, workers=None, compress
 		info = FileInfo(ld.sector, ld.camera, ld.ccd, cadence=ld.cadence, n_readout=ld.n_readout, num_frm=ld.num_frm or 60, header=header)   # (60: BasePhotometry.py:372)
 		if r.method == 'halo':
 			headers = dict(results.halo.headers)
+		elif r.method == 'linpsf':
+			headers = dict(r.additional_headers)                             # (PSF_FERR, PSF_CONT: no mask was made, no K2P2 cards)
 		else:
 			headers = dict(k2p2_headers)
 			if 'contamination' in r._details:

@@ -1423,3 +1423,270 @@ def halo_tpfs(ctx, group, idx, catalogs, positions, starid=None, sumimage=None, 
 		for a in (diag, d_block, d_status, d_mask, d_sum, d_time, d_q):
 			a.free()
 	return out
+
+
+#--------------------------------------------------------------------------------------------------
+# LinPSF photometry of many target pixel files of one shape (the batched counterpart of the LinPSF plugin on a ``tpf`` source)
+#--------------------------------------------------------------------------------------------------
+class LinPSFTpfsResult(PSFFramesResult):
+	"""
+	Columnar results of :func:`linpsf_tpfs` over the chosen slots of a group: what :class:`PSFFramesResult` holds for ``'linpsf'``, the
+	``status`` and ``errors`` final -- with what ``BasePhotometry.photometry`` makes of the light-curve diagnostics --, plus per target
+	``diagnostics`` (the dict of ``engine.DIAGNOSTICS_COLUMNS`` for a target the fit left OK or WARNING, else None), ``n_stars`` (stars
+	fitted), ``fitted`` (the target went through the fit: its ``flux`` / ``flux_err`` are the fit's) and ``headers`` (the
+	``additional_headers`` of the plugin: ``PSF_FERR``, ``PSF_CONT``).  ``flux_errors``: whether the error pass ran.
+	"""
+	def __init__(self, n, T, flux_errors):
+		super().__init__(n, T, 'linpsf')
+		self.flux_errors = bool(flux_errors)
+		self.diagnostics = [None] * n
+		self.headers = [{} for _ in range(n)]
+		self.n_stars = np.zeros(n, dtype='int64')
+		self.fitted = np.zeros(n, dtype=bool)
+
+	def __getitem__(self, i):
+		i = int(i)
+		r = super().__getitem__(i)
+		r.update(diagnostics=self.diagnostics[i], headers=dict(self.headers[i]), n_stars=int(self.n_stars[i]), fitted=bool(self.fitted[i]))
+		return r
+
+
+def _prf_models_of_slots(group, slots, prf):
+	"""The PRF model of every chosen slot -- ``prf`` itself, ``prf[(camera, ccd)]``, or with ``None`` the SPOC model of the file's sector,
+	camera and CCD from ``TESSPHOT_PSF_DIR`` as ``BasePhotometry.psf`` finds it -- or the text of the exception the plugin would die of."""
+	import os
+	from . import psf as hpsf
+	from .plugins import _PRF_CACHE
+	models = []
+	for s in slots:
+		ld = group.loaded[s]
+		try:
+			if prf is None:
+				psf_dir = os.environ.get('TESSPHOT_PSF_DIR')
+				if not psf_dir:
+					raise FileNotFoundError("the stamp source provides no PRF model and no PRF directory is configured (TESSPHOT_PSF_DIR)")
+				key = (os.path.abspath(psf_dir), int(ld.sector), int(ld.camera), int(ld.ccd))
+				if key not in _PRF_CACHE:
+					_PRF_CACHE[key] = hpsf.PRFModel.for_ccd(psf_dir, ld.sector, ld.camera, ld.ccd)
+				models.append(_PRF_CACHE[key])
+			elif isinstance(prf, hpsf.PRFModel):
+				models.append(prf)
+			else:
+				models.append(prf[(int(ld.camera), int(ld.ccd))])
+		except (FileNotFoundError, ValueError, KeyError, TypeError) as e:
+			models.append(f"{type(e).__name__}: {e}")
+	return models
+
+
+def _consecutive_slices(slots, cost, budget):
+	"""``slots`` (rising) cut into slices of consecutive slot numbers whose summed ``cost`` stays within ``budget`` (a slice holds at least
+	one slot): ``[(first position in slots, count), ...]``."""
+	out, a = [], 0
+	while a < len(slots):
+		b, spent = a + 1, cost[a]
+		while b < len(slots) and slots[b] == slots[b - 1] + 1 and spent + cost[b] <= budget:
+			spent += cost[b]
+			b += 1
+		out.append((a, b - a))
+		a = b
+	return out
+
+
+def linpsf_tpfs(ctx, group, idx, catalogs, positions, starid, prf, cutoff_radius=5, flux_errors=False, budget_bytes=None):
+	"""
+	``LinPSFPhotometry.do_photometry`` for the slots ``idx`` of a ``tpf.TpfGroup`` whose cubes are resident on the device --
+	``tessphot('linpsf', starid, TpfStampSource(loaded, catalog, prf=model), datasource='tpf')`` for many files of one shape.  The stamp
+	is the file's ``max_stamp``; the stars fitted beside each target are selected as the plugin selects them (``psf.select_stars`` over
+	the concatenated ``catalogs``: per chosen slot the stars of its stamp with ``starid, tmag, row_stamp, column_stamp``); their positions
+	at every cadence are catalogue position + the FILE's ``pos_corr`` at the cadence ``tpf.jitter_lookup`` names, summed in float32 and
+	formed on the device from the group's ``pos_corr`` uploaded once (``tp_star_positions_targets``, one call per axis and slice; a file
+	whose lookup is not the identity has its stars redone with it); ``tp_linpsf_fit`` runs on ``group.cubes['images']`` as it lies, and with
+	``flux_errors`` ``tp_linpsf_flux_err`` on ``group.cubes['images_err']`` with the same device arrays.
+
+	``prf``: a ``psf.PRFModel`` for all files, a mapping ``(camera, ccd) -> PRFModel``, or ``None``: the SPOC model of each file's sector,
+	camera and CCD from ``TESSPHOT_PSF_DIR``.  Models that share their knots are fitted in one pass, each slot with the coefficients of
+	its own model; models with other knots get a pass of their own over their slots.  ``positions`` (``(len(idx), 3)`` row, column, Tmag
+	of the main targets, as :func:`halo_tpfs` takes them) and ``starid``: the main targets.
+
+	Slots that are not in ``idx`` are never handed to a kernel: the fit runs over slices of CONSECUTIVE chosen slots, the cube pointer
+	moved to the first slot of a slice.  A slice also ends where its position, per-star flux, flux and flux-error arrays (float64, one
+	row of ``T`` per fitted star or target) would pass ``budget_bytes`` (default: a quarter of the device memory free at the call); every
+	target is fitted on its own, so where a slice ends changes no bit.
+
+	Status and messages are the plugin's: ERROR "All target flux values are NaN.", WARNING "High contamination" above 0.1, else OK; then
+	the light-curve diagnostics of the OK / WARNING targets (one ``tp_lightcurve_diagnostics_times`` launch, every target on its own time
+	axis) as ``BasePhotometry.photometry`` reads them: all fluxes or all errors NaN, or an invalid time vector, is ERROR with the
+	``ValueError``'s text -- with ``flux_errors`` off that is every target, as in the reference, whose ``flux_err`` is NaN.
+	Returns a :class:`LinPSFTpfsResult` over ``idx``.
+	"""
+	idx = [int(s) for s in idx]
+	m = len(idx)
+	H, W, T = group.shape
+	if any(b <= a for a, b in zip(idx, idx[1:])) or (m and not (0 <= idx[0] and idx[-1] < len(group))):
+		raise ValueError("linpsf_tpfs: idx must be rising slot numbers of the group")
+	starid = np.asarray(starid, dtype='int64').reshape(m)
+	out = LinPSFTpfsResult(m, T, flux_errors)
+	for j, s in enumerate(idx):
+		out.stamp[j] = group.loaded[s].max_stamp
+	# what a target cannot be fitted without: its model and itself among its stars (the plugin dies of the exception; so does the target)
+	models = _prf_models_of_slots(group, idx, prf)
+	fit = []
+	for j in range(m):
+		if isinstance(models[j], str):
+			out.status[j], out.errors[j] = STATUS.ERROR.value, [models[j]]
+		elif not np.any(np.asarray(catalogs[j]['starid']) == starid[j]):
+			out.status[j], out.errors[j] = STATUS.ERROR.value, ['ValueError: main target missing from its catalog']
+		else:
+			fit.append(j)
+	# one pass per set of models with the same knots
+	passes = []
+	for j in fit:
+		for p in passes:
+			ref = models[p[0]]
+			if models[j] is ref or (np.array_equal(models[j].tx, ref.tx) and np.array_equal(models[j].ty, ref.ty)):
+				p.append(j)
+				break
+		else:
+			passes.append([j])
+	if budget_bytes is None:
+		budget_bytes = ctx.mem_info()[0] / 4.0
+	images, images_err = group.cubes['images'], group.cubes['images_err']
+	d_shift = None
+	try:
+		if fit:
+			# the group's POS_CORR, once: [n][T] float64 per axis (column, row)
+			jit = np.stack([np.asarray(ld.pos_corr, dtype='float64').reshape(T, 2) for ld in group.loaded])
+			d_shift = (ctx.array(np.ascontiguousarray(jit[:, :, 0])), ctx.array(np.ascontiguousarray(jit[:, :, 1])))
+		for members in passes:
+			_linpsf_tpfs_pass(ctx, group, idx, members, catalogs, starid, models, d_shift, images, images_err if flux_errors else None,
+				cutoff_radius, budget_bytes, out)
+	finally:
+		ctx.sync()
+		for a in d_shift or ():
+			a.free()
+	# linpsf_photometry.py:198-200, :214-219: ERROR when every flux is NaN, WARNING above 10 % contamination (NaN compares false)
+	for j in fit:
+		if flux_errors:
+			out.headers[j]['PSF_FERR'] = (True, 'flux errors propagated from pixel errors')
+		if out.status[j] == 2:
+			out.status[j], out.errors[j] = STATUS.ERROR.value, ['All target flux values are NaN.']
+			continue
+		contamination = float(out.contamination[j])
+		out.headers[j]['PSF_CONT'] = (contamination, 'PSF contamination')
+		if contamination > 0.1:
+			out.status[j], out.errors[j] = STATUS.WARNING.value, ['High contamination']
+		else:
+			out.status[j] = STATUS.OK.value
+	out.finish()
+	# BasePhotometry.photometry (BasePhotometry.py:1343-1407) for the OK / WARNING targets, every target on its own time axis: one launch
+	ok = np.array([j for j in fit if out.status[j] in (STATUS.OK.value, STATUS.WARNING.value)], dtype='int64')
+	if len(ok):
+		slots = [idx[j] for j in ok]
+		block = np.zeros((5, len(ok), T))
+		block[0], block[1] = out.flux[ok], out.flux_err[ok]                 # (no centroids: the plugin leaves pos_centroid at zero)
+		d_time, d_q = ctx.array(np.ascontiguousarray(group.time[slots])), ctx.array(np.ascontiguousarray(group.quality[slots], dtype='int32'))
+		d_status, d_block = ctx.array(np.ascontiguousarray(out.status[ok], dtype='int32')), ctx.array(block)
+		lc = engine.LightCurves(ctx, len(ok), T, block=d_block)
+		diag = engine.lightcurve_diagnostics(ctx, lc, d_time, d_q, status=d_status)
+		host = diag.to_host()
+		for a in (diag, d_block, d_status, d_time, d_q):
+			a.free()
+		for r, j in enumerate(ok):
+			d = dict(zip(engine.DIAGNOSTICS_COLUMNS, host[r]))
+			out.diagnostics[j] = d
+			problems = int(d['flags'])
+			text = ('ValueError: Final lightcurve fluxes are all NaNs' if problems & 1 else 'ValueError: Final lightcurve errors are all NaNs' if problems & 2
+				else 'ValueError: Invalid time-vector specified' if problems & 4 else None)
+			if text is not None:
+				out.status[j] = STATUS.ERROR.value
+				out.errors.setdefault(int(j), []).append(text)
+			elif problems & 8:
+				out.errors.setdefault(int(j), []).append('WARNING: Could not detrend lightcurve for variability calculation.')
+	return out
+
+
+def _linpsf_tpfs_pass(ctx, group, idx, members, catalogs, starid, models, d_shift, images, images_err, cutoff_radius, budget_bytes, out):
+	"""One pass of :func:`linpsf_tpfs`: the chosen targets ``members`` (positions in ``idx``), whose models share their knots, slice by slice."""
+	from . import psf as hpsf, tpf
+	H, W, T = group.shape
+	ref = models[members[0]]
+	slots = [idx[j] for j in members]
+	# the stars of every member, as the plugin selects them
+	counts = [len(catalogs[j]['starid']) for j in members]
+	offs = np.concatenate(([0], np.cumsum(counts))).astype('int64')
+	cat = {k: np.concatenate([np.asarray(catalogs[j][k]) for j in members]) for k in ('starid', 'tmag', 'row_stamp', 'column_stamp')}
+	sel, star_offsets, target_index = hpsf.select_stars(cat, offs, starid[members])
+	n_stars = np.diff(star_offsets)
+	out.n_stars[members] = n_stars
+	base_row = np.ascontiguousarray(cat['row_stamp'][sel], dtype='float32')
+	base_col = np.ascontiguousarray(cat['column_stamp'][sel], dtype='float32')
+	star_target = np.repeat(np.asarray(slots, dtype='int32'), n_stars).astype('int32')     # (the slot: the row of the group's pos_corr)
+	# per member: positions and per-star fluxes of its stars, its flux and flux error -- float64 rows of T
+	cost = [(3 * max(int(k), 1) + 2) * T * 8 for k in n_stars]
+	# the spline coefficients of every member's slot, each from its own model: [members][n * ny] float64
+	by_model = {}
+	for r, j in enumerate(members):
+		by_model.setdefault(id(models[j]), []).append(r)
+	coef = ctx.empty((len(members), ref.base_coef.shape[1]), 'float64')
+	tx, ty = ctx.array(ref.tx), ctx.array(ref.ty)
+	keep = [coef, tx, ty]
+	try:
+		for rows in by_model.values():
+			model = models[members[rows[0]]]
+			d_base = ctx.array(model.base_coef)
+			keep.append(d_base)
+			a = 0
+			while a < len(rows):                                               # (runs of consecutive members: written in place)
+				b = a + 1
+				while b < len(rows) and rows[b] == rows[b - 1] + 1:
+					b += 1
+				d_w = ctx.array(model.weights(out.stamp[[members[r] for r in rows[a:b]]]))
+				keep.append(d_w)
+				engine.linpsf_prf(ctx, d_base, d_w, out=coef.slice0(rows[a], b - a))
+				a = b
+		lookups = {r: tpf.jitter_lookup(group.loaded[s].time, group.loaded[s].timecorr) for r, s in enumerate(slots)}
+		for a, count in _consecutive_slices(slots, cost, budget_bytes):
+			rows = np.arange(a, a + count)
+			s0, s1 = int(star_offsets[a]), int(star_offsets[a + count])
+			nfit = s1 - s0
+			d_row, d_col = ctx.array(base_row[s0:s1]), ctx.array(base_col[s0:s1])
+			d_tgt = ctx.array(star_target[s0:s1])
+			pos_row, pos_col = ctx.empty((max(nfit, 1), T), 'float64'), ctx.empty((max(nfit, 1), T), 'float64')
+			held = [d_row, d_col, d_tgt, pos_row, pos_col]
+			engine.star_positions_targets(ctx, d_row, d_tgt, d_shift[1], T, out=pos_row)
+			engine.star_positions_targets(ctx, d_col, d_tgt, d_shift[0], T, out=pos_col)
+			for r in rows:
+				if lookups[int(r)] is None or n_stars[r] == 0:
+					continue
+				# a file whose tref repeats or is not finite: its stars again, through its lookup
+				b0, k = int(star_offsets[r]) - s0, int(n_stars[r])
+				d_look = ctx.array(lookups[int(r)].reshape(1, T))
+				d_zero = ctx.array(np.zeros(k, dtype='int32'))
+				held += [d_look, d_zero]
+				s = slots[int(r)]
+				engine.star_positions_targets(ctx, d_row.slice0(b0, k), d_zero, d_shift[1].slice0(s, 1), T, lookup=d_look, out=pos_row.slice0(b0, k))
+				engine.star_positions_targets(ctx, d_col.slice0(b0, k), d_zero, d_shift[0].slice0(s, 1), T, lookup=d_look, out=pos_col.slice0(b0, k))
+			d_offsets = ctx.array((star_offsets[a:a + count + 1] - s0).astype('int64'))
+			d_index = ctx.array(np.ascontiguousarray(target_index[a:a + count], dtype='int32'))
+			held += [d_offsets, d_index]
+			max_stars = max(int(n_stars[a:a + count].max()), 1)
+			cube = images.slice0(slots[a], count)
+			res = engine.linpsf_fit(ctx, cube, coef.slice0(a, count), tx, ty, d_offsets, d_index, pos_row, pos_col, max_stars, cutoff_radius=cutoff_radius)
+			held += [res.flux, res.flux_err, res.fluxes_all, res.contamination, res.status, res.fluxes_mean]
+			if images_err is not None:
+				engine.linpsf_flux_err(ctx, cube, images_err.slice0(slots[a], count), coef.slice0(a, count), tx, ty, d_offsets, d_index, pos_row, pos_col,
+					max_stars, cutoff_radius=cutoff_radius, out=res.flux_err)
+			host = res.to_host(('flux', 'flux_err', 'contamination', 'status'))
+			where = [members[int(r)] for r in rows]
+			out.flux[where] = host['flux'][:, :T]
+			out.flux_err[where] = host['flux_err'][:, :T]
+			out.contamination[where] = host['contamination']
+			out.status[where] = host['status']
+			out._covered[where] = True
+			out.fitted[where] = True
+			for x in held:
+				x.free()
+	finally:
+		ctx.sync()
+		for x in keep:
+			x.free()

@@ -15,7 +15,8 @@ call sites run_tessphot.py:153, run_tessphot_mpi.py:178) with the contract they 
 ``tessphot_batch`` / ``tessphot_frames`` are the throughput entries (not in the reference): a whole batch per device pass.
 ``tessphot_tpfs`` is the one for target pixel files: ``tessphot('aperture', ..., datasource='tpf')`` for many files, one pass per group
 of files that share stamp shape and number of cadences; with ``method=None`` or ``'halo'`` it is ``tessphot(None, ...)`` /
-``tessphot('halo', ...)`` for them, the Halo problems built on the device from the group's cubes (``pipeline.halo_tpfs``).
+``tessphot('halo', ...)`` for them, the Halo problems built on the device from the group's cubes (``pipeline.halo_tpfs``), and with
+``method='linpsf'`` ``tessphot('linpsf', ...)``, one fit per group on the cubes as they lie (``pipeline.linpsf_tpfs``).
 """
 
 import logging
@@ -155,6 +156,8 @@ class BatchResult(object):
 		self.final_phot_mask = mask
 		#: the weight maps of a target done with Halo photometry (``halo.photometry``'s ``weightmap`` dict), else None
 		self.halo_weightmap = None
+		#: the header cards a method adds to its light-curve file where the batch knows them per target (LinPSF: ``PSF_FERR``, ``PSF_CONT``)
+		self.additional_headers = {}
 
 
 def _diagnostics_into(details, d, status):
@@ -506,7 +509,8 @@ class TpfBatchResults(BatchResults):
 	``column(name)`` as there; ``results[i]`` is the :class:`BatchResult` the per-file call ``tessphot('aperture', starid,
 	TpfStampSource(...), datasource='tpf')`` returns (with ``method=None`` / ``'halo'`` of the entry: what ``tessphot(None, ...)`` /
 	``tessphot('halo', ...)`` returns; ``halo_rows``, ``halo`` and ``halo_requests`` say which targets were switched, to what, or would have
-	been with Halo photometry on): its light curve carries ``time, timecorr, cadenceno, quality`` and ``pos_corr``
+	been with Halo photometry on; with ``method='linpsf'``: what ``tessphot('linpsf', ...)`` returns, ``linpsf`` holds the groups'
+	``pipeline.LinPSFTpfsResult`` s): its light curve carries ``time, timecorr, cadenceno, quality`` and ``pos_corr``
 	(``POS_CORR1/2``) of the file besides the photometry.  ``stamp_resizes`` is 0 throughout (a ``tpf`` stamp is the whole file) and is
 	kept in the details, as on :class:`BatchResults`; where the diagnostics raise upstream the details carry that error alone, as the
 	plugin's do.  ``loaded``: the ``tpf.LoadedTPF`` of every file (its cubes are gone once the chunk has been yielded).
@@ -524,6 +528,48 @@ class TpfBatchResults(BatchResults):
 		self.ctx = None
 		#: ``method=None`` with Halo photometry off: target -> the recorded request (:meth:`keep_aperture_results`)
 		self.halo_requests = {}
+		#: ``method='linpsf'``: the :class:`~photometry_amd.pipeline.LinPSFTpfsResult` of every group, target -> (part, row), and the files
+		#: whose main target is not in the catalogue -> the error (:meth:`set_linpsf`); None for the other methods
+		self.linpsf = None
+		self._linpsf_where, self._linpsf_lost = {}, {}
+
+	def set_linpsf(self, parts, where, lost):
+		"""The chunk was run with ``method='linpsf'``: ``parts`` are the ``pipeline.linpsf_tpfs`` results of its groups, target ``i`` is row
+		``where[i][1]`` of ``parts[where[i][0]]``; the targets of ``lost`` never got a photometry object (``lost[i]``: why)."""
+		self.linpsf = list(parts)
+		self._linpsf_where = {int(i): (int(p), int(j)) for i, (p, j) in where.items()}
+		self._linpsf_lost = {int(i): str(text) for i, text in lost.items()}
+		self.status[:] = STATUS.ERROR.value
+		for i, (p, j) in self._linpsf_where.items():
+			self.status[i] = self.linpsf[p].status[j]
+
+	def _linpsf_item(self, i):
+		"""What ``tessphot('linpsf', starid, TpfStampSource(...), datasource='tpf')`` returns for file ``i``."""
+		if not 0 <= i < len(self):
+			raise IndexError(i)
+		if i not in self._linpsf_where:
+			return BatchResult(int(self.starid[i]), STATUS.ERROR, 'linpsf', {'errors': [self._linpsf_lost[i]]}, None, None)
+		p, j = self._linpsf_where[i]
+		r = self.linpsf[p][j]
+		status = STATUS(r['status'])
+		details = {'stamp': r['stamp']}
+		lc = None
+		if r['fitted']:
+			# (the fit ran: the plugin's light curve holds what it gave whatever became of the status; pos_centroid stays as created)
+			T = len(r['flux'])
+			lc = {'flux': r['flux'], 'flux_err': r['flux_err'], 'flux_background': np.zeros(T), 'pos_centroid': np.zeros((T, 2))}
+		d = r['diagnostics']
+		if d is not None and status in (STATUS.OK, STATUS.WARNING):
+			for key in ('mean_flux', 'variance', 'rms_hour', 'ptp', 'variability'):
+				details[key] = float(d[key])
+			details['pos_centroid'] = np.array([d['pos_centroid_col'], d['pos_centroid_row']])
+		if r['errors']:
+			details['errors'] = list(r['errors'])
+		if i in self._filepath_rel:
+			details['filepath_lightcurve'] = self._filepath_rel[i]
+		out = BatchResult(int(self.starid[i]), status, 'linpsf', details, lc, None)
+		out.additional_headers = r['headers']
+		return out
 
 	def keep_aperture_results(self, idx, codes):
 		"""The targets ``idx`` should have gone to Halo photometry (reasons ``codes``) but it is off: the aperture results are kept, the
@@ -550,7 +596,7 @@ class TpfBatchResults(BatchResults):
 
 	def __getitem__(self, i):
 		i = int(i) + len(self) if int(i) < 0 else int(i)
-		out = super().__getitem__(i)
+		out = self._linpsf_item(i) if self.linpsf is not None else super().__getitem__(i)
 		if i not in self.halo_rows and (self._problems[i] & 7) and 'errors' in out._details:
 			out._details['errors'] = out._details['errors'][-1:]       # (the plugin raises: what it had logged is lost, BasePhotometry.py:1346-1349)
 		if i in self.halo_requests:
@@ -592,7 +638,38 @@ def _one_attempt(flags):
 	return (STATUS.WARNING if flags & 1 else status), True, messages
 
 
-def _tpf_chunk(ctx, files, headers, starid, catalog, targets, verify, method='aperture', settings=None):
+def _linpsf_tpfs_chunk(ctx, fr, groups, by_slot, cats, pos, lost, starid, files, loaded, prf, flux_errors):
+	"""``method='linpsf'`` for a loaded chunk: per group the sum images the light-curve files carry (``tp_sumimage`` on the group's cube with
+	every file's own quality row: the plugin's ``sumimage`` property) and one ``pipeline.linpsf_tpfs`` over the files whose main target is
+	in the catalogue.  No aperture mask is made and nothing of the K2P2 / extraction pass is run."""
+	from . import pipeline, engine
+	n = len(files)
+	apertures = [None] * n
+	parts, where = [], {}
+	for g, grp in enumerate(groups):
+		ids = by_slot[g]
+		d_quality = ctx.array(np.ascontiguousarray(grp.quality, dtype='int32'))
+		d_sum = engine.sumimage(ctx, grp.cubes['images'], d_quality)
+		fr.groups.append({'sumimage': d_sum.to_host()})
+		d_sum.free()
+		d_quality.free()
+		for s, i in enumerate(ids):
+			fr.group[i], fr.pos[i] = g, s
+			apertures[i] = grp.aperture[s]
+		slots = [s for s, i in enumerate(ids) if i not in lost]
+		if not slots:
+			continue
+		chosen = [ids[s] for s in slots]
+		res = pipeline.linpsf_tpfs(ctx, grp, slots, [cats[i] for i in chosen], pos[chosen], np.asarray(starid, dtype='int64')[chosen], prf, flux_errors=flux_errors)
+		for j, i in enumerate(chosen):
+			where[i] = (len(parts), j)
+		parts.append(res)
+	out = TpfBatchResults(fr, starid, pos[:, 2], files, loaded, apertures)
+	out.set_linpsf(parts, where, lost)
+	return out
+
+
+def _tpf_chunk(ctx, files, headers, starid, catalog, targets, verify, method='aperture', settings=None, prf=None, linpsf_errors=False):
 	"""One chunk of :func:`tessphot_tpfs`: load, one device pass per ``(H, W, T)`` group, the method switch, the results in input order."""
 	from . import tpf, pipeline
 	n = len(files)
@@ -641,9 +718,11 @@ def _tpf_chunk(ctx, files, headers, starid, catalog, targets, verify, method='ap
 		by_slot = [[None] * len(g) for g in groups]
 		for i, (g, s) in enumerate(index):
 			by_slot[g][s] = i
+		if method == 'linpsf':
+			return _linpsf_tpfs_chunk(ctx, fr, groups, by_slot, cats, pos, lost, starid, files, loaded, prf, linpsf_errors)   # (no K2P2 / extraction pass)
 		for g, grp in enumerate(groups):
 			ids = by_slot[g]
-			offs = np.concatenate(([0], np.cumsum([len(cats[i]['starid']) for i in ids]))).astype('int64')
+			offs =np.concatenate(([0], np.cumsum([len(cats[i]['starid']) for i in ids]))).astype('int64')
 			cat = {k: np.concatenate([cats[i][k] for i in ids]) for k in ('starid', 'tmag', 'row', 'column', 'row_stamp', 'column_stamp')}
 			scene = pipeline.GroupScene(grp.time, grp.quality, stamps_all[ids], offs, cat, pos[ids, 0], pos[ids, 1], pos[ids, 2],
 				np.asarray(starid, dtype='int64')[ids], grp.aperture, cadence_s=grp.loaded[0].cadence or 1800)
@@ -705,15 +784,15 @@ def _halo_switch_tpfs(ctx, out, groups, by_slot, cats, pos, lost, method, settin
 
 
 def tessphot_tpfs(ctx, files, catalog, targets=None, settings=None, output_folder=None, version=None, chunk_files=None, verify=True,
-	workers=None, compresslevel=9, compress='zlib', table='host', method='aperture'):
+	workers=None, compresslevel=9, compress='zlib', table='host', method='aperture', prf=None):
 	"""
 	Aperture photometry of many target pixel files: what ``tessphot('aperture', starid, tpf.TpfStampSource(loaded, catalog,
 	targets=targets), output_folder, datasource='tpf', version=version)`` returns and writes per file, with one pass of the fused
 	kernel, one launch of the diagnostics and one download per group of files that share ``(H, W, T)``.  A generator: one
 	:class:`TpfBatchResults` per chunk of ``chunk_files`` files, in input order.
 
-	``method``: ``'aperture'`` (the default), ``None`` or ``'halo'`` -- what the per-file :func:`tessphot` does with it; anything else
-	raises ``ValueError("Invalid method: '...'")`` before a file is opened.  ``None``: after a group's aperture pass the bright targets
+	``method``: ``'aperture'`` (the default), ``None``, ``'halo'`` or ``'linpsf'`` -- what the per-file :func:`tessphot` does with it; anything
+	else (``'psf'`` too) raises ``ValueError("Invalid method: '...'")`` before a file is opened.  ``None``: after a group's aperture pass the bright targets
 	whose mask still carries flux on the stamp edge (``TpfBatchResults.halo_switch`` with the ``tpf`` datasource; every reason is logged
 	as a warning) are redone with Halo photometry while the group's cubes are still on the device (``pipeline.halo_tpfs``: the problems
 	built there by ``csrc/halo_cubes.hip``, one ``tp_halo_tvmin`` call per chunk of targets); ``results[i]`` then has ``method == 'halo'``,
@@ -721,6 +800,13 @@ def tessphot_tpfs(ctx, files, catalog, targets=None, settings=None, output_folde
 	carries the ``WEIGHTMAP`` extension and the ``HALO_*`` cards.  With ``[halo] enabled`` off the aperture result is kept, the request
 	recorded among its errors and OK turned into WARNING before the file is written, as the per-file entry does.  ``'halo'``: Halo
 	photometry for every file (the aperture pass still runs: it supplies the sum images); ``NotImplementedError`` while Halo is off.
+	``'linpsf'``: ``tessphot('linpsf', starid, TpfStampSource(loaded, catalog, prf=model), ...)`` for every file, one fit per group on the
+	group's cubes as they lie (``pipeline.linpsf_tpfs``: the stars' positions formed on the device from every file's own ``POS_CORR``,
+	``tp_star_positions_targets``).  No aperture pass runs: a result has no photometric mask, ``additional_headers`` ``PSF_CONT`` (and
+	``PSF_FERR``), and the file's ``SUMIMAGE`` comes from ``tp_sumimage`` on the group's cube.  ``prf``: a ``psf.PRFModel``, a mapping
+	``(camera, ccd) -> PRFModel``, or ``None`` for the SPOC model of each file's sector, camera and CCD under ``TESSPHOT_PSF_DIR``.
+	``[linpsf] flux_errors`` of the settings is read once per call; while it is off every ``flux_err`` is NaN, as in the reference, and
+	every target ends in ERROR "Final lightcurve errors are all NaNs" without a file, as the per-file call does.
 
 	``files``: the paths; ``catalog`` / ``targets``: as for :class:`~photometry_amd.tpf.TpfStampSource` -- ``row`` / ``column`` in CCD
 	pixels, or ``ra`` / ``dec``, which every file projects through the WCS of its own APERTURE header and moves by its stamp's place
@@ -740,7 +826,7 @@ def tessphot_tpfs(ctx, files, catalog, targets=None, settings=None, output_folde
 	"""
 	from . import tpf, halo
 	logger = logging.getLogger(__name__)
-	if method is not None and method not in ('aperture', 'halo'):
+	if method is not None and method not in ('aperture', 'halo', 'linpsf'):
 		raise ValueError(f"Invalid method: '{method}'")
 	files = [str(f) for f in files]
 	if not files:
@@ -757,6 +843,7 @@ def tessphot_tpfs(ctx, files, catalog, targets=None, settings=None, output_folde
 			"TESSPHOT_SETTINGS to run this engine's TV-min implementation")
 	if method == 'aperture' and halo.enabled(settings):
 		logger.info("Halo photometry is enabled in the settings, but batches of target pixel files do not switch methods: aperture results are kept.")
+	linpsf_errors = method == 'linpsf' and LinPSFPhotometry.flux_errors(settings)      # ([linpsf] flux_errors: read once per call)
 	headers = [tpf.read_tpf_header(f) for f in files]
 	starid = tpf.main_targets(files, [h.header.get('TICID') for h in headers], targets)
 	if chunk_files is None:
@@ -764,7 +851,8 @@ def tessphot_tpfs(ctx, files, catalog, targets=None, settings=None, output_folde
 	chunk_files = max(1, int(chunk_files))
 	for a in range(0, len(files), chunk_files):
 		b = min(a + chunk_files, len(files))
-		out = _tpf_chunk(ctx, files[a:b], headers[a:b], starid[a:b], catalog, targets, verify, method=method, settings=settings)
+		out = _tpf_chunk(ctx, files[a:b], headers[a:b], starid[a:b], catalog, targets, verify, method=method, settings=settings, prf=prf,
+			linpsf_errors=linpsf_errors)
 		out.ctx = ctx
 		if output_folder is not None:
 			out.save_lightcurves(output_folder, version, workers=workers, compresslevel=compresslevel, compress=compress, table=table)

@@ -512,6 +512,34 @@ def load_tpf_groups(ctx, files, verify=True, headers=None):
 	return out_groups, index
 
 
+def jitter_lookup(time, timecorr):
+	"""
+	The row of a file's ``pos_corr`` the plugin applies at cadence ``k``: ``argmin(|tref - tref[k]|)`` with ``tref = time - timecorr``
+	(``BasePhotometry.catalog_attime`` for a source with ``jitter``, called with ``tref[k]`` by the LinPSF plugin).  Returns ``None`` when
+	that is ``k`` for every cadence, else the int32 vector.  For finite values it is the first cadence with the value of ``tref[k]``
+	-- ``k`` itself unless values repeat --, found by sorting; numpy's ``argmin`` returns the first NaN it meets, so with a value that is
+	not finite in ``tref`` the rows are computed as the plugin computes them, cadence by cadence (``T^2`` differences, in pieces).
+	"""
+	tref = np.asarray(time, dtype='float64') - np.asarray(timecorr, dtype='float64')
+	T = len(tref)
+	if T == 0:
+		return None
+	if np.all(np.isfinite(tref)):
+		if np.all(tref[1:] > tref[:-1]):
+			return None
+		_, first, inverse = np.unique(tref, return_index=True, return_inverse=True)
+		lookup = first[np.asarray(inverse).reshape(-1)]
+	else:
+		lookup = np.empty(T, dtype='int64')
+		step = max(1, (1 << 22) // T)
+		with np.errstate(invalid='ignore'):
+			for a in range(0, T, step):
+				lookup[a:a + step] = np.argmin(np.abs(tref[None, :] - tref[a:a + step, None]), axis=1)
+	if np.array_equal(lookup, np.arange(T)):
+		return None
+	return lookup.astype('int32')
+
+
 def _needs_projection(d):
 	return d is not None and 'row' not in d and 'column' not in d and 'ra' in d and 'dec' in d
 
