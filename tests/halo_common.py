@@ -148,7 +148,7 @@ def objective(P, fit, theta, with_grad=True):
 	return f, w * (g - w @ g)
 
 
-def lbfgs(P, fit, maxiter=SETTINGS['maxiter'], history=HISTORY, ftol=FTOL, gtol=GTOL, theta0=None):
+def lbfgs(P, fit, maxiter=SETTINGS['maxiter'], history=HISTORY, ftol=FTOL, gtol=GTOL, theta0=None, trace=None):
 	"""
 	The optimiser of tp_halo_tvmin.  From ``theta = 0``: gradient ``g``; if ``|g|_inf <= gtol`` converged (0 iterations).
 	Iteration: direction ``d`` by the two-loop recursion over the stored pairs (oldest .. newest, ``gamma = s.y / y.y`` of the
@@ -157,6 +157,10 @@ def lbfgs(P, fit, maxiter=SETTINGS['maxiter'], history=HISTORY, ftol=FTOL, gtol=
 	theta kept; accepted: ``s = theta_new - theta``, ``y = g_new - g``, the pair kept (the oldest of ``history`` dropped) if
 	``s.y > 1e-10 y.y``; then in order: ``f_k - f_k+1 <= ftol max(|f_k|, |f_k+1|, 1)`` -> 1, ``|g_new|_inf <= gtol`` -> 1,
 	``iterations >= maxiter`` -> 2.  Returns dict ``theta, w, f, iterations, status``.
+
+	``trace`` (a dict, optional) only records what was decided: ``trials`` gets ``(fn, f + C1 alpha g.d, accepted)`` of every
+	line-search trial, ``pairs`` gets ``(s.y, 1e-10 y.y, kept)`` of every accepted step, ``stops`` gets
+	``(f_k - f_k+1, ftol max(|f_k|, |f_k+1|, 1), |g_new|_inf)`` of every accepted step.
 	"""
 	n = P.shape[1]
 	theta = np.zeros(n) if theta0 is None else np.asarray(theta0, dtype='float64').copy()
@@ -193,7 +197,10 @@ def lbfgs(P, fit, maxiter=SETTINGS['maxiter'], history=HISTORY, ftol=FTOL, gtol=
 		for trial in range(MAX_TRIALS):
 			tn = theta + alpha * d
 			fn = objective(P, fit, tn, with_grad=False)
-			if np.isfinite(fn) and fn <= f + C1 * alpha * gtd:
+			accepted = bool(np.isfinite(fn) and fn <= f + C1 * alpha * gtd)
+			if trace is not None:
+				trace.setdefault('trials', []).append((float(fn), float(f + C1 * alpha * gtd), accepted))
+			if accepted:
 				break
 			alpha = alpha * 0.5
 		else:
@@ -202,6 +209,9 @@ def lbfgs(P, fit, maxiter=SETTINGS['maxiter'], history=HISTORY, ftol=FTOL, gtol=
 		fn, gn = objective(P, fit, tn)
 		s, y = tn - theta, gn - g
 		sy, yy = s @ y, y @ y
+		if trace is not None:
+			trace.setdefault('pairs', []).append((float(sy), float(PAIR_CURV * yy), bool(sy > PAIR_CURV * yy)))
+			trace.setdefault('stops', []).append((float(f - fn), float(ftol * max(abs(f), abs(fn), 1.0)), float(np.max(np.abs(gn)))))
 		if sy > PAIR_CURV * yy:
 			S.append(s); Y.append(y); SY.append(sy); YY.append(yy)
 			if len(S) > history:

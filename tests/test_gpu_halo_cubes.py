@@ -12,7 +12,10 @@ import halo_cubes_common as cc
 
 pytestmark = pytest.mark.gpu
 
-SHAPES = ((1, 1, 3), (3, 5, 63), (3, 5, 64), (3, 5, 65), (9, 13, 70), (11, 11, 130))
+#: the last two are the stamp limit: 45 x 46 = 2070 pixels (more than 2048 kept: float4 column 2 of the solver's backward kernel) and
+#: 64 x 64 = 4096, the largest stamp the entries take
+SHAPES = ((1, 1, 3), (3, 5, 63), (3, 5, 64), (3, 5, 65), (9, 13, 70), (11, 11, 130), (45, 46, 65), (64, 64, 70))
+LIMIT_SHAPES = SHAPES[-2:]
 PADS = (np.nan, 1e30)
 FLUX_ERR_RTOL = 4096 * 2.0**-53
 MINFLUX = -100.0
@@ -35,13 +38,14 @@ def _targets(shape, n_segs, seed):
 	images = rng.uniform(50, 1000, (n, H, W, T)).astype('float32')
 	masks = np.ones((n, H, W), dtype=bool)
 	if H * W > 1:
+		# (a cadence is lost with one bad value in any kept pixel: a large stamp gets fewer of them, so that about a quarter is lost)
 		for value in (np.nan, np.inf, -np.inf):
-			images[rng.random(images.shape) < 0.002] = value
+			images[rng.random(images.shape) < (0.002 if H * W <= 2048 else 0.1 / (H * W))] = value
 		flat = images.reshape(n, H * W, T)
 		flat[:, 1, :] = (-500.0 + rng.normal(size=(n, T))).astype('float32')                 # far below minflux: dropped
 		flat[:, 2, :] = (-100.0 + rng.normal(size=(n, T))).astype('float32')                 # scattered round minflux: by the median
 		flat[:, 3, : T // 2] = -300.0                                                        # below in the first half only
-		masks = rng.random((n, H, W)) < 0.85
+		masks = rng.random((n, H, W)) < (0.85 if H * W <= 2048 else 0.995)   # (a large stamp keeps more than 2048 pixels)
 		masks.reshape(n, -1)[:, :5] = True
 	quality = np.where(rng.random((n, T)) < 0.1, 32, 0).astype('int32')
 	segs = np.zeros((n, T), dtype='int64')
@@ -74,6 +78,8 @@ def test_tile_and_wave_edges(ctx, shape):
 	if shape[0] * shape[1] > 1:
 		assert any(len(p['pix']) < masks[i].sum() for i, per in enumerate(a) for p in per), 'no pixel was dropped: the case shows nothing'
 		assert any(len(p['cad']) < np.count_nonzero(segs[i] == k) for i, per in enumerate(a) for k, p in enumerate(per))
+	if shape in LIMIT_SHAPES:
+		assert any(len(p['pix']) > 2048 for per in a for p in per), [len(p['pix']) for per in a for p in per]
 
 
 def test_mixed_segment_counts(ctx):
@@ -239,7 +245,7 @@ def _hold_outputs(ctx, res, images, errs, args, label):
 	print(f"{label}: worst relative flux_err difference {worst:.3e} (bound {FLUX_ERR_RTOL:.3e})")
 
 
-@pytest.mark.parametrize('shape', ((3, 5, 65), (9, 13, 70)), ids=lambda s: 'x'.join(map(str, s)))
+@pytest.mark.parametrize('shape', ((3, 5, 65), (9, 13, 70)) + LIMIT_SHAPES, ids=lambda s: 'x'.join(map(str, s)))
 def test_outputs_equal_the_per_target_path(ctx, shape):
 	from photometry_amd import halo
 	images, errs, args = _group(shape, seed=17 + shape[2])

@@ -87,13 +87,17 @@ def test_select_and_gather_on_the_region(ctx):
 	assert checked == len(stamps)
 
 
-@pytest.mark.parametrize('ncad', NCAD)
-def test_select_and_gather_on_synthetic_stamps(ctx, ncad):
+#: (ncad, stamp side, mask sizes): the shapes of the solver's tests on 36 x 36 stamps, and the stamp limit: 64 x 64 = 4096 pixels with
+#: masks of 2049 pixels and of all of them, two segments of one full and one partial select tile each
+SYNTHETIC = [pytest.param(ncad, 36, NPIX, id=str(ncad)) for ncad in NCAD] + [pytest.param(130, 64, (2049, 4096), id='130-64x64')]
+
+
+@pytest.mark.parametrize('ncad,side,npixs', SYNTHETIC)
+def test_select_and_gather_on_synthetic_stamps(ctx, ncad, side, npixs):
 	from photometry_amd import halo
 	from photometry_amd.pipeline import FrameStack
 	rng = np.random.default_rng(ncad)
-	H = W = 36
-	npixs = NPIX
+	H = W = side
 	n = len(npixs)
 	R, C = H, W * n
 	images = rng.uniform(50, 1000, (ncad, R, C)).astype('float32')
@@ -129,6 +133,8 @@ def test_select_and_gather_on_synthetic_stamps(ctx, ncad):
 	_check_problems(fp, cubes, masks, quality, seg, f'synthetic T={ncad}')
 	print(f"synthetic T={ncad}: npix {fp.npix.tolist()} of masks {[int(m.sum()) for m in masks]}, ncad {fp.ncad.tolist()}")
 	assert np.any(fp.npix < np.array([m.sum() for m in masks])[:, None]) or ncad <= 3
+	if side == 64:
+		assert fp.npix.max() > 3072 and fp.ncad.min() > 32, (fp.npix.tolist(), fp.ncad.tolist())
 	fp.free()
 	stack.dev['images'].free()
 
